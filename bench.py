@@ -17,12 +17,15 @@ points to their owners inside the step (weak scaling).  Points per rank: 125 M a
 config 5, 10^9 points over [0,128)^3 - otherwise 10 M (`--points-per-rank` overrides; at N = 8 the
 10 M/rank point of the weak-scaling series is measured as well and reported under `secondary`).
 
-Prints ONE JSON line of under 8 KB on rank 0's stdout (contract in the task description) with `roofline`
-(dominant kernel, live hipEvent timings), `roofline_build` (dominant streaming kernel of insert+subdivide)
-and `cpu_baseline` (the NumPy port of the reference's algorithm, timed on this box's host on a
-bounded sample of the same workload).  The full result - secondaries, per-kernel tables, notes, the
-N > 1 topology and exchange blocks - goes to bench_detail.json beside this script and to stderr
-(`compact_line` / `emit` below).
+Prints ONE JSON line of under 8 KB on rank 0's stdout.  A plain run sets up, warms up, times --steps steps, writes
+the last step's outputs when --dump-outputs DIR is given, and prints the line:
+`metric`, `value` (Mpoints/s over the timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the
+workload's `config`.  Everything else is measured only with --full: `roofline` (dominant kernel, live hipEvent
+timings), `roofline_build` (dominant streaming kernel of insert+subdivide), `cpu_baseline` (the NumPy port of the
+reference's algorithm, timed on the benchmark's host on a bounded sample of the same workload), the per-kernel
+tables of an instrumented pass, host waits and launches per step, the secondaries, and at N > 1 the topology and exchange blocks
+with their checks.  The full result goes to bench_detail.json beside this script and to stderr (`compact_line` /
+`emit` below).
 """
 
 import argparse
@@ -155,8 +158,14 @@ def parse_args():
                     help="distinct clouds resident in HBM that the timed loop rotates over (default: 3 up to 20 M points "
                          "per GPU - two draws of the scene and one moved by a voxel, which the geometry hint of the "
                          "previous step does not fit - else 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline: roofline, per-kernel tables, host waits, "
+                         "CPU baseline, secondaries, N > 1 topology / exchange (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (leaf table in the reference's "
+                         "order, leaf of a fixed sample of the points) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements")
     ap.add_argument("--no-overlap", action="store_true",
                     help="route inside the step on the compute stream instead of one step ahead on a "
                          "second context (A/B)")
@@ -184,7 +193,10 @@ def parse_args():
                     help="one GPU: generate only the points rank 0 of R would own after routing (a "
                          "rank's shard of the R-rank scene, e.g. --shard-of 8 --points-per-rank 125000000 "
                          "= one rank of BASELINE config 5)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Workload:
@@ -745,12 +757,12 @@ def plan(args):
     gen_s_per_cloud = 0.9 * chunks / max(1, min(threads, (os.cpu_count() or 1) // max(1, world)))   # ~0.9 s per 10 M-point chunk and thread
     ms_step = 4.5 * n_local / 1e7 * (1.0 if n_local <= 10_500_000 else 1.0)   # ~4.5 ms per 10 M points (RANSAC bound)
     timed_s = (args.steps + args.warmup + 12) * ms_step / 1e3
-    secondaries_s = 0.0 if args.no_secondary else 24 * 4.5e-3 + 2 * (0.9 + 1.0)   # 10 M / rank + strong series: two more clouds
+    secondaries_s = 0.0 if (args.no_secondary or not args.full) else 24 * 4.5e-3 + 2 * (0.9 + 1.0)   # 10 M / rank + strong series: two more clouds
     import_s, comm_s = 90.0, 20.0
     wall = import_s + comm_s + n_clouds * gen_s_per_cloud + timed_s + secondaries_s
     out = {
         "plan_for": f"python bench.py --gpus {world} --steps {args.steps} --warmup {args.warmup}"
-                    + (" --scaling strong" if strong else ""),
+                    + (" --scaling strong" if strong else "") + (" --full" if args.full else ""),
         "ranks": world, "points_per_rank": n_local, "total_points": n_local * world, "resident_clouds_per_rank": n_clouds,
         "host": {"cpu_count_here": os.cpu_count(), "generator_threads_per_rank": threads,
                  "ram_GB_per_rank_peak_estimate": round(host_gb_rank, 1),
@@ -767,6 +779,109 @@ def plan(args):
                 "~0.9 s per 10 M-point chunk and thread, ~4.5 ms of step per 10 M points); no GPU was touched",
     }
     print(json.dumps(out))
+
+
+def headline_result(args, world, n_local, dims, dt, shape, n_alive_after, n_clouds, strong, dense, overlap):
+    """The headline of the run: the contract's keys and the workload's configuration.  `shape` = (leaves, nodes,
+    levels) of the last timed step's build."""
+    leaves, nodes, levels = shape
+    if dense and world == 8:
+        what = "BASELINE config 5: 10^9 points, "
+    elif world == 1 and n_local == 10_000_000 and not args.shard_of:
+        what = "BASELINE config 3: "
+    else:
+        what = ""
+    return {
+        "metric": "Mpoints/s insert+subdivide+RANSAC",
+        "value": n_local * world * args.steps / dt / 1e6,
+        "unit": "Mpoints/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": what + f"Grid 1 m voxels, {n_local} {args.cloud} points per GPU "
+                        f"(scene {dims[0]}x{dims[1]}x{dims[2]} voxels), insert + subdivide(len>{args.k_split}) + "
+                        f"map_leaf_points_cuda_ransac(H=1024, k=6, thr=0.01, poses_per_batch=10) "
+                        f"incl. apply_mask"
+                        + (", sharded by top-level voxel with one RCCL all-to-all" if world > 1 else "")
+                        + (f", STRONG scaling: {n_local * world} points in total" if strong else "")
+                        + (f", one rank's shard of a {args.shard_of}-rank scene" if args.shard_of > 1 else "")
+                        + (" routed one step ahead on a second stream" if overlap else ""),
+            "points_per_gpu": n_local,
+            "K": args.k_split,
+            "hypotheses": H,
+            "leaves": leaves,
+            "nodes": nodes,
+            "levels": levels,
+            "points_after_ransac": n_alive_after,
+            "clouds_note": f"the timed loop rotates over {n_clouds} distinct clouds resident in HBM "
+                           "(leaves / nodes / points_after_ransac above: the last step's cloud)"
+                           if n_clouds > 1 else "one resident cloud, inserted again every step",
+        },
+    }
+
+
+# --dump-outputs: bounds of what is written (all float64, at most 52 MB together)
+DUMP_LEAVES = 750_000     # leaves written whole up to this many, else a fixed seeded sample of them
+DUMP_POINTS = 1_000_000   # input points whose leaf is written: a fixed seeded sample of the step's cloud
+DUMP_SEED = 20251016
+
+
+def dump_outputs(wl, out_dir, n_in, cloud):
+    """What the last timed step computed, as a caller of Grid.insert_points + subdivide + map_leaf_points_cuda_ransac
+    receives it (Grid.get_leaf_points): the non-empty leaves in the reference's order with corner, edge and the number
+    of points RANSAC left in them, and for a fixed sample of the step's `n_in` input points the position (in that
+    order) of the leaf that holds the point, -1 when RANSAC dropped it.  Nothing in it depends on node numbering or on
+    the storage order of the blocks, so two builds of the library can be compared file by file.  Written as
+    out_dir/<name>.npy, float64:
+      leaf_index (m)    positions of the written leaves in the reference's order (all of them up to DUMP_LEAVES)
+      leaf_corner (m,3), leaf_edge (m), leaf_points (m)
+      point_index (k)   sampled indices into the step's cloud (ascending), point_leaf (k)"""
+    ctx, lib, fh = wl.ctx, wl.lib, wl.fh
+    n = C.c_int64(0)
+    ctx.check(lib.octl_forest_get_blocks(fh, 0, None, None, None, None, C.byref(n)))
+    nb = n.value
+    node, start, size = np.empty(nb, np.int32), np.empty(nb, np.int64), np.empty(nb, np.int32)
+    ctx.check(lib.octl_forest_get_blocks(fh, nb, nat.ptr(node), None, nat.ptr(start), nat.ptr(size), C.byref(n)))
+    order = np.empty(nb, np.int32)
+    ctx.check(lib.octl_forest_reference_order(fh, nat.ptr(wl.e0), len(wl.e0), nb, nat.ptr(order), C.byref(n)))
+    ctx.check(lib.octl_forest_get_nodes(fh, 0, None, None, None, None, None, None, None, C.byref(n)))
+    corner, edge = np.empty((n.value, 3)), np.empty(n.value)
+    ctx.check(lib.octl_forest_get_nodes(fh, n.value, None, None, None, None, nat.ptr(corner), nat.ptr(edge), None,
+                                        C.byref(n)))
+    ctx.check(lib.octl_forest_get_perm(fh, 0, None, C.byref(n)))
+    perm = np.empty(n.value, np.int64)
+    ctx.check(lib.octl_forest_get_perm(fh, n.value, nat.ptr(perm), C.byref(n)))
+    sizes = size.astype(np.int64)
+    if sizes.sum() != len(perm) or (len(perm) and not 0 <= perm.min() <= perm.max() < n_in):
+        raise RuntimeError(f"--dump-outputs: {sizes.sum()} rows in the block table, {len(perm)} in the permutation, "
+                           f"{n_in} input points")
+
+    rank = np.empty(nb, np.int64)        # block -> its position in the reference's order
+    rank[order] = np.arange(nb)
+    rows = np.repeat(start - (np.cumsum(sizes) - sizes), sizes) + np.arange(len(perm))   # storage row of each block row
+    point_leaf = np.full(n_in, -1, np.int64)
+    point_leaf[perm[rows]] = np.repeat(rank, sizes)
+
+    rng = np.random.default_rng(DUMP_SEED)
+    leaf_index = np.arange(nb) if nb <= DUMP_LEAVES else np.sort(rng.choice(nb, DUMP_LEAVES, replace=False))
+    point_index = np.arange(n_in) if n_in <= DUMP_POINTS else np.sort(rng.choice(n_in, DUMP_POINTS, replace=False))
+    blk = order[leaf_index]
+    arrays = {
+        "leaf_index": leaf_index, "leaf_corner": corner[node[blk]], "leaf_edge": edge[node[blk]],
+        "leaf_points": sizes[blk], "point_index": point_index, "point_leaf": point_leaf[point_index],
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    print(f"bench.py: outputs of the last timed step (cloud {cloud}: {nb} leaves, {len(perm)} of {n_in} points kept) "
+          f"-> {out_dir}", file=sys.stderr)
 
 
 def main():
@@ -883,17 +998,41 @@ def main():
     # Inside the timed region only the DOMINANT kernel (RANSAC scoring) is timed with hipEvents on its own
     # stream, as the roofline needs it; every event pair drains the pipeline for ~10 us, so the other
     # kernels' durations come from a second, fully instrumented pass of a few steps behind the timed region.
+    # A plain run (no --full) times the step alone: no hipEvent pair inside the timed region.
     wl.run(args.warmup)
-    ctx.set_profiling(2)
+    if args.full:
+        ctx.set_profiling(2)
     barrier()
     wl.tick = 0   # (the timed region starts with cloud 0: which cloud got how many steps is known)
     t0 = time.perf_counter()
     wl.run(args.steps)
     barrier()
     dt = time.perf_counter() - t0
-    live = ctx.timings()
+    live = ctx.timings() if args.full else {}
     ctx.set_profiling(False)
     dt = max_over_ranks(dt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs, int(wl.n_recv.value) if route else n_local, (args.steps - 1) % n_clouds)
+
+    def shutdown():
+        wl.close()
+        if route:
+            lib.octl_comm_destroy(rctx.handle)
+        if world > 1:
+            dist.destroy_process_group()
+        if rctx is not ctx:
+            rctx.close()
+        ctx.close()
+
+    if not args.full:
+        wl.settle()
+        if rank == 0:
+            shape = (int(wl.info.n_blocks), int(wl.info.n_nodes), int(wl.info.n_levels))
+            emit(headline_result(args, world, n_local, dims, dt, shape, int(wl.n_alive.value), n_clouds, strong, dense,
+                                 overlap), args.detail)
+        shutdown()
+        return
+
     prof_steps = max(2, min(args.steps, 5))
     ctx.set_profiling(True)
     if rctx is not ctx:
@@ -1332,9 +1471,6 @@ def main():
         }
 
     if rank == 0:
-        total_points = n_local * world
-        ms_per_step = dt / args.steps * 1e3
-        value = total_points * args.steps / dt / 1e6
         kern = {k: {"ms_avg": v[0] / max(v[1], 1), "launches_per_step": v[1] / args.steps,
                     "ms_per_step": v[0] / args.steps} for k, v in timings.items()}
         dom = max(kern, key=lambda k: kern[k]["ms_per_step"])
@@ -1359,49 +1495,13 @@ def main():
         valu_tflops = flops / (ransac_ms * 1e-3) / 1e12 if ransac_ms else None
         # insert + subdivide: per-kernel table (three figures each) and the dominant streaming kernel
         roofline_build = build_summary(kern, n_step, "headline")
-        if dense and world == 8:
-            what = "BASELINE config 5: 10^9 points, "
-        elif world == 1 and n_local == 10_000_000 and not args.shard_of:
-            what = "BASELINE config 3: "
-        else:
-            what = ""
-        out = {
-            "metric": "Mpoints/s insert+subdivide+RANSAC",
-            "value": value,
-            "unit": "Mpoints/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
+        out = headline_result(args, world, n_local, dims, dt, (leaves, nodes, levels), n_alive_after, n_clouds, strong,
+                              dense, overlap)
+        out["config"]["clouds"] = per_cloud
+        out.update({
             "host_syncs_per_step": host_syncs,
             "launches_per_step": launches,
             "speculative_finish": spec_finish,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": what + f"Grid 1 m voxels, {n_local} {args.cloud} points per GPU "
-                            f"(scene {dims[0]}x{dims[1]}x{dims[2]} voxels), insert + subdivide(len>{args.k_split}) + "
-                            f"map_leaf_points_cuda_ransac(H=1024, k=6, thr=0.01, poses_per_batch=10) "
-                            f"incl. apply_mask"
-                            + (", sharded by top-level voxel with one RCCL all-to-all" if world > 1 else "")
-                            + (f", STRONG scaling: {n_local * world} points in total" if strong else "")
-                            + (f", one rank's shard of a {args.shard_of}-rank scene" if args.shard_of > 1 else "")
-                            + (" routed one step ahead on a second stream" if overlap else ""),
-                "points_per_gpu": n_local,
-                "K": args.k_split,
-                "hypotheses": H,
-                "leaves": leaves,
-                "nodes": nodes,
-                "levels": levels,
-                "points_after_ransac": n_alive_after,
-                "clouds": per_cloud,
-                "clouds_note": f"the timed loop rotates over {n_clouds} distinct clouds resident in HBM "
-                               "(leaves / nodes / points_after_ransac above: the last step's cloud)"
-                               if n_clouds > 1 else "one resident cloud, inserted again every step",
-            },
             "roofline": {
                 "kernel": dom,
                 "bound": "hbm",
@@ -1447,7 +1547,7 @@ def main():
             "kernels_note": "ransac: hipEvents inside the timed region (live); the others: the same step "
                             "fully instrumented for a few steps behind the timed region (an event pair costs "
                             "~10 us of pipeline, a dozen per step would be 2 % of the step)",
-        }
+        })
         if topology is not None:
             out["rccl_ranks"] = topology["rccl_ranks"]
             out["topology"] = topology
@@ -1460,14 +1560,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(scene_dims(1, False), wl.table)
         emit(out, args.detail)
 
-    wl.close()
-    if route:
-        lib.octl_comm_destroy(rctx.handle)
-    if world > 1:
-        dist.destroy_process_group()
-    if rctx is not ctx:
-        rctx.close()
-    ctx.close()
+    shutdown()
 
 
 # ---- what goes on stdout ------------------------------------------------------------------------------------------
@@ -1500,7 +1593,8 @@ def compact_line(full):
     line = _pick(full, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                         "scaling", "vs_baseline", "dtype", "data"))
     line["config"] = _pick(cfg, ("workload", "points_per_gpu", "K", "hypotheses", "leaves"))
-    line["roofline"] = _pick(full.get("roofline"), ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
+    if full.get("roofline"):   # (--full only, like the blocks below)
+        line["roofline"] = _pick(full["roofline"], ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
                                                     "launch_ms"))
     rv = full.get("roofline_valu")
     if rv:

@@ -44,7 +44,7 @@ def test_bench_gpus_n_through_the_stand_in(ranks, tmp_path):
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     line, err, detail = str(tmp_path / "line.json"), str(tmp_path / "err.txt"), str(tmp_path / "detail.json")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--points-per-rank", str(pts), "--no-cpu-baseline", "--detail", detail]
+           "--points-per-rank", str(pts), "--full", "--no-cpu-baseline", "--detail", detail]
     parent, child = mp.Pipe()
     p = mp.Process(target=_run_bench, args=(cmd, env, line, err, child), daemon=True)
     p.start()

@@ -1,18 +1,18 @@
 #!/bin/bash
 # Collect the profiles kept under profiles/ (run on the GPU box through gpurun):
 #   tools/profile_round.sh TAG      e.g. TAG=r03
-# Every rocprofv3 pass profiles the HEADLINE scene only (bench.py --no-secondary --no-cpu-baseline: the timed
+# Every rocprofv3 pass profiles the HEADLINE scene only (bench.py --full --no-secondary --no-cpu-baseline: the timed
 # region of BASELINE config 3 and nothing else), so that the per-kernel averages of the tracked files are the
 # headline's own - the secondaries (uniform scene, two streams, Python API ...) launch the same kernels on other
 # inputs and used to be averaged in.
-# 1. (last, see 6.) full default bench.py run                   -> profiles/TAG_bench.json
+# 1. (last, see 6.) bench.py --full run                         -> profiles/TAG_bench.json
 # 2. rocprofv3 --kernel-trace --stats of the headline-only run    -> profiles/TAG_kernel_stats.csv
 # 3. separate --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ counters), as MI355X_MICROARCH.md asks
 # 4. the same kernel-stats pass on the uniform scene               -> profiles/TAG_uniform_kernel_stats.csv
 # then tools/summarize_profiles.py condenses them into profiles/TAG_*.
 TAG=${1:-r06}
 R=${GRAFT_REPO_ROOT:-$PWD}
-HEAD="--no-secondary --no-cpu-baseline"
+HEAD="--full --no-secondary --no-cpu-baseline"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$TAG -- python3 $R/bench.py --steps 20 --warmup 3 $HEAD > $R/gpurun_out/prof_${TAG}_bench.json 2> $R/gpurun_out/prof_$TAG.err || exit 2
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/pmc_fetch_$TAG -- python3 $R/bench.py --steps 3 --warmup 1 $HEAD > /dev/null 2>&1 || exit 3
@@ -44,9 +44,10 @@ if [ -z "$OCTL_PROFILE_HEADLINE_ONLY" ]; then
   done
   cd $R
 fi
-# 6. the full default bench.py run LAST: its counter figures (roofline.traffic, roofline_build) are read from the
+# 6. the bench.py --full run LAST: its counter figures (roofline.traffic, roofline_build) are read from the
 #    profiles/TAG_* files the passes above have just written
-cd /tmp && python3 $R/bench.py --detail $R/gpurun_out/${TAG}_bench_detail.json > $R/gpurun_out/${TAG}_bench.json 2> $R/gpurun_out/${TAG}_bench.err || exit 1
-cd $R && cp gpurun_out/${TAG}_bench.json profiles/${TAG}_bench.json && cp gpurun_out/${TAG}_bench_detail.json profiles/${TAG}_bench_detail.json
+T=$(mktemp -d)
+cd /tmp && python3 $R/bench.py --full --detail $T/bench_detail.json > $T/bench.json 2> $T/bench.err || { tail -50 $T/bench.err >&2; exit 1; }
+cd $R && cp $T/bench.json profiles/${TAG}_bench.json && cp $T/bench_detail.json profiles/${TAG}_bench_detail.json
 # profiles/ is not writable back from the box: the condensed files are copied to gpurun_out/ too
 mkdir -p gpurun_out/profiles_$TAG && cp profiles/${TAG}_* gpurun_out/profiles_$TAG/

@@ -14,7 +14,7 @@ export OCTL_RCCL_LIBRARY=$PWD/tests/rccl_stub/librccl_stub.so OCTL_BENCH_DEVICE=
 mkdir -p gpurun_out
 for MODE in weak strong; do
   DETAIL=gpurun_out/bench_n${N}_${MODE}_detail.json
-  timeout -k 10 500 python bench.py --gpus $N --steps 3 --warmup 1 --points-per-rank $PTS --no-cpu-baseline --scaling $MODE \
+  timeout -k 10 500 python bench.py --gpus $N --steps 3 --warmup 1 --points-per-rank $PTS --full --no-cpu-baseline --scaling $MODE \
     --detail $DETAIL > gpurun_out/bench_n${N}_$MODE.json 2> gpurun_out/bench_n${N}_$MODE.err
   echo "$MODE: rc=$? stdout lines: $(wc -l < gpurun_out/bench_n${N}_$MODE.json) bytes: $(wc -c < gpurun_out/bench_n${N}_$MODE.json)"
   python tools/check_rehearsal.py gpurun_out/bench_n${N}_$MODE.json $DETAIL $N $MODE $PTS || exit 1
