@@ -131,6 +131,23 @@ int octl_forest_extend_pose(octl_forest* f, int32_t slot, const double* xyz, int
 /* Same, from a device pointer (device-to-device copy; ordered behind an octl_dev_upload_async into it).  */
 int octl_forest_extend_pose_device(octl_forest* f, int32_t slot, const double* xyz_dev, int64_t n);
 
+/* float32 clouds (row-major (n,3) float).  The reference upcasts every cloud to f64 before any arithmetic
+ * (internal/voxel.py:81-83: np.vstack onto an f64 array; the grid's voxel corners are f64), and f32 -> f64 is exact:
+ * each entry below leaves the forest exactly as its f64 counterpart leaves it for the widened cloud - store, tables,
+ * counts, errors.  The widening runs on the device (12 B per point cross PCIe instead of 24); the store stays f64.  */
+/* Grid.insert_points (grid/grid.py:58-109), OctreeManager.insert_points (octree_manager.py:161-171) and
+ * Octree.insert_points (octree/octree.py:235-239) of an f32 host cloud: octl_forest_add_pose.  The host buffer is
+ * the caller's again when the call returns.                                                                    */
+int octl_forest_add_pose_f32(octl_forest* f, const float* xyz, int64_t n, int32_t* slot);
+/* The same from a device pointer: octl_forest_add_pose_device (consumed in stream order, ordered behind an
+ * octl_dev_upload_async into it).  Never read in place: the points are widened into the forest's own store.    */
+int octl_forest_add_pose_device_f32(octl_forest* f, const float* xyz_dev, int64_t n, int32_t* slot);
+/* OctreeManager.insert_points on an existing pose (octree_manager.py:161-171), Octree.insert_points
+ * (octree/octree.py:235-239): octl_forest_extend_pose for an f32 host cloud.                                    */
+int octl_forest_extend_pose_f32(octl_forest* f, int32_t slot, const float* xyz, int64_t n);
+/* The same from a device pointer: octl_forest_extend_pose_device.                                              */
+int octl_forest_extend_pose_device_f32(octl_forest* f, int32_t slot, const float* xyz_dev, int64_t n);
+
 typedef struct octl_build_info {
   int64_t n_points;     /* alive points that were placed                                   */
   int64_t n_voxels;     /* top-level voxels (roots)                                        */

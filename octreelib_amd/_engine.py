@@ -80,6 +80,15 @@ class Forest:
     def add_pose(self, points) -> int:
         from octreelib_amd.feed import DeviceCloud
 
+        if isinstance(points, DeviceCloud) and points.dtype == np.float32:
+            # an f32 cloud on the device: widened into the store by the library, never read in place; kept alive
+            # until the copy has been consumed (the next synchronising call)
+            slot = C.c_int32(-1)
+            self.ctx.check(self.lib.octl_forest_add_pose_device_f32(self.handle, points.ptr, points.n, C.byref(slot)))
+            self._device_clouds.append(points)
+            self._in_place = None
+            self._register_slot(points.n)
+            return slot.value
         if isinstance(points, DeviceCloud):
             # a cloud that is (being) uploaded already: read in place when it is the first pose, copied on
             # the device otherwise; the forest keeps the object alive while it reads its buffer
@@ -94,9 +103,10 @@ class Forest:
             else:
                 self._in_place = None   # (the store grew: it is the forest's own now)
             return slot
-        pts = nat.as_points(points)
+        pts = nat.as_points_native(points)   # (f32 stays f32: the library widens it on the device)
         slot = C.c_int32(-1)
-        self.ctx.check(self.lib.octl_forest_add_pose(self.handle, nat.ptr(pts), len(pts), C.byref(slot)))
+        fn = self.lib.octl_forest_add_pose_f32 if pts.dtype == np.float32 else self.lib.octl_forest_add_pose
+        self.ctx.check(fn(self.handle, nat.ptr(pts), len(pts), C.byref(slot)))
         self._in_place = None
         self._register_slot(len(pts))
         return slot.value
@@ -129,12 +139,15 @@ class Forest:
 
         if isinstance(points, DeviceCloud):
             # appended device-to-device behind the pose's points (the library orders the copy behind the upload)
-            self.ctx.check(self.lib.octl_forest_extend_pose_device(self.handle, slot, points.ptr, points.n))
+            fn = (self.lib.octl_forest_extend_pose_device_f32 if points.dtype == np.float32
+                  else self.lib.octl_forest_extend_pose_device)
+            self.ctx.check(fn(self.handle, slot, points.ptr, points.n))
             self._device_clouds.append(points)   # (alive until the copy has been consumed by the next build)
             n_new = points.n
         else:
-            pts = nat.as_points(points)
-            self.ctx.check(self.lib.octl_forest_extend_pose(self.handle, slot, nat.ptr(pts), len(pts)))
+            pts = nat.as_points_native(points)
+            fn = self.lib.octl_forest_extend_pose_f32 if pts.dtype == np.float32 else self.lib.octl_forest_extend_pose
+            self.ctx.check(fn(self.handle, slot, nat.ptr(pts), len(pts)))
             n_new = len(pts)
         self._in_place = None
         self.slot_sizes[slot] += n_new

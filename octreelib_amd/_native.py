@@ -69,6 +69,10 @@ SIGNATURES = {
     "octl_forest_set_contents": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
     "octl_forest_extend_pose": (C.c_int, [_p, _i32, _p, _i64]),
     "octl_forest_extend_pose_device": (C.c_int, [_p, _i32, _p, _i64]),
+    "octl_forest_add_pose_f32": (C.c_int, [_p, _p, _i64, _pi32]),
+    "octl_forest_add_pose_device_f32": (C.c_int, [_p, _p, _i64, _pi32]),
+    "octl_forest_extend_pose_f32": (C.c_int, [_p, _i32, _p, _i64]),
+    "octl_forest_extend_pose_device_f32": (C.c_int, [_p, _i32, _p, _i64]),
     "octl_forest_build": (C.c_int, [_p, _i64, _p, _i32, _i32, _i32, C.POINTER(BuildInfo)]),
     "octl_forest_set_scheme": (C.c_int, [_p, _p, _p, _i64, _i32]),
     "octl_forest_get_nodes": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _pi64]),
@@ -300,6 +304,20 @@ def as_points(points) -> np.ndarray:
     """(n,3) C-contiguous float64 — the reference upcasts every input to f64
     (internal/voxel.py:81-83, octree.py:100)."""
     a = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+    if a.size == 0:
+        return a.reshape(0, 3)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"expected an (n, 3) point cloud, got shape {a.shape}")
+    return a
+
+
+def as_points_native(points) -> np.ndarray:
+    """as_points, except that a float32 NumPy array stays float32: (n,3) C-contiguous f32 (strided and Fortran-ordered
+    views are copied, still in f32).  The library widens such a cloud on the device, exactly ((double)v), to what
+    as_points would have produced on the host - half the bytes over PCIe.  Anything else goes through as_points."""
+    if not (isinstance(points, np.ndarray) and points.dtype == np.float32):
+        return as_points(points)
+    a = np.ascontiguousarray(points)
     if a.size == 0:
         return a.reshape(0, 3)
     if a.ndim != 2 or a.shape[1] != 3:

@@ -161,6 +161,9 @@ struct octl_ctx {
   // cuda_ransac.py:39-41, and a loop over scans hands the same one over for every scan - to a fresh forest each
   // time): kept per CONTEXT so that it is uploaded once
   DevBuf hyp_dev;
+  // device staging of host float32 clouds (octl_forest_add_pose_f32 / _extend_pose_f32): the upload lands here and
+  // the ingest kernel widens it into the forest's f64 store; kept between calls so that a scan loop does no hipMalloc
+  DevBuf f32_stage;
   // launch counters of ransac.hip's preparation: two sets used alternately (a launch zeroes the next one's)
   DevBuf rs_counters;
   int rs_parity = 0;

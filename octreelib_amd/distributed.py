@@ -89,7 +89,7 @@ class ShardedGrid:
         the right context): hand the result to insert_points while the previous pose is still being built."""
         from octreelib_amd.feed import DeviceCloud
 
-        return DeviceCloud(points, ctx=self.ctx)
+        return DeviceCloud(nat.as_points(points), ctx=self.ctx)   # (the routing kernels read f64 clouds only)
 
     def insert_points(self, points, index_base: int = 0) -> int:
         """Route this rank's part of a pose to the owners and insert what this rank receives.
@@ -102,9 +102,11 @@ class ShardedGrid:
         if isinstance(points, DeviceCloud):
             if points.ctx is not self.ctx:
                 raise ValueError("the DeviceCloud lives on another context: use ShardedGrid.upload_async")
+            if points.dtype != np.float64:
+                raise ValueError("the routed path takes f64 clouds only: use ShardedGrid.upload_async")
             cloud, own = points, False
         else:
-            cloud, own = DeviceCloud(points, ctx=self.ctx), True
+            cloud, own = DeviceCloud(nat.as_points(points), ctx=self.ctx), True
         n_recv = C.c_int64(0)
         self.ctx.check(self.lib.octl_route_points(self.ctx.handle, cloud.ptr, None, cloud.n, int(index_base),
                                                   nat.ptr(self._corner), self.L, C.byref(n_recv), None))

@@ -18,7 +18,8 @@ previous scan:
         cur.release()
 
 Plain NumPy arrays work too (the copy then blocks the caller while HIP stages the pageable memory; it still
-overlaps device work that was enqueued before).
+overlaps device work that was enqueued before).  float32 clouds (pinned_empty((n, 3), np.float32)) are uploaded as
+f32 - 12 bytes per point instead of 24 - and widened exactly into the grid's f64 store on the device.
 """
 
 import ctypes as C
@@ -53,15 +54,19 @@ def _free_pinned(ctx, address):
 
 
 class DeviceCloud:
-    """An (n, 3) f64 cloud on its way into (or already in) device memory.  Grid.insert_points /
+    """An (n, 3) f64 or f32 cloud on its way into (or already in) device memory.  Grid.insert_points /
     OctreeManager.insert_points / Octree.insert_points take it in place of the host array: the first pose of
-    an empty grid reads the device buffer in place (octl_forest_add_pose_adopt), any other pose copies it
-    device-to-device.  The object owns the device buffer: keep it alive while a grid reads it in place."""
+    an empty grid reads an f64 device buffer in place (octl_forest_add_pose_adopt), any other pose copies it
+    device-to-device.  A float32 NumPy array stays f32 (`dtype`, 12 bytes per point uploaded): the library widens
+    it exactly into the grid's f64 store when it is inserted, so it is never read in place.  The object owns the
+    device buffer: keep it alive while a grid reads it in place."""
 
     def __init__(self, points, ctx=None):
         self.ctx = ctx if ctx is not None else nat.get_context()
-        pts = nat.as_points(points)
+        pts = nat.as_points_native(points)
         self.n = len(pts)
+        self.dtype = pts.dtype
+        self.nbytes = pts.nbytes
         self._host = pts  # must stay unchanged until the upload has finished
         self._readers = []  # weak references to the forests that read the buffer in place
         self.ptr = C.c_void_p()
@@ -109,8 +114,10 @@ class _StagedCloud(DeviceCloud):
     """A scan in one of the pipeline's device staging buffers: fully uploaded before a worker sees it; release()
     hands the buffer back to the uploader instead of freeing it."""
 
-    def __init__(self, ctx, ptr, n, give_back):
+    def __init__(self, ctx, ptr, n, give_back, dtype=np.float64):
         self.ctx, self.ptr, self.n = ctx, ptr, int(n)
+        self.dtype = np.dtype(dtype)
+        self.nbytes = self.n * 3 * self.dtype.itemsize
         self._host = None
         self._readers = []
         self._give_back = give_back
@@ -197,7 +204,7 @@ class ScanPipeline:
                         cloud = points
                         self._free.put(b)
                     else:
-                        pts = nat.as_points(points)
+                        pts = nat.as_points_native(points)   # (an f32 scan is staged as f32: half the upload)
                         if pts.nbytes > bufs[b][1]:
                             if bufs[b][0].value:
                                 ctx.check(lib.octl_dev_free(ctx.handle, bufs[b][0]))
@@ -206,7 +213,7 @@ class ScanPipeline:
                             bufs[b][1] = max(pts.nbytes, 16)
                         ctx.check(lib.octl_dev_upload_async(ctx.handle, bufs[b][0], nat.ptr(pts), pts.nbytes))
                         ctx.check(lib.octl_ctx_sync_uploads(ctx.handle))   # this thread waits, nobody else does
-                        cloud = _StagedCloud(ctx, bufs[b][0], len(pts), lambda b=b: self._free.put(b))
+                        cloud = _StagedCloud(ctx, bufs[b][0], len(pts), lambda b=b: self._free.put(b), pts.dtype)
                 except BaseException as e:
                     self._free.put(b)
                     fut.set_exception(e)
