@@ -221,6 +221,15 @@ int octl_forest_get_points(octl_forest* f, int64_t start, int64_t count, double*
  * in block_ids.                                                                                                */
 int octl_forest_gather_blocks(octl_forest* f, const int32_t* block_ids, int64_t m, int64_t cap, double* xyz,
                               int64_t* n_points);
+/* Per-(leaf, pose) point statistics over the blocks block_ids[0..nb) (indices into the block table), outputs
+ * indexed like block_ids, any may be NULL: count (nb) i64, mean (nb,3), cov (nb,6) upper triangle xx xy xz yy yz zz
+ * of the population covariance, eigval (nb,3) ascending, eigvec (nb,3,3) columns = eigenvectors. Read-only: the
+ * forest, its caches, a pending RANSAC mask are untouched. OCTL_E_STATE before the first build, OCTL_E_INVALID for an
+ * id outside [0, n_blocks).                                                                                       */
+int octl_forest_leaf_stats(octl_forest* f, const int32_t* block_ids, int64_t nb, int64_t* count, double* mean,
+                           double* cov, double* eigval, double* eigvec);
+/* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
+int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 
 /* ---- RANSAC on the forest (device resident) ------------------------------------------- */
 

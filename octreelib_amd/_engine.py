@@ -509,6 +509,24 @@ class Forest:
             raise RuntimeError(f"gather_blocks: {got.value} rows on the device, {n} in the host's block table")
         return out
 
+    def leaf_stats(self, block_ids, eigen: bool = True):
+        """Point count, mean, population covariance and (eigen=True) its eigen-decomposition of every given block,
+        computed on the device in one call (octl_forest_leaf_stats): a LeafStatistics whose row i describes
+        block_ids[i].  With eigen=False its eigenvalues / eigenvectors are None."""
+        from octreelib_amd.leaf_stats import LeafStatistics, cov6_to_full
+
+        ids = np.ascontiguousarray(block_ids, dtype=np.int32).reshape(-1)
+        self.ensure_built()
+        n = len(ids)
+        count = np.empty(n, dtype=np.int64)
+        mean = np.empty((n, 3), dtype=np.float64)
+        cov = np.empty((n, 6), dtype=np.float64)
+        w = np.empty((n, 3), dtype=np.float64) if eigen else None
+        v = np.empty((n, 3, 3), dtype=np.float64) if eigen else None
+        self.ctx.check(self.lib.octl_forest_leaf_stats(self.handle, nat.ptr(ids), n, nat.ptr(count), nat.ptr(mean),
+                                                       nat.ptr(cov), nat.ptr(w), nat.ptr(v)))
+        return LeafStatistics(count, mean, cov6_to_full(cov), w, v)
+
     @property
     def perm(self) -> np.ndarray:
         """perm[i] = index (in the concatenation of all pose clouds, slot order) of the point at

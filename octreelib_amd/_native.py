@@ -84,6 +84,7 @@ SIGNATURES = {
     "octl_forest_get_perm": (C.c_int, [_p, _i64, _p, _pi64]),
     "octl_forest_get_points": (C.c_int, [_p, _i64, _i64, _p]),
     "octl_forest_gather_blocks": (C.c_int, [_p, _p, _i64, _i64, _p, _pi64]),
+    "octl_forest_leaf_stats": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _p]),
     "octl_forest_ransac": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, _f64, _p, _p, _p]),
     "octl_forest_reference_order": (C.c_int, [_p, _p, _i32, _i64, _p, _pi64]),
     "octl_forest_ransac_all": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _f64]),
@@ -128,6 +129,7 @@ SIGNATURES = {
     "octl_debug_radix_sort": (C.c_int, [_p, _p, _p, _i64, C.c_int]),
     "octl_debug_plane_arith": (C.c_int, [_p, _p, _p, _p, C.c_int32, _i64, _p, _p, _p]),
     "octl_debug_plane_arith_certified": (C.c_int, [_p, _p, _p, _p, C.c_int32, _i64, _p, _p, _p]),
+    "octl_debug_sym3_eigen": (C.c_int, [_p, _p, _i64, _p, _p]),
 }
 
 _lib = None

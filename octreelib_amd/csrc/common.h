@@ -164,6 +164,9 @@ struct octl_ctx {
   // device staging of host float32 clouds (octl_forest_add_pose_f32 / _extend_pose_f32): the upload lands here and
   // the ingest kernel widens it into the forest's f64 store; kept between calls so that a scan loop does no hipMalloc
   DevBuf f32_stage;
+  // octl_forest_leaf_stats / octl_debug_sym3_eigen (leaf_stats.hip): block ids, outputs, claim words, chunk work
+  // items and chunk partials of one call; kept between calls
+  DevBuf ls_buf;
   // launch counters of ransac.hip's preparation: two sets used alternately (a launch zeroes the next one's)
   DevBuf rs_counters;
   int rs_parity = 0;

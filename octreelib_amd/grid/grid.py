@@ -17,6 +17,7 @@ from octreelib_amd._engine import Forest
 from octreelib_amd.criteria import try_count_threshold
 from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, VisualizationConfig
 from octreelib_amd.internal.voxel import Voxel
+from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 
 __all__ = ["Grid", "GridConfig"]
 
@@ -87,6 +88,16 @@ class Grid(GridBase):
         if self._plug is not None:
             return self._plug.get_leaf_points(pose_number, non_empty)
         return _views.leaf_views(self._forest, self._slots[pose_number], non_empty)
+
+    def leaf_statistics(self, pose_number: int) -> LeafStatistics:
+        """Count, mean, covariance and its eigen-decomposition (least-squares plane) of every non-empty leaf of a
+        pose: row i describes get_leaf_points(pose_number)[i].  One device call over the pose's blocks; a grid on
+        the caller's own plug types computes it on the host from get_leaf_points.  KeyError for an unknown pose."""
+        if self._plug is not None:
+            return leaf_statistics_of_leaves(self._plug.get_leaf_points(pose_number, True))
+        slot = self._slots[pose_number]
+        self._forest.ensure_built()
+        return self._forest.leaf_stats(self._forest.slot_blocks(slot))
 
     # grid.py:234-242: all managers in first-creation order, DFS order inside a manager
     def get_points(self, pose_number: int):

@@ -14,6 +14,7 @@ from octreelib_amd import _views
 from octreelib_amd._engine import Forest
 from octreelib_amd.criteria import try_count_threshold
 from octreelib_amd.internal import T, Voxel
+from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_np
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase, OctreeNodeBase
 
 __all__ = ["OctreeNode", "Octree", "OctreeConfig"]
@@ -78,6 +79,14 @@ class Octree(OctreeBase, Generic[T]):
         if self._slot is None:
             self._slot = self._forest.add_pose(np.empty((0, 3)))
         return _views.leaf_views(self._forest, self._slot, non_empty)
+
+    def leaf_statistics(self) -> LeafStatistics:
+        """Count, mean, covariance and its eigen-decomposition (least-squares plane) of every non-empty leaf: row i
+        describes get_leaf_points()[i].  One device call."""
+        if self._slot is None:
+            return leaf_statistics_np([])
+        self._forest.ensure_built()
+        return self._forest.leaf_stats(self._forest.slot_blocks(self._slot))
 
     @property
     def n_points(self):

@@ -12,6 +12,7 @@ from octreelib_amd import _views
 from octreelib_amd._engine import Forest
 from octreelib_amd.criteria import try_count_threshold
 from octreelib_amd.internal.voxel import Voxel, VoxelBase
+from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase
 
 __all__ = ["OctreeManager"]
@@ -90,6 +91,18 @@ class OctreeManager(VoxelBase):
         if pose_number in self._slots:
             return _views.leaf_views(self._forest, self._slots[pose_number], non_empty)
         return []
+
+    def leaf_statistics(self, pose_number: int) -> LeafStatistics:
+        """Count, mean, covariance and its eigen-decomposition (least-squares plane) of every non-empty leaf of a
+        pose: row i describes get_leaf_points(True, pose_number)[i].  One device call over the pose's blocks; a
+        manager on the caller's own octree type computes it on the host.  KeyError for an unknown pose."""
+        if self._plug is not None:
+            if pose_number not in self._plug.octrees:
+                raise KeyError(pose_number)
+            return leaf_statistics_of_leaves(self._plug.get_leaf_points(True, pose_number))
+        slot = self._slots[pose_number]
+        self._forest.ensure_built()
+        return self._forest.leaf_stats(self._forest.slot_blocks(slot))
 
     def get_points(self, pose_number: Optional[int] = None):
         if self._plug is not None:
