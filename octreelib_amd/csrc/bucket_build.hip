@@ -3064,9 +3064,7 @@ static int bucket_build_impl(octl_forest* f, const BucketBuildArgs& a, NodeTable
                        bb[3] - bb[0] + 1, f->vorg, small + SM_BK_MISSING);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t missing = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, small + SM_BK_MISSING, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(&missing, ctx->small_host, 4);
+    OCTL_TRY(octl_readback(ctx, small + SM_BK_MISSING, 1, &missing));
     if (missing) return OCTL_OK;
   }
   nt.n = total;

@@ -1010,14 +1010,6 @@ __global__ __launch_bounds__(256) void k_block_sizes(const uint32_t* __restrict_
   blk_size[b] = (int32_t)(e - blk_start[b]);
 }
 
-inline unsigned grid_for(int64_t n, int threads = 256) { return (unsigned)ceil_div(n, threads); }
-
-int bits_for(uint64_t max_value) {
-  int b = 0;
-  while (b < 64 && (max_value >> b) != 0) ++b;
-  return b;
-}
-
 }  // namespace
 
 int nodes_reserve(octl_ctx* ctx, NodeTable& t, int64_t cap) {
@@ -1037,15 +1029,6 @@ void nodes_free(octl_ctx* ctx, NodeTable& t) {
                     &t.old_id, &t.epoch, &t.corner, &t.edge})
     devbuf_release(ctx, *b);
   t.cap = t.n = 0;
-}
-
-// read `count` uint32 scalars of the small block (synchronises the stream)
-static int read_small(octl_ctx* ctx, int first, int count, uint32_t* out) {
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, ctx->small.as<uint32_t>() + first,
-                              (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(out, ctx->small_host, (size_t)count * 4);
-  return OCTL_OK;
 }
 
 // (Re)build the (leaf, pose) block table from pos_node / ord_idx.  Asynchronous: the block count
@@ -1090,7 +1073,7 @@ int forest_make_blocks(octl_forest* f) {
 
 int forest_finish_blocks(octl_forest* f, uint32_t* err_out) {
   uint32_t sm[32];
-  OCTL_TRY(read_small(f->ctx, 0, 32, sm));
+  OCTL_TRY(octl_readback(f->ctx, f->ctx->small.p, 32, sm));
   f->n_blocks = sm[SM_NBLOCKS];
   if (err_out) *err_out = sm[SM_ERR];
   return OCTL_OK;
@@ -1203,7 +1186,7 @@ static int run_level_loop(LevelLoop& L) {
       OCTL_TRY(octl_exclusive_scan_u32(ctx, tile_base, tile_base, L.n_new, small + SM_NTILES));
     }
     uint32_t lv[2];
-    OCTL_TRY(read_small(ctx, SM_NSPLIT, 2, lv));
+    OCTL_TRY(octl_readback(ctx, small + SM_NSPLIT, 2, lv));
     const int ns = (int)lv[0];
     const uint32_t n_tiles = lv[1];
     if (ns == 0) break;
@@ -1601,7 +1584,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   uint32_t sm[32];
   int bb[6] = {0, 0, 0, 0, 0, 0};  // (a single cube is voxel 0)
   if (!cube_fast) {
-    OCTL_TRY(read_small(ctx, 0, 32, sm));
+    OCTL_TRY(octl_readback(ctx, small, 32, sm));
     if (sm[SM_ERR])
       return octl_set_error(ctx, OCTL_E_DOMAIN,
                             "a point has a non-finite coordinate, a top-level voxel index outside +-%d, or "
@@ -1689,7 +1672,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
                        vlin_d, vstart_d);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t nv;
-    OCTL_TRY(read_small(ctx, SM_NVOX, 1, &nv));
+    OCTL_TRY(octl_readback(ctx, small + SM_NVOX, 1, &nv));
     v_pts = nv;
     if (!fresh) {
       vlin_h.resize(v_pts);

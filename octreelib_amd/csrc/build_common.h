@@ -5,30 +5,6 @@
 
 constexpr uint32_t IDX_MASK = 0x7FFFFFFFu;
 
-// slots of the context's small device scalar block (uint32 units)
-enum {
-  SM_ERR = 0,       // domain error flag
-  SM_BBOX = 4,      // 6 x int32: min xyz, max xyz
-  SM_NVOX = 12,     // voxels with points
-  SM_NSPLIT = 13,   // nodes to split at the next level
-  SM_NTILES = 14,   // tiles of the next level
-  SM_ETOTAL = 15,   // total of the scanned tile histogram
-  SM_NBLOCKS = 16,
-  // 20, 21: kept points / blocks of apply_mask (21 also: slot-voxel count), 24: debug scan total
-  SM_BK_NOORDER = 23,   // bucket build: some bucket has too many nodes / blocks for k_bucket_finish's own block order
-  SM_BK_FLAGS = 25,     // bucket build: some bucket / voxel does not fit (BF_* bits)
-  SM_BK_TOTAL = 26,     // bucket build: grand total of the scanned bucket table
-  SM_BK_TODO = 27,      // bucket build: voxels left as one leaf for the level loop of build.hip
-  SM_BK_MISSING = 28,
-  SM_BK_OVERFULL = 18,  // bucket build: buckets with more than 4096 points (they are built in chunks of whole voxels)
-  SM_BK_TICKET = 17,    // bucket build: workgroups of k_bucket_scan_totals that have finished (the last one forms the totals)
-  SM_CK_COUNT = 29,     // bucket build: chunks of the buckets with more than 4096 points (k_bucket_plan)   // bucket build over a previous scheme: voxels of that scheme without points now
-  SM_BK_LEVEL = 40,     // bucket build: internal nodes per level (7 words)
-  // 64..: slot histogram (RANSAC batches), 512..: allreduce
-  SM_GEOM = 64,         // bucket build: key geometry formed on the device (GeomDev, <= 192 bytes; the region is
-                        // the slot histogram's during RANSAC - never at the same time)
-};
-
 struct NodePtrs {
   uint32_t *start, *count, *scount;
   int32_t *depth, *voxel, *parent, *first_child, *old_id, *epoch;

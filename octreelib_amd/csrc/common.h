@@ -200,6 +200,62 @@ enum { MIRROR_COPY_WORDS = 512, MIRROR_BBOX_WORD = 896, MIRROR_RS_VIOLATION = 99
 static_assert(MIRROR_COPY_WORDS <= MIRROR_BBOX_WORD && MIRROR_BBOX_WORD + 8 <= MIRROR_RS_VIOLATION &&
               MIRROR_RS_VIOLATION < MIRROR_MASK_TOTALS &&
               MIRROR_MASK_TOTALS + 2 <= MIRROR_FLAG_BUILD && MIRROR_FLAG_MASK1 < 1024, "mirror layout");
+// Words of the context's scalar block ctx->small (4 KiB of device uint32; the pinned mirror above has the same size).
+// Words [0, SM_BUILD_WORDS) belong to the build: forest_build's first kernel (k_build_begin) resets them.  A word with
+// more than one name has owners that never hold a live value in it at the same time:
+//  - 28..31: the bucket build (SM_BK_MISSING, SM_CK_COUNT), the incremental insertion (SM_INC_*) and
+//    octl_forest_slot_counts (SM_SLOT_COUNTS).  forest_build tries the incremental insertion first and falls through
+//    to the bucket build only for K < 0 over a scheme without internal nodes: k_inc_place then never counts SM_INC_BAD
+//    (it counts only in cubes that are split), so word 29 still holds the zero SM_CK_COUNT starts from, and the bucket
+//    build zeroes word 28 itself before k_old_voxels_missing counts into it.  build.hip's prefix partition counts
+//    into SM_BK_MISSING only on a forest that was never built, which the incremental insertion leaves alone.
+//    octl_forest_slot_counts zeroes its four words and reads them back before it returns: never inside a build.
+//  - 64..: the key geometry of the bucket build (SM_GEOM) and the RANSAC slot histogram (SM_SLOT_HIST): a build
+//    and the reference order of a RANSAC pass are never in flight at the same time.
+enum {
+  SM_ERR = 0,           // domain error flag
+  SM_BBOX = 4,          // 6 x int32: min xyz, max xyz
+  SM_NVOX = 12,         // voxels with points
+  SM_NSPLIT = 13,       // nodes to split at the next level
+  SM_NTILES = 14,       // tiles of the next level
+  SM_ETOTAL = 15,       // total of the scanned tile histogram
+  SM_NBLOCKS = 16,      // blocks of the block table a build or an incremental insertion forms
+  SM_BK_TICKET = 17,    // bucket build: workgroups of k_bucket_scan_totals that have finished (the last one forms the totals)
+  SM_BK_OVERFULL = 18,  // bucket build: buckets with more than 4096 points (they are built in chunks of whole voxels)
+  SM_SLOT_VOXELS = 21,  // octl_forest_get_slot_voxels: scan total = voxels in which the pose has points
+  SM_MASK_TOTAL = 22,   // apply_mask without the fused kernel: grand total of its scan
+  SM_BK_NOORDER = 23,   // bucket build: some bucket has too many nodes / blocks for k_bucket_finish's own block order
+  SM_DEBUG_TOTAL = 24,  // octl_debug_exclusive_scan: scan total
+  SM_BK_FLAGS = 25,     // bucket build: some bucket / voxel does not fit (BF_* bits)
+  SM_BK_TOTAL = 26,     // bucket build: grand total of the scanned bucket table
+  SM_BK_TODO = 27,      // bucket build: voxels left as one leaf for the level loop of build.hip
+  SM_BK_MISSING = 28,   // bucket build over a previous scheme: voxels of that scheme without points now
+                        // (build.hip's prefix partition, k_top_tree: some node above depth pm does not split)
+  SM_CK_COUNT = 29,     // bucket build: chunks of the buckets with more than 4096 points (k_bucket_plan)
+  SM_INC_MISS = 28,     // incremental insertion: new points whose voxel the scheme does not know
+  SM_INC_BAD = 29,      // incremental insertion: new points outside a cube that is split
+  SM_INC_DEAD = 30,     // incremental insertion: new points that are not alive
+  SM_INC_NEWVOX = 31,   // incremental insertion: distinct new voxels
+  SM_SLOT_COUNTS = 28,  // octl_forest_slot_counts: two u64 (points, leaves of the pose), words 28..31
+  SM_BUILD_WORDS = 32,  // (end of the words k_build_begin resets)
+  SM_BK_LEVEL = 40,     // bucket build: internal nodes per level (7 words)
+  SM_GEOM = 64,         // bucket build: key geometry formed on the device (GeomDev, <= 192 bytes)
+  SM_SLOT_HIST = 64,    // forest_reference_order: blocks per pose slot (up to 256 words)
+  SM_ALLREDUCE = 512,   // route.hip: int64 allreduce buffer (up to 256 values, to the end of the block)
+  SM_WORDS = 1024
+};
+static_assert(SM_ERR < SM_BUILD_WORDS && SM_BBOX + 6 <= SM_BUILD_WORDS && SM_NVOX < SM_BUILD_WORDS &&
+                  SM_NSPLIT < SM_BUILD_WORDS && SM_NTILES < SM_BUILD_WORDS && SM_ETOTAL < SM_BUILD_WORDS &&
+                  SM_NBLOCKS < SM_BUILD_WORDS && SM_BK_TICKET < SM_BUILD_WORDS && SM_BK_OVERFULL < SM_BUILD_WORDS &&
+                  SM_SLOT_VOXELS < SM_BUILD_WORDS && SM_MASK_TOTAL < SM_BUILD_WORDS &&
+                  SM_BK_NOORDER < SM_BUILD_WORDS && SM_DEBUG_TOTAL < SM_BUILD_WORDS && SM_BK_FLAGS < SM_BUILD_WORDS &&
+                  SM_BK_TOTAL < SM_BUILD_WORDS && SM_BK_TODO < SM_BUILD_WORDS && SM_BK_MISSING < SM_BUILD_WORDS &&
+                  SM_CK_COUNT < SM_BUILD_WORDS && SM_INC_NEWVOX < SM_BUILD_WORDS &&
+                  SM_SLOT_COUNTS + 4 <= SM_BUILD_WORDS,
+              "single words of the scalar block lie among the words k_build_begin resets");
+static_assert(SM_BUILD_WORDS <= SM_BK_LEVEL && SM_BK_LEVEL + 7 <= SM_GEOM && SM_GEOM + 192 / 4 <= SM_ALLREDUCE &&
+                  SM_SLOT_HIST + 256 <= SM_ALLREDUCE && SM_ALLREDUCE + 2 * 256 <= SM_WORDS,
+              "scalar block regions");
 uint32_t octl_wait_next_seq(octl_ctx* ctx);
 int octl_wait_mirror_flags(octl_ctx* ctx, const int* words, int n_words, uint32_t seq, int64_t budget_us);
 // device side: publish `seq` behind everything this thread (and, through the barriers in front of the call, its
@@ -252,6 +308,22 @@ struct KTimer {
 int octl_collect_timings(octl_ctx* ctx);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workgroups of 256 threads for n items, one item per thread (n = 0: no workgroup - the caller guards or clamps)
+static inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n, 256); }
+// bits needed to hold max_value (0 for 0)
+static inline int bits_for(uint64_t max_value) {
+  int b = 0;
+  while (b < 64 && (max_value >> b) != 0) ++b;
+  return b;
+}
+// blocking readback of `count` uint32 words from the device (the scalar block, as a rule) through the pinned mirror:
+// one counted synchronisation of the context's stream
+static inline int octl_readback(octl_ctx* ctx, const void* src_dev, int64_t count, void* out) {
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, src_dev, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(out, ctx->small_host, (size_t)count * 4);
+  return OCTL_OK;
+}
 
 // ---- device-wide primitives (scan.hip, radix_sort.hip) ------------------------------------
 // exclusive prefix sum of n uint32 (in may equal out); if total_dev != nullptr the grand total

@@ -68,7 +68,7 @@ struct octl_forest {
   int built_poses = 0;
   bool append_only = true;
   // voxel bounding box of every point added since the last clear, kept by the ingest kernel
-  // (api.hip): int32 x 8 = {min x,y,z, max x,y,z, domain-error flag, point outside a hinted box}
+  // (store.hip): int32 x 8 = {min x,y,z, max x,y,z, domain-error flag, point outside a hinted box}
   DevBuf bbox_dev;
   // octl_forest_clear does not launch anything: the box on the device is STALE until something resets it - the next
   // ingest / box pass (bbox_ensure), or the first kernel of a build that finds the box itself (k_build_begin)
@@ -163,15 +163,15 @@ int ransac_launch(octl_ctx* ctx, const double* xyz_dev, int64_t n_points,
                   uint8_t* evaluated_dev, DevBuf& scratch, int64_t max_block = INT64_MAX);
 // the hypothesis table must hold draws from [0, 1) (np.random.random, cuda_ransac.py:39-41): anything
 // else would index outside the block in the sampling arithmetic (cuda_ransac.py:103-107)
-// api.hip: an empty store takes over a library-owned device buffer (swap) instead of copying it
+int ransac_check_table(octl_ctx* ctx, const double* hyp, int32_t H, int32_t k);
+// store.hip: an empty store takes over a library-owned device buffer (swap) instead of copying it
 int store_adopt(octl_forest* f, DevBuf& src, int64_t n, bool* adopted);
-// api.hip: fold the whole store into bbox_dev (clears bbox_pending); copy a borrowed store into the forest's own block
+// store.hip: fold the whole store into bbox_dev (clears bbox_pending); copy a borrowed store into the forest's own block
 int store_compute_bbox(octl_forest* f);
-// api.hip: the box on the device is valid (reset if octl_forest_clear left it stale) / the alive flags are written
+int store_materialize(octl_forest* f);
+// store.hip: the box on the device is valid (reset if octl_forest_clear left it stale) / the alive flags are written
 int bbox_ensure(octl_forest* f);
 int alive_ensure(octl_forest* f);
-int store_materialize(octl_forest* f);
-int ransac_check_table(octl_ctx* ctx, const double* hyp, int32_t H, int32_t k);
 // build.hip: (re)build the (leaf, pose) block table from pos_node / ord_idx
 int forest_make_blocks(octl_forest* f);
 // reads the block count (and the domain-error flag) left on the device: one synchronisation
@@ -186,8 +186,10 @@ int forest_fix_origin(octl_forest* f, const int bb[6]);
 int forest_sync_vcodes(octl_forest* f);
 int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info);
 
-// api.hip: wait for the counts an asynchronous apply_mask left in flight (octl_forest_apply_mask_async) and book
+// mask.hip: wait for the counts an asynchronous apply_mask left in flight (octl_forest_apply_mask_async) and book
 // them; a no-op otherwise.  Every entry point that looks at the forest calls it first.
 int forest_settle(octl_forest* f);
 // ... and forget them (clear / destroy: nothing will look at the counts)
 void forest_forget_pending(octl_forest* f);
+// mask.hip: the RANSAC mask is allocated and, when it is not valid, all ones (every point kept)
+int ensure_mask(octl_forest* f);

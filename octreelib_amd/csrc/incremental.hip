@@ -28,17 +28,8 @@
 
 namespace {
 
-enum {  // words of the context's small scalar block (reset by forest_build)
-  SM_INC_MISS = 28,   // new points whose voxel the scheme does not know
-  SM_INC_BAD = 29,    // new points outside a cube that is split
-  SM_INC_DEAD = 30,   // new points that are not alive
-  SM_INC_NEWVOX = 31  // distinct new voxels
-};
-
 constexpr uint64_t KEY_MISS = 1ull << 63;
 constexpr uint64_t KEY_DEAD = ~0ull;
-
-inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(std::max<int64_t>(n, 1), 256); }
 
 __device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t x) {
   int64_t lo = 0, hi = n;
@@ -306,20 +297,6 @@ __global__ __launch_bounds__(256) void k_inc_block_sizes(const uint32_t* __restr
   blk_size[b] = (int32_t)(e - blk_start[b]);
 }
 
-int bits_for(uint64_t max_value) {
-  int b = 0;
-  while (b < 64 && (max_value >> b) != 0) ++b;
-  return b;
-}
-
-int read_words(octl_ctx* ctx, int first, int count, uint32_t* out) {
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, ctx->small.as<uint32_t>() + first, (size_t)count * 4,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(out, ctx->small_host, (size_t)count * 4);
-  return OCTL_OK;
-}
-
 }  // namespace
 
 // The sorted packed voxel codes of the current scheme on the device (roots = nodes [0, V) in this order).
@@ -375,7 +352,7 @@ int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info) 
     HIP_TRY(ctx, hipGetLastError());
   }
   uint32_t sm[32];
-  OCTL_TRY(read_words(ctx, 0, 32, sm));
+  OCTL_TRY(octl_readback(ctx, small, 32, sm));
   if (sm[SM_ERR] || sm[SM_INC_BAD]) {
     // forest_build's general path raises the error; its scalar block has to look untouched
     HIP_TRY(ctx, hipMemsetAsync(small + SM_ERR, 0, 4, st));
@@ -420,11 +397,11 @@ int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info) 
                        (const uint32_t*)rank, ucode);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t u32 = 0;
-    OCTL_TRY(read_words(ctx, SM_INC_NEWVOX, 1, &u32));
+    OCTL_TRY(octl_readback(ctx, small + SM_INC_NEWVOX, 1, &u32));
     U = u32;
     if (n_nodes + U >= ((int64_t)1 << 31)) return OCTL_OK;
     OCTL_TRY(devbuf_reserve(ctx, f->vcode_dev[1], (size_t)(V + U) * 8));
-    OCTL_LAUNCH(k_inc_merge_roots, dim3(grid_for(V + U)), dim3(256), 0, st,
+    OCTL_LAUNCH(k_inc_merge_roots, dim3(grid_for(std::max<int64_t>(V + U, 1))), dim3(256), 0, st,
                        (const uint64_t*)f->vcode_dev[0].as<uint64_t>(), V, (const uint64_t*)ucode, U,
                        f->vcode_dev[1].as<uint64_t>(), shift_w, root_w);
     HIP_TRY(ctx, hipGetLastError());
@@ -432,12 +409,12 @@ int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info) 
     OCTL_TRY(nodes_reserve(ctx, nxt, n_nodes + U));
     nxt.n = n_nodes + U;
     NodePtrs dst = node_ptrs(nxt);
-    OCTL_LAUNCH(k_inc_copy_nodes, dim3(grid_for(n_nodes)), dim3(256), 0, st, nd, dst, n_nodes, V,
-                       (int32_t)U, (const int32_t*)shift_w);
+    OCTL_LAUNCH(k_inc_copy_nodes, dim3(grid_for(std::max<int64_t>(n_nodes, 1))), dim3(256), 0, st, nd, dst,
+                       n_nodes, V, (int32_t)U, (const int32_t*)shift_w);
     HIP_TRY(ctx, hipGetLastError());
-    OCTL_LAUNCH(k_inc_new_roots, dim3(grid_for(U)), dim3(256), 0, st, (const uint64_t*)ucode,
-                       (const int32_t*)root_w, U, f->mode, f->edge, f->corner[0], f->corner[1], f->corner[2], f->vorg,
-                       dst);
+    OCTL_LAUNCH(k_inc_new_roots, dim3(grid_for(std::max<int64_t>(U, 1))), dim3(256), 0, st,
+                       (const uint64_t*)ucode, (const int32_t*)root_w, U, f->mode, f->edge, f->corner[0], f->corner[1],
+                       f->corner[2], f->vorg, dst);
     HIP_TRY(ctx, hipGetLastError());
     if (n_blocks > 0) {
       OCTL_LAUNCH(k_inc_remap, dim3(grid_for(n_blocks)), dim3(256), 0, st, f->blk_node.as<int32_t>(),
@@ -485,7 +462,7 @@ int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info) 
     HIP_TRY(ctx, hipGetLastError());
   }
   uint32_t nb_new = 0;
-  if (n_live > 0) OCTL_TRY(read_words(ctx, SM_NBLOCKS, 1, &nb_new));
+  if (n_live > 0) OCTL_TRY(octl_readback(ctx, small + SM_NBLOCKS, 1, &nb_new));
 
   // ---- commit ---------------------------------------------------------------------------------------------------
   if (U > 0) {

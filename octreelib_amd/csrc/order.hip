@@ -150,13 +150,6 @@ __global__ __launch_bounds__(256) void k_slot_hist(const int32_t* __restrict__ b
   if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n, 256); }
-int bits_for(uint64_t max_value) {
-  int b = 0;
-  while (b < 64 && (max_value >> b) != 0) ++b;
-  return b;
-}
-
 }  // namespace
 
 // Fills f->rs_order (device, int32 per block) with all blocks in the reference's order
@@ -307,7 +300,7 @@ int forest_reference_order(octl_forest* f, const int32_t* e0_host, std::vector<u
   HIP_TRY(ctx, hipMemcpyAsync(f->rs_order.p, vals_b[res2], (size_t)nb * 4,
                               hipMemcpyDeviceToDevice, st));
   // blocks per slot (only needed to cut the order into batches)
-  uint32_t* hist = ctx->small.as<uint32_t>() + 64;
+  uint32_t* hist = ctx->small.as<uint32_t>() + SM_SLOT_HIST;
   if (!need_slot_counts) {
     // nothing to do
   } else if (n_poses <= 256) {
@@ -316,9 +309,7 @@ int forest_reference_order(octl_forest* f, const int32_t* e0_host, std::vector<u
     OCTL_LAUNCH(k_slot_hist, dim3((unsigned)ceil_div(nb, 2048)), dim3(256), 0, st,
                        (const int32_t*)f->blk_slot.as<int32_t>(), nb, hist);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, hist, (size_t)n_poses * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(slot_counts.data(), ctx->small_host, (size_t)n_poses * 4);
+    OCTL_TRY(octl_readback(ctx, hist, n_poses, slot_counts.data()));
   } else {
     std::vector<int32_t> slots((size_t)nb);
     HIP_TRY(ctx, hipMemcpyAsync(slots.data(), f->blk_slot.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));

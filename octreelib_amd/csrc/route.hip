@@ -199,8 +199,6 @@ __global__ void k_route_status(unsigned long long* __restrict__ counts, int n_ra
   }
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n, 256); }
-
 // Steps 1-2 of the routing for R destination ranks: destination of every point + counts, stable
 // partition by destination (one radix pass), packed send buffers (xyz, global index) in the
 // context's scratch.  Independent of the communicator (the test hook below runs it for any R).
@@ -220,7 +218,7 @@ static int route_partition(octl_ctx* ctx, const double* xyz_dev, const int64_t* 
   OCTL_TRY(devbuf_reserve(ctx, hist, ((size_t)R * ntiles + 8) * 4));
   OCTL_TRY(devbuf_reserve(ctx, send_xyz, (size_t)n1 * 24));
   OCTL_TRY(devbuf_reserve(ctx, send_gidx, (size_t)n1 * 8));
-  uint32_t* err = ctx->small.as<uint32_t>();
+  uint32_t* err = ctx->small.as<uint32_t>() + SM_ERR;
   HIP_TRY(ctx, hipMemsetAsync(counts_d.p, 0, (size_t)R * 8 + 16, st));
   HIP_TRY(ctx, hipMemsetAsync(err, 0, 4, st));
   if (n > 0) {
@@ -371,7 +369,7 @@ int octl_route_points(octl_ctx* ctx, const double* xyz_dev, const int64_t* gidx_
     }                      \
   } while (0)
   RT_TRY(route_partition(ctx, xyz_dev, gidx_dev, n, index_base, L, R));
-  uint32_t* err = ctx->small.as<uint32_t>();
+  uint32_t* err = ctx->small.as<uint32_t>() + SM_ERR;
   // --- 3. counts exchange ---------------------------------------------------------------------------------
   // A rank that left this function alone after the exchange would leave its peers waiting for ever in
   // the Send/Recv group below (RCCL has no timeout), so every exit between here and the group is
@@ -401,6 +399,7 @@ int octl_route_points(octl_ctx* ctx, const double* xyz_dev, const int64_t* gidx_
     matrix[2] = cap_pts;
   }
   uint32_t err_h = 0;
+  // (not octl_readback: an exit of the exchange goes through cleanup() and reports a route error, see above)
   if (hipMemcpyAsync(ctx->small_host, err, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) {
     cleanup();
@@ -436,7 +435,7 @@ int octl_route_points(octl_ctx* ctx, const double* xyz_dev, const int64_t* gidx_
     int rc_a = devbuf_reserve(ctx, ctx->routed_xyz, (size_t)std::max<int64_t>(nr, 1) * 24 + 16);
     if (rc_a == OCTL_OK) rc_a = devbuf_reserve(ctx, ctx->routed_gidx, (size_t)std::max<int64_t>(nr, 1) * 8);
     if (use_rccl && grow_any) {
-      int64_t* flag_d = reinterpret_cast<int64_t*>(ctx->small.as<uint32_t>() + 512);
+      int64_t* flag_d = reinterpret_cast<int64_t*>(ctx->small.as<uint32_t>() + SM_ALLREDUCE);
       int64_t* flag_h = static_cast<int64_t*>(ctx->small_host);
       *flag_h = rc_a == OCTL_OK ? 0 : 1;
       ncclResult_t r = ncclSuccess;
@@ -585,7 +584,7 @@ int octl_comm_allreduce_i64(octl_ctx* ctx, int64_t* inout_host, int32_t n) {
   if (n == 0 || (ctx->n_ranks == 1 && !ctx->comm)) return OCTL_OK;
   if (!ctx->comm) return octl_set_error(ctx, OCTL_E_STATE, "communicator not initialised");
   hipStream_t st = ctx->stream;
-  int64_t* d = reinterpret_cast<int64_t*>(ctx->small.as<uint32_t>() + 512);  // 2 KiB into the block
+  int64_t* d = reinterpret_cast<int64_t*>(ctx->small.as<uint32_t>() + SM_ALLREDUCE);
   HIP_TRY(ctx, hipMemcpyAsync(d, inout_host, (size_t)n * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   NCCL_TRY(ctx, g_rccl.AllReduce(d, d, (size_t)n, ncclInt64, ncclSum,
