@@ -272,6 +272,11 @@ constexpr int RS_SMALL_THREADS = 128;  // ... blocks with fewer points than this
 constexpr int RS_TINY_THREADS = 64;    // ... and blocks with fewer points than this ONE wave x 16
 constexpr int RS_PER_CU = 64, RS_SMALL_PER_CU = 128, RS_TINY_PER_CU = 256;   // workgroups per CU of the three
 constexpr int RS_KMAX = 16;   // initial_points_number supported by the register path
+// the two-stage widened count of the one-wave instance (see "the two-stage widened count" in k_ransac; the numbers
+// come out of tools/prescreen_stage_sim.py, HISTORY.md 10)
+constexpr int RS_STAGE1_SLACK = 2;    // stage 1 looks at (budget + this) points, rounded up to a multiple of four
+constexpr int RS_STAGE2_MIN = 6;      // ... and only when at least this many points are left for stage 2
+constexpr int RS_STAGE2_RING = 128;   // entries of the stage-2 queue (a ring: at most 63 waiting + 64 arriving)
 
 // everything the kernel needs to know about one batch entry, written by k_block_desc so that a
 // workgroup reads ONE 32-byte record instead of chasing order -> size -> start -> vstart
@@ -667,9 +672,15 @@ __device__ __forceinline__ void screen_ub(const f4* __restrict__ loc, int n, con
 //   [5] blocks whose survivors overflowed the queue   [8] blocks   [9] blocks that ended with group 0
 //   [10] workgroups   [11] sum of block sizes   [12] hypothesis groups prescreened   [13] hypotheses recounted exactly
 //   [14] hypothesis groups fitted and scored exactly   [15] sum over those groups of the block size
+//   the two-stage widened count (see "the two-stage widened count" in k_ransac):
+//   [16] (point, hypothesis) pairs of stage 1   [17] pairs of stage 2 (lanes without a queued hypothesis included)
+//   [18] hypotheses queued for stage 2   [19] prescreened blocks that took the single-stage count
+//   [20] pairs of the single-stage count   [21] stage-2 passes   [22] pairs a single-stage count of every block takes
 #ifdef RS_COUNTS
-__device__ unsigned long long g_rs_stamps[16];
-#define RS_COUNT_INIT unsigned long long _rs_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+constexpr int RS_NSTAMPS = 24;
+__device__ unsigned long long g_rs_stamps[RS_NSTAMPS];
+#define RS_COUNT_INIT unsigned long long _rs_acc[RS_NSTAMPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,  \
+                                                                0, 0, 0, 0, 0, 0, 0, 0};                             \
                       const unsigned long long _rs_m0 = __builtin_amdgcn_s_memtime(),                      \
                                                _rs_r0 = __builtin_amdgcn_s_memrealtime()
 #define RS_COUNT(k, v) _rs_acc[k] += (unsigned long long)(v)
@@ -679,7 +690,7 @@ __device__ unsigned long long g_rs_stamps[16];
       _rs_acc[0] = __builtin_amdgcn_s_memtime() - _rs_m0;                               \
       _rs_acc[1] = __builtin_amdgcn_s_memrealtime() - _rs_r0;                           \
       _rs_acc[10] += 1;                                                                 \
-      for (int _k = 0; _k < 16; ++_k) atomicAdd(&g_rs_stamps[_k], _rs_acc[_k]);         \
+      for (int _k = 0; _k < RS_NSTAMPS; ++_k) atomicAdd(&g_rs_stamps[_k], _rs_acc[_k]); \
     }                                                                                   \
   } while (0)
 #else
@@ -995,6 +1006,83 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
           const bool elig = prescreen_constants(extent, ox, oy, oz, thr, pc) && blk_fast && !no_prescreen;
           if (elig) {
             RS_COUNT(4, 1);
+            // ---- the two-stage widened count (one wave per block) ---------------------------------------------------
+            // A later hypothesis is dead as soon as it has MISSED budget = n - Lcur points: its bound cannot exceed
+            // Lcur any more.  The count is a sum of per-point bits, so the order of the points is free: a second copy of
+            // the local points, permuted so that the points the wave's best hypothesis of group 0 misses come first
+            // (a good hypothesis spends its whole budget on them, a bad one misses nearly everything anyway), is
+            // counted in two stages.  Stage 1: the first m1 points for NH hypotheses per lane, as before; whoever has
+            // not used up the budget goes to a queue in LDS with its plane, its count so far and its index.  Stage 2,
+            // whenever 64 are waiting and at the end: one queued hypothesis per lane over the other n - m1 points, then
+            // the unchanged decision (bound > Lcur survives).  Hypotheses the bound cannot vouch for travel through
+            // both stages with a plane that counts every point, so the survivors keep their index order.  Same bits,
+            // same sums, same survivors - fewer (point, hypothesis) pairs.  Blocks with a budget close to n (uniform
+            // clouds, small Lcur) take the single-stage count.
+            // No new LDS: with one wave per block only buffer `buf` of the three rotating ones is live during the
+            // compute (the next block is staged at the end of the iteration): the permuted copy lives in the third
+            // s_loc buffer, the queue in the two idle s_pts buffers.
+            constexpr bool TWO = THREADS == 64;
+            typedef uint32_t __attribute__((may_alias)) u32a;
+            const int budget = n - Lcur;
+            int m1 = n, qhead = 0, qtail = 0;
+            bool two_stage = false;
+            f4* ploc = nullptr;
+            u32a *qlo = nullptr, *qhi = nullptr;
+            if constexpr (TWO) {
+              m1 = min(n, (budget + RS_STAGE1_SLACK + 3) & ~3);
+              two_stage = n - m1 >= RS_STAGE2_MIN;
+              if (two_stage) {
+                const int third = buf == 0 ? 2 : buf - 1;
+                ploc = s_loc[third];
+                qlo = (u32a*)&s_pts[third][0][0];
+                qhi = (u32a*)&s_pts[buf == 2 ? 0 : buf + 1][0][0];
+                static_assert(3 * RS_STAGE2_RING * sizeof(uint32_t) <= sizeof(s_pts[0]), "three words per idle buffer");
+                // the screening order: points outside the threshold of the wave's best plane of group 0 first
+                const unsigned long long wl = __ballot(cnt == Lcur);   // (never empty: Lcur is the maximum of cnt)
+                const int src = __ffsll((long long)wl) - 1;
+                const float A = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(fa), src));
+                const float B = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(fb), src));
+                const float Cc = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(fc), src));
+                const float To = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(sto), src));
+                const bool mine = (int)tx < n;
+                const f4 Lp = loc[mine ? tx : 0];
+                const float sv = fma32(A, Lp.x, fma32(B, Lp.y, fma32(Cc, Lp.z, To)));
+                const bool far = mine && !(fma32(sv, sv, nthr2) < 0.f);
+                const unsigned long long mf = __ballot(far), mn = __ballot(mine && !far);
+                const unsigned long long mm = far ? mf : mn;
+                const int pos = (far ? 0 : __popcll(mf)) +
+                                (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+                if (mine) ploc[pos] = Lp;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+              } else {
+                RS_COUNT(19, 1);
+              }
+            }
+            // survivors of the widened count join the exact-fit queue
+            auto survive = [&](const bool sv, const uint32_t ub, const int t) {
+              const unsigned long long mk = __ballot(sv);
+              if (sv) {
+                const int pos = S + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                if (pos < PRE_LIST) s_surv[pos] = (uint16_t)((ub << 10) | (uint32_t)t);
+              }
+              S += __popcll(mk);
+            };
+            // stage 2: the first nq queued hypotheses, one per lane, over the points stage 1 left out
+            auto stage2 = [&](const int nq) {
+              __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+              const bool mine = (int)tx < nq;
+              const int e = (qhead + (mine ? (int)tx : 0)) & (RS_STAGE2_RING - 1);
+              const float a = __uint_as_float(qlo[e]), b = __uint_as_float(qlo[RS_STAGE2_RING + e]),
+                          c = __uint_as_float(qlo[2 * RS_STAGE2_RING + e]), to = __uint_as_float(qhi[e]),
+                          T2 = __uint_as_float(qhi[RS_STAGE2_RING + e]);
+              const uint32_t w = qhi[2 * RS_STAGE2_RING + e];
+              int c2[1] = {(int)(w >> 10)};
+              screen_ub<1>(ploc + m1, n - m1, &a, &b, &c, &to, &T2, c2);
+              RS_COUNT(17, 64 * (n - m1));
+              RS_COUNT(21, 1);
+              survive(mine && c2[0] > Lcur, (uint32_t)c2[0], (int)(w & 1023u));
+              qhead += nq;
+            };
             // NH hypothesis groups at a time (three; the last one or two of a lane's HPL - 1 on their own): every point
             // read from LDS serves NH hypotheses of the lane
             auto prescreen = [&](auto nh_tag, const int qb) {
@@ -1069,25 +1157,61 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
 #pragma unroll
                 for (int h = 0; h < NH; ++h) qok[h] = qok[h] && (pe[h].y >> 16) == 0u;
               }
-              screen_ub<NH>(loc, n, qa, qb_, qc, qto, qT2, qcnt);
               RS_COUNT(12, NH);
+              RS_COUNT(22, 64 * NH * n);
+              if constexpr (TWO) {
+                if (two_stage) {   // (wave-uniform)
+                  bool bad = false;
 #pragma unroll
-              for (int h = 0; h < NH; ++h) {
-                const bool sv = !(qok[h] && qcnt[h] <= Lcur) && (FULLH || hyp_a(h) < H);
-                const unsigned long long mk = __ballot(sv);
-                if (sv) {
-                  const int pos = S + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                  const uint32_t ub = (THREADS == 64 && qok[h]) ? (uint32_t)qcnt[h] : 63u;
-                  if (pos < PRE_LIST) s_surv[pos] = (uint16_t)((ub << 10) | (uint32_t)hyp_a(h));
+                  for (int h = 0; h < NH; ++h) bad = bad || !qok[h];
+                  if (__any(bad)) {   // not vouched for: a plane that counts every point (bound n > Lcur)
+#pragma unroll
+                    for (int h = 0; h < NH; ++h) {
+                      if (!qok[h]) {
+                        qa[h] = qb_[h] = qc[h] = qto[h] = 0.f;
+                        qT2[h] = 1.f;
+                      }
+                    }
+                  }
+                  screen_ub<NH>(ploc, m1, qa, qb_, qc, qto, qT2, qcnt);
+                  RS_COUNT(16, 64 * NH * m1);
+#pragma unroll
+                  for (int h = 0; h < NH; ++h) {
+                    // (misses so far m1 - qcnt < budget)
+                    const bool alive = qcnt[h] > m1 - budget && (FULLH || hyp_a(h) < H);
+                    const unsigned long long mk = __ballot(alive);
+                    if (alive) {
+                      const int e = (qtail + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))) &
+                                    (RS_STAGE2_RING - 1);
+                      qlo[e] = __float_as_uint(qa[h]);
+                      qlo[RS_STAGE2_RING + e] = __float_as_uint(qb_[h]);
+                      qlo[2 * RS_STAGE2_RING + e] = __float_as_uint(qc[h]);
+                      qhi[e] = __float_as_uint(qto[h]);
+                      qhi[RS_STAGE2_RING + e] = __float_as_uint(qT2[h]);
+                      qhi[2 * RS_STAGE2_RING + e] = ((uint32_t)qcnt[h] << 10) | (uint32_t)hyp_a(h);
+                    }
+                    qtail += __popcll(mk);
+                    RS_COUNT(18, __popcll(mk));
+                    if (qtail - qhead >= 64) stage2(64);
+                  }
+                  return;
                 }
-                S += __popcll(mk);
               }
+              screen_ub<NH>(loc, n, qa, qb_, qc, qto, qT2, qcnt);
+              RS_COUNT(20, 64 * NH * n);
+#pragma unroll
+              for (int h = 0; h < NH; ++h)
+                survive(!(qok[h] && qcnt[h] <= Lcur) && (FULLH || hyp_a(h) < H),
+                        (THREADS == 64 && qok[h]) ? (uint32_t)qcnt[h] : 63u, hyp_a(h));
             };
             constexpr int PNH = 3;   // (four or five at a time: within the box-to-box noise, HISTORY 9)
             constexpr int TRIOS = (HPL - 1) / PNH, REST = (HPL - 1) % PNH;
 #pragma unroll 1
             for (int i = 0; i < TRIOS; ++i) prescreen(std::integral_constant<int, PNH>{}, 1 + PNH * i);
             if constexpr (REST > 0) prescreen(std::integral_constant<int, (REST > 0 ? REST : 1)>{}, 1 + PNH * TRIOS);
+            if constexpr (TWO) {
+              if (qtail != qhead) stage2(qtail - qhead);
+            }
             RS_COUNT(2, S);
             use_list = S <= PRE_LIST;
             if (!use_list) RS_COUNT(5, 1);
@@ -2096,12 +2220,12 @@ static int debug_plane_arith(octl_ctx* ctx, const double* num3, const double* de
 }
 
 #ifdef RS_COUNTS
-extern "C" int octl_debug_rs_stamps(octl_ctx* ctx, unsigned long long out[16], int reset) {
+extern "C" int octl_debug_rs_stamps(octl_ctx* ctx, unsigned long long out[RS_NSTAMPS], int reset) {
   if (!ctx || !out) return OCTL_E_INVALID;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rs_stamps), sizeof(unsigned long long) * 16));
+  HIP_TRY(ctx, hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rs_stamps), sizeof(unsigned long long) * RS_NSTAMPS));
   if (reset) {
-    unsigned long long z[16] = {0};
+    unsigned long long z[RS_NSTAMPS] = {0};
     HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_rs_stamps), z, sizeof(z)));
   }
   return OCTL_OK;

@@ -17,14 +17,15 @@ lib.octl_debug_rs_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 wl = bench.Workload(ctx, ctx, 0, 1, 10_000_000, (32, 32, 32), "planar", 64, False, False, n_clouds=3)
 for _ in range(3):
     wl.step()
-out = (C.c_ulonglong * 16)()
+NW = 24   # RS_NSTAMPS of csrc/ransac.hip
+out = (C.c_ulonglong * NW)()
 ctx.check(lib.octl_debug_rs_stamps(ctx.handle, out, 1))
 reps = 6
 for _ in range(reps):
     wl.step()
 ctx.sync()
 ctx.check(lib.octl_debug_rs_stamps(ctx.handle, out, 0))
-v = [out[i] / reps for i in range(16)]
+v = [out[i] / reps for i in range(NW)]
 blocks, exit0, pts = v[8], v[9], v[11]
 H, LANES, HPL = 1024, 64, 16
 eligible, a_groups, survivors, b_batches, overflow = v[4], v[12], v[2], v[3], v[5]
@@ -49,6 +50,14 @@ res = {
     "fraction_pairs_scored": v[15] * LANES / (pts * H),
     "hypotheses_recounted_f64": v[13], "fraction_hypotheses_recounted": v[13] / max(exact_groups * LANES, 1),
     "fraction_blocks_leaving_after_pass_1": exit0 / blocks,          # (the key bench.py reads)
+    # the two-stage widened count (pairs = points x 64 lanes x hypotheses per lane, idle stage-2 lanes included;
+    # tools/prescreen_stage_sim.py predicts the same figures in group-rows = pairs / 64)
+    "widened_count_blocks_single_stage": v[19], "fraction_prescreened_blocks_single_stage": v[19] / max(eligible, 1),
+    "widened_count_pairs_stage_1": v[16], "widened_count_pairs_stage_2": v[17], "widened_count_pairs_single_stage": v[20],
+    "widened_count_pairs_if_all_single_stage": v[22],
+    "widened_count_pairs_fraction_of_single_stage": (v[16] + v[17] + v[20]) / max(v[22], 1),
+    "hypotheses_queued_for_stage_2": v[18], "fraction_prescreened_queued_for_stage_2": v[18] / max(a_groups * LANES, 1),
+    "stage_2_passes": v[21], "stage_2_passes_per_two_stage_block": v[21] / max(eligible - v[19], 1),
     "note": "average per launch over %d steps of the rotating headline workload; the instance runs one wave per block" % reps,
 }
 print(json.dumps(res, indent=1))
