@@ -171,6 +171,25 @@ typedef struct octl_build_info {
 int octl_forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
                       int32_t keep_scheme, int32_t max_depth, octl_build_info* info);
 
+/* octl_forest_build with a second split rule, evaluated on the device: a node splits when its scheme-pose count
+ * exceeds K (K < 0: no count rule) OR it holds at least min_points scheme points and the smallest eigenvalue of
+ * their covariance sum (p - mean)(p - mean)^T / (n - ddof) exceeds max_variance ("split while the points are not
+ * flat"; octreelib_amd.NotPlanar is the same predicate as a host callable).  Scheme over the union of the poses of
+ * scheme_mask, then every pose is placed; the result is an ordinary scheme (keep_scheme builds, late poses, RANSAC,
+ * leaf_stats, masks work on it unchanged).  max_variance must be finite and > 0 - a cube of edge e cannot hold
+ * points with a statistic above e^2 / 3, which bounds the depth whatever the points - min_points >= 4, ddof 0 or 1:
+ * OCTL_E_INVALID otherwise.  Errors and what they leave behind as octl_forest_build.                            */
+int octl_forest_build_planar(octl_forest* f, int64_t K, double max_variance, int32_t min_points, int32_t ddof,
+                             const uint8_t* scheme_mask, int32_t n_mask, int32_t max_depth, octl_build_info* info);
+/* Why the nodes of the last octl_forest_build_planar split: per scheme node (indexed like octl_forest_get_nodes)
+ * the scheme-point count and the statistic the decision compared with max_variance - NaN where none was evaluated
+ * (fewer than min_points scheme points).  Node i is internal iff n_scheme[i] > K or (n_scheme[i] >= min_points and
+ * lambda_min[i] > max_variance).  Kept while the node table is the one that build left (placements into the scheme
+ * that add no voxel keep it); for any other scheme n_scheme is 0 and lambda_min NaN everywhere.  Either output may
+ * be NULL; size query with cap = 0.                                                                            */
+int octl_forest_get_split_stats(octl_forest* f, int64_t cap, uint32_t* n_scheme, double* lambda_min,
+                                int64_t* n_nodes);
+
 /* Install a host-defined subdivision scheme (for criteria that are arbitrary host callables,
  * octree.py:26: the host decides which nodes split, the device does the placement): nodes
  * [0,V) are the roots in voxel order, the 8 children of node i are first_child[i]..+7 (-1 =

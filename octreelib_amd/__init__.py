@@ -12,8 +12,8 @@ for gfx950.  There is no CPU fallback: without liboctree_hip.so and a GPU every 
 raises.
 """
 
-from octreelib_amd.criteria import MaxPoints
+from octreelib_amd.criteria import MaxPoints, NotPlanar
 from octreelib_amd.feed import DeviceCloud, ScanPipeline, pinned_empty, upload_async
 
 __version__ = "0.1.0"
-__all__ = ["MaxPoints", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "__version__"]
+__all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "__version__"]

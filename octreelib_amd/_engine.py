@@ -189,6 +189,50 @@ class Forest:
     def subdivide(self, K: int, scheme_slots=None, max_depth=0):
         self.build(K, scheme_slots, False, max_depth)
 
+    def subdivide_planar(self, rule, scheme_slots=None, max_depth=0):
+        """Subdivision by `rule` = (K, max_variance, min_points, ddof) of criteria.try_planar_threshold: count > K
+        OR NotPlanar, decided inside the level loop on the device (octl_forest_build_planar)."""
+        k, max_variance, min_points, ddof = rule
+        self._resolve_membership()
+        mask = None
+        if scheme_slots is not None:
+            mask = np.zeros(self.n_slots, dtype=np.uint8)
+            mask[list(scheme_slots)] = 1
+        info = nat.BuildInfo()
+        try:
+            self.ctx.check(
+                self.lib.octl_forest_build_planar(
+                    self.handle, int(k), float(max_variance), int(min_points), int(ddof), nat.ptr(mask),
+                    self.n_slots if mask is not None else 0, int(max_depth), C.byref(info),
+                )
+            )
+        except (RecursionError, nat.DomainError, MemoryError, RuntimeError):
+            self.has_scheme = False   # (the library dropped the scheme: see build)
+            self._dirty = True
+            self.info = None
+            self._invalidate()
+            raise
+        self.info = info
+        self.n_ord = int(info.n_points)
+        self._dirty = False
+        self._invalidate()
+        self.epoch += 1
+        self.has_scheme = True
+        self._update_membership()
+
+    def split_stats(self):
+        """(n_scheme u32, lambda_min f64) per scheme node: what the split decisions of the last planar subdivide
+        saw (octl_forest_get_split_stats); NaN where no statistic was evaluated."""
+        self.ensure_built()
+        n = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_get_split_stats(self.handle, 0, None, None, C.byref(n)))
+        cnt = np.empty(n.value, dtype=np.uint32)
+        lam = np.empty(n.value, dtype=np.float64)
+        if n.value:
+            self.ctx.check(self.lib.octl_forest_get_split_stats(self.handle, n.value, nat.ptr(cnt), nat.ptr(lam),
+                                                                C.byref(n)))
+        return cnt, lam
+
     def subdivide_callable(self, criteria, scheme_slots=None, max_depth=63):
         """Subdivision driven by arbitrary host callables (octree.py:26: a node splits when
         any(criterion(points))).  A Python callable cannot run inside a kernel: the host evaluates

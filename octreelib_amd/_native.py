@@ -74,6 +74,8 @@ SIGNATURES = {
     "octl_forest_extend_pose_f32": (C.c_int, [_p, _i32, _p, _i64]),
     "octl_forest_extend_pose_device_f32": (C.c_int, [_p, _i32, _p, _i64]),
     "octl_forest_build": (C.c_int, [_p, _i64, _p, _i32, _i32, _i32, C.POINTER(BuildInfo)]),
+    "octl_forest_build_planar": (C.c_int, [_p, _i64, _f64, _i32, _i32, _p, _i32, _i32, C.POINTER(BuildInfo)]),
+    "octl_forest_get_split_stats": (C.c_int, [_p, _i64, _p, _p, _pi64]),
     "octl_forest_set_scheme": (C.c_int, [_p, _p, _p, _i64, _i32]),
     "octl_forest_get_nodes": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _pi64]),
     "octl_forest_get_voxels": (C.c_int, [_p, _i64, _p, _pi64]),

@@ -8,6 +8,10 @@ or as a plain lambda/def of exactly that shape, which is recognised from its byt
 double-checked by probing.  Any other callable is evaluated by the host, level by level, on the
 node point arrays the device produces (the predicate is the caller's Python code and can only
 run there); the bucketing / partition / ordering stays on the device.
+
+``NotPlanar`` is the second criterion with a device form: "split while the points are not flat" (smallest
+eigenvalue of the covariance above a threshold).  It is an ordinary NumPy callable, and lists of count criteria and
+``NotPlanar`` instances are recognised (``try_planar_threshold``) and evaluated inside the level loop on the device.
 """
 
 import dis
@@ -16,8 +20,8 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-__all__ = ["MaxPoints", "count_threshold", "try_count_threshold", "try_count_interval",
-           "UnsupportedCriterion"]
+__all__ = ["MaxPoints", "NotPlanar", "count_threshold", "try_count_threshold", "try_count_interval",
+           "try_planar_threshold", "UnsupportedCriterion"]
 
 
 class UnsupportedCriterion(NotImplementedError):
@@ -35,6 +39,55 @@ class MaxPoints:
 
     def __repr__(self):
         return f"MaxPoints({self.k})"
+
+
+class NotPlanar:
+    """Subdivide a node while its points are not flat::
+
+        n = len(points)
+        False                                    if n < min_points
+        C = sum (p - mean)(p - mean)^T / (n - ddof)
+        True  iff  the smallest eigenvalue of C  >  max_variance
+
+    This ``__call__`` (NumPy, two-pass, ``eigvalsh``) is the definition; a list of count criteria and ``NotPlanar``
+    instances given to ``subdivide`` of Grid / OctreeManager / Octree is evaluated on the device instead
+    (octl_forest_build_planar), a one-pass shifted f64 reduction that may differ from it only where the statistic is
+    within rounding (about 1e-11 of the squared node edge) of ``max_variance``.
+
+    Depth bound: the smallest eigenvalue is at most trace(C) / 3, and every axis variance of points inside a cube
+    of edge e is at most e^2 / 4 (times n / (n - 1) <= 4 / 3 for ddof = 1), so no node with e^2 / 3 <= max_variance
+    splits, whatever its points - duplicates included.  That is why ``max_variance`` must be > 0.
+
+    ValueError unless ``max_variance`` is finite and > 0, ``min_points >= 4`` and ``ddof`` is 0 or 1."""
+
+    def __init__(self, max_variance: float, min_points: int = 8, ddof: int = 0):
+        mv = float(max_variance)
+        if not np.isfinite(mv) or not mv > 0.0:
+            raise ValueError(f"max_variance must be finite and > 0, got {max_variance!r}")
+        if int(min_points) != min_points or int(min_points) < 4:
+            raise ValueError(f"min_points must be an integer >= 4, got {min_points!r}")
+        if ddof not in (0, 1):
+            raise ValueError(f"ddof must be 0 or 1, got {ddof!r}")
+        self.max_variance = mv
+        self.min_points = int(min_points)
+        self.ddof = int(ddof)
+
+    def smallest_eigenvalue(self, points) -> float:
+        """The statistic itself (NaN below ``min_points``)."""
+        p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        n = len(p)
+        if n < self.min_points:
+            return float("nan")
+        d = p - p.mean(axis=0)
+        return float(np.linalg.eigvalsh(d.T @ d / (n - self.ddof))[0])
+
+    def __call__(self, points) -> bool:
+        if len(points) < self.min_points:
+            return False
+        return self.smallest_eigenvalue(points) > self.max_variance
+
+    def __repr__(self):
+        return f"NotPlanar({self.max_variance!r}, min_points={self.min_points}, ddof={self.ddof})"
 
 
 def _resolve(fn, ins):
@@ -252,3 +305,31 @@ def count_threshold(criteria: Sequence[Callable]) -> int:
         # len(points) > K with K < 0 is true for empty nodes: the reference recurses forever
         raise RecursionError("the criterion is true for empty nodes: subdivision never terminates")
     return min(ks)  # any(): the smallest threshold decides
+
+
+def _is_plain_not_planar(c) -> bool:
+    """A NotPlanar, or an instance of a subclass that leaves __call__ alone."""
+    return isinstance(c, NotPlanar) and type(c).__call__ is NotPlanar.__call__ and "__call__" not in vars(c)
+
+
+def try_planar_threshold(criteria: Sequence[Callable]):
+    """(K, max_variance, min_points, ddof) when the list consists of count criteria (as try_count_threshold
+    recognises them) and at least one NotPlanar, with any() semantics: the smallest K (-1 when there is no count
+    criterion) and ONE planar rule.  Several NotPlanar reduce to one rule when they share min_points and ddof (the
+    smallest max_variance decides); otherwise their OR is not a single parameter set and the result is None, as it
+    is for anything else in the list (a lambda around a NotPlanar included): the host evaluates those."""
+    if criteria is None:
+        return None
+    planar = [c for c in criteria if _is_plain_not_planar(c)]
+    if not planar:
+        return None
+    rest = [c for c in criteria if not _is_plain_not_planar(c)]
+    if any(isinstance(c, NotPlanar) for c in rest):   # (a subclass with its own __call__)
+        return None
+    try:
+        k = count_threshold(rest)
+    except UnsupportedCriterion:
+        return None
+    if len({(c.min_points, c.ddof) for c in planar}) != 1:
+        return None
+    return k, min(c.max_variance for c in planar), planar[0].min_points, planar[0].ddof

@@ -141,7 +141,7 @@ void octl_forest_destroy(octl_forest* f) {
         &f->hist, &f->idxbuf[0], &f->idxbuf[1], &f->pathbuf[0], &f->pathbuf[1], &f->flags,
         &f->entries, &f->split[0], &f->split[1], &f->split_tiles[0], &f->split_tiles[1],
         &f->child_sc, &f->pose_off_dev, &f->scheme_dev, &f->root_up, &f->vlin_dev, &f->vcode_dev[0],
-        &f->vcode_dev[1]})
+        &f->vcode_dev[1], &f->split_lambda, &f->split_n})
     devbuf_release(f->ctx, *b);
   delete f;
 }
@@ -181,25 +181,54 @@ int octl_forest_clear(octl_forest* f) {
   f->n_ord = 0;
   f->n_blocks = 0;
   f->mask_valid = false;
+  f->split_stats_valid = false;
   return OCTL_OK;
+}
+
+// a build that failed half way has overwritten scratch the previous tables referred to: the forest is left WITHOUT
+// a scheme (its points and voxels are kept); the next build starts from the top-level voxels again
+static void forest_drop_scheme(octl_forest* f) {
+  f->built = false;
+  f->n_ord = 0;
+  f->n_blocks = 0;
+  f->n_internal = 0;
+  f->mask_valid = false;
+  f->store_dirty = true;
+  f->split_stats_valid = false;
 }
 
 int octl_forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
                       int32_t keep_scheme, int32_t max_depth, octl_build_info* info) {
   if (!f) return OCTL_E_INVALID;
   OCTL_TRY(forest_settle(f));
+  const int64_t nodes_before = f->built ? f->nodes[f->cur].n : -1, voxels_before = f->n_voxels;
   const int rc = forest_build(f, K, scheme_mask, n_mask, keep_scheme, max_depth, info);
-  if (rc != OCTL_OK && rc != OCTL_E_INVALID && rc != OCTL_E_STATE) {
-    // a build that failed half way has overwritten scratch the previous tables referred to:
-    // the forest is left WITHOUT a scheme (its points and voxels are kept); the next build starts
-    // from the top-level voxels again
-    f->built = false;
-    f->n_ord = 0;
-    f->n_blocks = 0;
-    f->n_internal = 0;
-    f->mask_valid = false;
-    f->store_dirty = true;
-  }
+  if (rc != OCTL_OK && rc != OCTL_E_INVALID && rc != OCTL_E_STATE) forest_drop_scheme(f);
+  // the split statistics of a planar build describe the node table it left: a placement into that scheme that adds
+  // no voxel keeps the numbering (roots in voxel order, children in the order of their parents), anything else
+  // renumbers or replaces the nodes
+  if (rc == OCTL_OK && (!keep_scheme || f->nodes[f->cur].n != nodes_before || f->n_voxels != voxels_before))
+    f->split_stats_valid = false;
+  return rc;
+}
+
+int octl_forest_build_planar(octl_forest* f, int64_t K, double max_variance, int32_t min_points, int32_t ddof,
+                             const uint8_t* scheme_mask, int32_t n_mask, int32_t max_depth, octl_build_info* info) {
+  if (!f) return OCTL_E_INVALID;
+  OCTL_TRY(forest_settle(f));
+  octl_ctx* ctx = f->ctx;
+  // (max_variance > 0 is what bounds the depth: the statistic of points inside a cube of edge e is at most e^2 / 3)
+  if (!(max_variance > 0.0) || !(max_variance <= 1.7976931348623157e308))
+    return octl_set_error(ctx, OCTL_E_INVALID, "build_planar: max_variance must be finite and > 0 (got %g)",
+                          max_variance);
+  if (min_points < 4)
+    return octl_set_error(ctx, OCTL_E_INVALID, "build_planar: min_points must be >= 4 (got %d)", min_points);
+  if (ddof != 0 && ddof != 1)
+    return octl_set_error(ctx, OCTL_E_INVALID, "build_planar: ddof must be 0 or 1 (got %d)", ddof);
+  const PlanarRule rule{max_variance, min_points, ddof};
+  f->split_stats_valid = false;
+  const int rc = forest_build(f, K, scheme_mask, n_mask, 0, max_depth, info, &rule);
+  if (rc != OCTL_OK && rc != OCTL_E_INVALID && rc != OCTL_E_STATE) forest_drop_scheme(f);
   return rc;
 }
 
@@ -234,6 +263,7 @@ int octl_forest_set_scheme(octl_forest* f, const int32_t* first_child, const int
   t.n = n_nodes;
   f->n_internal = n_internal;
   f->uniform_epoch = false;
+  f->split_stats_valid = false;
   if (new_epoch > f->epoch) f->epoch = new_epoch;
   // only first_child / epoch of this table are meaningful until the next (keep_scheme) build,
   // which has to place every point again

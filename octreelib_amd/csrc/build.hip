@@ -565,6 +565,37 @@ __global__ __launch_bounds__(256) void k_split_flags(NodePtrs nd, int64_t first,
   flags[j] = split ? 1u : 0u;
 }
 
+// ... and of a planar build (octl_forest_build_planar; kernels of their own, so that the count-driven loop above
+// stays as it is): scheme-pose count > K, or at least min_points scheme points whose statistic - the value
+// split_planar.hip stored for the node, read by both kernels, never recomputed - exceeds max_variance (a NaN, "not
+// evaluated", compares false)
+__device__ __forceinline__ bool planar_split(const NodePtrs& nd, int64_t c, int64_t K, PlanarRule rule,
+                                             const double* __restrict__ lambda) {
+  const int64_t n = nd.scount[c];
+  return (K >= 0 && n > K) || (n >= rule.min_points && lambda[c] > rule.max_variance);
+}
+__global__ __launch_bounds__(256) void k_split_flags_planar(NodePtrs nd, int64_t first, int64_t n_new, int64_t K,
+                                                            PlanarRule rule, const double* __restrict__ lambda,
+                                                            uint32_t* __restrict__ flags) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_new) return;
+  flags[j] = planar_split(nd, first + j, K, rule, lambda) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_compact_split_planar(NodePtrs nd, int64_t first, int64_t n_new,
+                                                              const uint32_t* __restrict__ flags_scanned, int64_t K,
+                                                              PlanarRule rule, const double* __restrict__ lambda,
+                                                              int32_t* __restrict__ split_nodes,
+                                                              uint32_t* __restrict__ split_tiles) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_new) return;
+  const int64_t c = first + j;
+  if (planar_split(nd, c, K, rule, lambda)) {
+    const uint32_t pos = flags_scanned[j];
+    split_nodes[pos] = (int32_t)c;
+    split_tiles[pos] = (nd.count[c] + LV_TILE - 1) / LV_TILE;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_compact_split(NodePtrs nd, int64_t first, int64_t n_new,
                                                        const uint32_t* __restrict__ flags_scanned,
                                                        int keep_mode, int64_t K,
@@ -1132,6 +1163,8 @@ struct LevelLoop {
   // records of a prefix partition (4 doubles per point; the indices are record positions then)
   const double* gx = nullptr;
   int xs = 3;
+  // the second split rule of a planar build (never with keep_scheme or resume); nullptr: count only
+  const PlanarRule* planar = nullptr;
 };
 
 // The first launch of a build (round 5: was the scalar block's copy, k_geom_set and - from octl_forest_clear -
@@ -1169,17 +1202,30 @@ static int run_level_loop(LevelLoop& L) {
     }
     int32_t* split_nodes = f->split[0].as<int32_t>();
     uint32_t* tile_base = f->split_tiles[0].as<uint32_t>();
+    // a planar build: the statistic of the fresh nodes first (their points are in this level's buffer)
+    if (L.planar)
+      OCTL_TRY(planar_level_stats(f, *L.planar, nt, L.first_new, L.n_new,
+                                  (const uint32_t*)f->idxbuf[L.level & 1].as<uint32_t>(), gx, L.xs, L.n_alive));
     {
       KTimer t(ctx, "level_prepare");
       const int leaves_only = (L.resume && L.level == 0) ? 1 : 0;
-      OCTL_LAUNCH(k_split_flags, dim3(grid_for(L.n_new)), dim3(256), 0, st, nd, L.first_new,
+      const double* lambda = f->split_lambda.as<double>();
+      if (L.planar)
+        OCTL_LAUNCH(k_split_flags_planar, dim3(grid_for(L.n_new)), dim3(256), 0, st, nd, L.first_new, L.n_new, L.K,
+                    *L.planar, lambda, flags);
+      else
+        OCTL_LAUNCH(k_split_flags, dim3(grid_for(L.n_new)), dim3(256), 0, st, nd, L.first_new,
                          L.n_new, L.keep_scheme, L.K, L.old_fc, leaves_only, flags);
       HIP_TRY(ctx, hipGetLastError());
       OCTL_TRY(octl_exclusive_scan_u32(ctx, flags, flags, L.n_new, small + SM_NSPLIT));
       // tiles of the nodes that split: scanned over L.n_new entries (zeros beyond the ns that are
       // filled) so that ns and the tile count come back in ONE readback
       HIP_TRY(ctx, hipMemsetAsync(tile_base, 0, (size_t)(L.n_new + 8) * 4, st));
-      OCTL_LAUNCH(k_compact_split, dim3(grid_for(L.n_new)), dim3(256), 0, st, nd, L.first_new,
+      if (L.planar)
+        OCTL_LAUNCH(k_compact_split_planar, dim3(grid_for(L.n_new)), dim3(256), 0, st, nd, L.first_new, L.n_new,
+                    (const uint32_t*)flags, L.K, *L.planar, lambda, split_nodes, tile_base);
+      else
+        OCTL_LAUNCH(k_compact_split, dim3(grid_for(L.n_new)), dim3(256), 0, st, nd, L.first_new,
                          L.n_new, (const uint32_t*)flags, L.keep_scheme, L.K, L.old_fc, leaves_only,
                          split_nodes, tile_base);
       HIP_TRY(ctx, hipGetLastError());
@@ -1268,7 +1314,8 @@ static int run_level_loop(LevelLoop& L) {
                            gx, L.xs, shift, (const uint32_t*)entries,
                            (int32_t)child_base, f->idxbuf[src ^ 1].as<uint32_t>(),
                            f->pathbuf[src ^ 1].as<uint32_t>(), pos_node, small,
-                           (L.all_scheme && !L.keep_scheme && !L.resume && L.K >= 0 && L.level + 1 < L.max_depth)
+                           (L.all_scheme && !L.keep_scheme && !L.resume && !L.planar && L.K >= 0 &&
+                            L.level + 1 < L.max_depth)
                                ? L.K : (int64_t)-1);
         HIP_TRY(ctx, hipGetLastError());
       }
@@ -1326,7 +1373,7 @@ static int forest_ensure_origin(octl_forest* f) {
 }
 
 int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
-                 int32_t keep_scheme, int32_t max_depth, octl_build_info* info) {
+                 int32_t keep_scheme, int32_t max_depth, octl_build_info* info, const PlanarRule* planar) {
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1336,6 +1383,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
     return octl_set_error(ctx, OCTL_E_INVALID, "more than 2^31-1 points in one forest");
   if (keep_scheme && !f->built)
     return octl_set_error(ctx, OCTL_E_STATE, "keep_scheme build without a previous scheme");
+  if (keep_scheme && planar) return octl_set_error(ctx, OCTL_E_INVALID, "a planar build makes its own scheme");
   if (scheme_mask && n_mask != n_poses)
     return octl_set_error(ctx, OCTL_E_INVALID, "scheme mask has %d entries for %d poses", n_mask,
                           n_poses);
@@ -1425,7 +1473,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   // (K < 0, "never split", over a scheme that has no internal nodes - the state between insert_points calls
   //  before the first subdivide - is the same thing: new points into the existing roots, new voxels as
   //  new roots; only the build counter advances)
-  const bool unsplit_again = !keep_scheme && K < 0 && f->built && f->n_internal == 0;
+  const bool unsplit_again = !keep_scheme && !planar && K < 0 && f->built && f->n_internal == 0;
   if (keep_scheme || unsplit_again) {
     int done = 0;
     OCTL_TRY(forest_insert_incremental(f, &done, info));
@@ -1449,7 +1497,8 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   //         must all be there again) ----------------------------------------------------------------------------
   const bool fresh0 = !f->built && f->vkeys.empty() && !f->vkeys_stale;
   const bool over_old = f->built && !ctx->opt.no_bucket_history;
-  if (!keep_scheme && (fresh0 || over_old) && n_alive > 0) {
+  // (not a planar build: its statistic is evaluated level by level, by the level loop below)
+  if (!keep_scheme && !planar && (fresh0 || over_old) && n_alive > 0) {
     NodeTable& bt = f->nodes[f->cur ^ 1];
     const int cur_epoch = f->epoch + 1;
     BucketBuildArgs ba{K, scheme_dev, cur_epoch, max_depth};
@@ -1565,7 +1614,8 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   uint32_t pre_stride = 0;
   // (OCTL_CUBE_PREFIX_MIN: tests run this path on small clouds; OCTL_NO_CUBE_PREFIX: never)
   const int64_t prefix_min = ctx->opt.cube_prefix_min > 0 ? ctx->opt.cube_prefix_min : ((int64_t)4 << 20);
-  if (cube_fast && all_scheme && !keep_scheme && K >= 0 && n_alive >= prefix_min && !ctx->opt.no_cube_prefix) {
+  if (cube_fast && all_scheme && !keep_scheme && !planar && K >= 0 && n_alive >= prefix_min &&
+      !ctx->opt.no_cube_prefix) {
     for (int c = 4; c >= 2 && !pm; --c)   // every node above depth pm has to split: expect >= 2 K points per depth-pm node
       if (n_alive >= 2 * std::max<int64_t>(K, 1) * ((int64_t)1 << (3 * c)) && c <= max_depth) pm = c;
     if (pm) OCTL_TRY(forest_prefix_partition(f, pm, &pre_recs, &pre_bstart, &pre_stride, &pre_bad));
@@ -1858,6 +1908,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   std::vector<octl_forest::LevelSeg> segs{{0, V, 0}};
   LevelLoop L{f, &nt, K, (int)keep_scheme, all_scheme, scheme_dev, old_fc, old_epoch, cur_epoch, max_depth,
               n_alive, false, first_new, n_new, 0, 0, &segs};
+  L.planar = planar;
   if (pm) {  // levels 0 .. pm-1 are done: all of their nodes are internal
     for (int d = 1; d <= pm; ++d) segs.push_back({top_base(d), top_base(d + 1), d});
     L.first_new = top_base(pm);
@@ -1945,6 +1996,13 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   f->built_store = f->n_store;
   f->built_poses = n_poses;
   f->append_only = true;
+  if (planar) {  // what the decisions saw, for octl_forest_get_split_stats (the statistic is in place already)
+    OCTL_TRY(devbuf_reserve(ctx, f->split_n, (size_t)std::max<int64_t>(nt.n, 1) * 4));
+    if (nt.n > 0)
+      HIP_TRY(ctx, hipMemcpyAsync(f->split_n.p, nt.scount.p, (size_t)nt.n * 4, hipMemcpyDeviceToDevice, st));
+    f->split_stats_nodes = nt.n;
+    f->split_stats_valid = true;
+  }
   if (info) {
     info->n_points = n_alive;
     info->n_voxels = V;

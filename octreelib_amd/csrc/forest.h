@@ -37,6 +37,13 @@ struct NodeTable {
   int64_t cap = 0, n = 0;
 };
 
+// the second split rule of octl_forest_build_planar (criteria.py: NotPlanar): a node with at least min_points scheme
+// points splits when the smallest eigenvalue of their covariance (divisor n - ddof) exceeds max_variance
+struct PlanarRule {
+  double max_variance;
+  int32_t min_points, ddof;
+};
+
 struct octl_forest {
   octl_ctx* ctx = nullptr;
   int mode = 0;  // 0 grid, 1 single cube
@@ -96,6 +103,12 @@ struct octl_forest {
   int64_t n_internal = 0;
   bool uniform_epoch = true;  // every internal node of the current scheme has the same epoch
   int32_t max_depth_reached = 0;
+  // octl_forest_get_split_stats: what the split decisions of the last planar build saw, per node of the current
+  // table - the statistic (split_planar.hip writes it level by level) and the scheme-point count (copied when the
+  // build commits).  Valid while the table is the one that build left: any later build that renumbers it drops them.
+  DevBuf split_lambda, split_n;  // f64, u32 [split_stats_nodes]
+  bool split_stats_valid = false;
+  int64_t split_stats_nodes = 0;
 
   // leaf-ordered arrays of the last build
   DevBuf ord_idx;    // u32 [n_ord] store index of the point at storage position i
@@ -150,8 +163,13 @@ struct octl_forest {
       split_tiles[2], child_sc, pose_off_dev, scheme_dev, root_up;
 };
 
+// planar != nullptr: the scheme for "count > K OR planar rule" (K < 0: no count rule), always through the level loop
 int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
-                 int32_t keep_scheme, int32_t max_depth, octl_build_info* info);
+                 int32_t keep_scheme, int32_t max_depth, octl_build_info* info, const PlanarRule* planar = nullptr);
+// split_planar.hip: the planar statistic of the fresh nodes [first_new, first_new + n_new) of table nt into
+// f->split_lambda; idx = the level buffer that holds their points, xyz / xs = the coordinates behind its indices
+int planar_level_stats(octl_forest* f, const PlanarRule& rule, NodeTable& nt, int64_t first_new, int64_t n_new,
+                       const uint32_t* idx, const double* xyz, int xs, int64_t n_alive);
 int nodes_reserve(octl_ctx* ctx, NodeTable& t, int64_t cap);
 void nodes_free(octl_ctx* ctx, NodeTable& t);
 

@@ -14,7 +14,7 @@ import numpy as np
 
 from octreelib_amd import _views
 from octreelib_amd._engine import Forest
-from octreelib_amd.criteria import try_count_threshold
+from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, VisualizationConfig
 from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
@@ -76,8 +76,11 @@ class Grid(GridBase):
     def subdivide(self, subdivision_criteria: List[Callable], pose_numbers: Optional[List[int]] = None):
         if self._plug is not None:
             return self._plug.subdivide(subdivision_criteria, pose_numbers)
-        k = try_count_threshold(subdivision_criteria)
         scheme = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+        rule = try_planar_threshold(subdivision_criteria)
+        if rule is not None:
+            return self._forest.subdivide_planar(rule, scheme)
+        k = try_count_threshold(subdivision_criteria)
         if k is None:
             self._forest.subdivide_callable(subdivision_criteria, scheme)
         else:

@@ -10,7 +10,7 @@ import numpy as np
 
 from octreelib_amd import _views
 from octreelib_amd._engine import Forest
-from octreelib_amd.criteria import try_count_threshold
+from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.internal.voxel import Voxel, VoxelBase
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase
@@ -56,12 +56,15 @@ class OctreeManager(VoxelBase):
     def subdivide(self, subdivision_criteria: List[Callable], pose_numbers: Optional[List[int]] = None):
         if self._plug is not None:
             return self._plug.subdivide(subdivision_criteria, pose_numbers)
-        k = try_count_threshold(subdivision_criteria)
+        rule = try_planar_threshold(subdivision_criteria)
+        k = None if rule is not None else try_count_threshold(subdivision_criteria)
         if pose_numbers is None:
             scheme = None
         else:
             scheme = [self._slots[p] for p in pose_numbers]  # KeyError for an unknown pose, as upstream
-        if k is None:
+        if rule is not None:
+            self._forest.subdivide_planar(rule, scheme)
+        elif k is None:
             self._forest.subdivide_callable(subdivision_criteria, scheme)
         else:
             self._forest.subdivide(k, scheme)
