@@ -247,6 +247,49 @@ int octl_forest_gather_blocks(octl_forest* f, const int32_t* block_ids, int64_t 
  * id outside [0, n_blocks).                                                                                       */
 int octl_forest_leaf_stats(octl_forest* f, const int32_t* block_ids, int64_t nb, int64_t* count, double* mean,
                            double* cov, double* eigval, double* eigvec);
+/* One plane per LEAF over a set of poses (a map plane pools the poses that observed the leaf): for every leaf that
+ * holds at least one point of the poses with slot_sel[slot] != 0 (NULL: all poses; otherwise n_sel = number of poses),
+ * in ascending node id (the row index of octl_forest_get_nodes), the node, the count, mean, population covariance
+ * (6 upper-triangle values) and eigen-decomposition - conventions, sign rule and solver of octl_forest_leaf_stats - of
+ * ALL its points of those poses together.  *n_leaves = number of such leaves; rows are written only when cap >=
+ * *n_leaves (size query: cap = 0); any output may be NULL.  Arithmetic: anchor a = the leaf's centre (corner + edge/2),
+ * every (leaf, pose) block's sums of d = p - a and d d^T by the chunked wave reduction of octl_forest_leaf_stats, the
+ * blocks added in ascending slot order.  With B pooled blocks, the largest of n_max points, g = (ceil(n_max / 64) +
+ * ceil(n_max / 4096) + B + 16) * 2^-53 and R = max |p - a|_inf over the pooled points: mean within 2 g R + 2^-53 |mean|,
+ * every covariance entry within 4 g R^2 of the exact value; eigenvalues within 64 * 2^-53 * |C|_F of those of the
+ * returned covariance.  A leaf's bits depend on its own points and on the selection only.  The table also stays on
+ * the device for octl_forest_point_to_plane, until a call changes the forest's contents or scheme (build*, add_pose*,
+ * extend_pose*, apply_mask*, apply_host_mask, filter_count, set_contents, set_scheme, clear).  Read-only otherwise.
+ * OCTL_E_STATE before the first build.  No reference counterpart (the reference has no per-leaf statistics).        */
+int octl_forest_pooled_leaf_stats(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int64_t cap, int32_t* node,
+                                  int64_t* count, double* mean, double* cov6, double* eigval, double* eigvec,
+                                  int64_t* n_leaves);
+/* Which leaf of the scheme does each of n query points (n,3) f64 fall into?  node[i] = id (row of
+ * octl_forest_get_nodes) of the leaf whose cube contains point i, found exactly as the point of a late pose is placed
+ * (voxel by floor division, root by binary search over the sorted voxel keys, descent by the reference's child-index
+ * comparisons, octree/octree.py:67-100); -1 for a point whose top-level voxel the scheme does not hold, that lies
+ * outside the single cube of a mode-1 forest or outside the cube of a split node, outside the voxel domain, or is not
+ * finite.  Such a point raises nothing and leaves octl_last_error alone.  Read-only: tables, store, counters, a
+ * pending mask are untouched; an unsubdivided forest answers with root nodes.  One kernel (plus the voxel-key sync the
+ * first time after a build); the host form adds one upload, one download and one wait.  OCTL_E_STATE before the
+ * first build.  No reference counterpart: the reference can only insert the points, which changes the tree.        */
+int octl_forest_locate(octl_forest* f, const double* xyz, int64_t n, int32_t* node);
+/* The same with pointers from octl_dev_alloc: nothing is downloaded and the host does not wait (the answer is
+ * complete in stream order: octl_dev_download / octl_ctx_sync).  No reference counterpart.                        */
+int octl_forest_locate_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t* node_dev);
+/* octl_forest_locate fused with the plane of the leaf in the table of the last octl_forest_pooled_leaf_stats
+ * (OCTL_E_STATE, with a message that names the cause, if there is none or the forest has changed since): row[i] =
+ * row of that table, or -1 when node[i] < 0, the leaf holds no pooled point, fewer than min_points of them, or (when
+ * max_variance >= 0) a smallest eigenvalue above max_variance; distance[i] = the signed distance
+ * fma(nx, dx, fma(ny, dy, nz * dz)), d = p - mean, n = the smallest eigenvalue's vector, NaN where row[i] < 0.  Given
+ * the table's own plane bits the result is within 4 * 2^-53 * (|nx dx| + |ny dy| + |nz dz|) of the exact value.
+ * One kernel; the host form adds one upload, three downloads and one wait.  No reference counterpart.              */
+int octl_forest_point_to_plane(octl_forest* f, const double* xyz, int64_t n, int32_t min_points, double max_variance,
+                               int32_t* node, int32_t* row, double* distance);
+/* The same with pointers from octl_dev_alloc; no host wait.  No reference counterpart.                             */
+int octl_forest_point_to_plane_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t min_points,
+                                      double max_variance, int32_t* node_dev, int32_t* row_dev,
+                                      double* distance_dev);
 /* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
 int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 

@@ -14,6 +14,9 @@ raises.
 
 from octreelib_amd.criteria import MaxPoints, NotPlanar
 from octreelib_amd.feed import DeviceCloud, ScanPipeline, pinned_empty, upload_async
+from octreelib_amd.query import (LeafPlanes, PointToPlane, locate_np, point_to_plane_np,
+                                 pooled_leaf_statistics_np)
 
 __version__ = "0.1.0"
-__all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "__version__"]
+__all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "LeafPlanes",
+           "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np", "__version__"]

@@ -75,6 +75,7 @@ class Forest:
         self._slot_blocks = None
         self._counts = None
         self._internal = None
+        self._pooled = None      # (pose selection, LeafPlanes) of the pooled table the device holds
 
     # -- points -----------------------------------------------------------------------------
     def add_pose(self, points) -> int:
@@ -570,6 +571,84 @@ class Forest:
         self.ctx.check(self.lib.octl_forest_leaf_stats(self.handle, nat.ptr(ids), n, nat.ptr(count), nat.ptr(mean),
                                                        nat.ptr(cov), nat.ptr(w), nat.ptr(v)))
         return LeafStatistics(count, mean, cov6_to_full(cov), w, v)
+
+    # -- queries (octreelib_amd/query.py is the host definition of each) -----------------------------------------
+    def locate(self, points) -> np.ndarray:
+        """int32 node id of the scheme leaf every query point falls into, -1 where there is none
+        (octl_forest_locate: one kernel, read-only)."""
+        from octreelib_amd.query import _as_queries
+
+        pts = _as_queries(points)
+        self.ensure_built()
+        out = np.empty(len(pts), dtype=np.int32)
+        if len(pts):
+            self.ctx.check(self.lib.octl_forest_locate(self.handle, nat.ptr(pts), len(pts), nat.ptr(out)))
+        return out
+
+    def locate_device(self, xyz_dptr, n: int, node_dptr):
+        """locate for points that are in device memory already, answers left there (pointers from octl_dev_alloc);
+        enqueued on the context's stream, the host does not wait."""
+        self.ensure_built()
+        self.ctx.check(self.lib.octl_forest_locate_device(self.handle, xyz_dptr, int(n), node_dptr))
+
+    def leaf_planes(self, slots=None):
+        """One plane per leaf over the poses of `slots` (None: all), all their points pooled
+        (octl_forest_pooled_leaf_stats): a LeafPlanes in ascending node id.  The device keeps the table for
+        point_to_plane; the same selection on an unchanged forest is answered from the copy made here."""
+        from octreelib_amd.leaf_stats import cov6_to_full
+        from octreelib_amd.query import LeafPlanes
+
+        self.ensure_built()
+        key = None if slots is None else tuple(sorted(set(int(s) for s in slots)))
+        if self._pooled is not None and self._pooled[0] == key:
+            return self._pooled[1]
+        sel = None
+        if key is not None and self.n_slots > 0:
+            sel = np.zeros(self.n_slots, dtype=np.uint8)
+            sel[list(key)] = 1
+        n_sel = self.n_slots if sel is not None else 0
+        n = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_pooled_leaf_stats(self.handle, nat.ptr(sel), n_sel, 0, None, None, None,
+                                                              None, None, None, C.byref(n)))
+        m = n.value
+        node = np.empty(m, dtype=np.int32)
+        count = np.empty(m, dtype=np.int64)
+        mean = np.empty((m, 3), dtype=np.float64)
+        cov = np.empty((m, 6), dtype=np.float64)
+        w = np.empty((m, 3), dtype=np.float64)
+        v = np.empty((m, 3, 3), dtype=np.float64)
+        if m:
+            self.ctx.check(self.lib.octl_forest_pooled_leaf_stats(
+                self.handle, nat.ptr(sel), n_sel, m, nat.ptr(node), nat.ptr(count), nat.ptr(mean), nat.ptr(cov),
+                nat.ptr(w), nat.ptr(v), C.byref(n)))
+        planes = LeafPlanes(count, mean, cov6_to_full(cov), w, v, node)
+        self._pooled = (key, planes)
+        return planes
+
+    def point_to_plane(self, points, slots=None, min_points: int = 8, max_variance=None):
+        """Leaf, plane row and signed distance of every query point (octl_forest_point_to_plane: one fused kernel);
+        the pooled table is recomputed only when the device one is stale or was made for another selection."""
+        from octreelib_amd.query import PointToPlane, _as_queries
+
+        pts = _as_queries(points)
+        planes = self.leaf_planes(slots)
+        n = len(pts)
+        node = np.empty(n, dtype=np.int32)
+        row = np.empty(n, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float64)
+        if n:
+            mv = -1.0 if max_variance is None else float(max_variance)
+            self.ctx.check(self.lib.octl_forest_point_to_plane(self.handle, nat.ptr(pts), n, int(min_points), mv,
+                                                               nat.ptr(node), nat.ptr(row), nat.ptr(dist)))
+        return PointToPlane(node, row, dist, planes)
+
+    def point_to_plane_device(self, xyz_dptr, n: int, node_dptr, row_dptr, dist_dptr, min_points: int = 8,
+                              max_variance=None):
+        """point_to_plane against the pooled table the device holds (leaf_planes first), device pointers in and
+        out; the host does not wait."""
+        mv = -1.0 if max_variance is None else float(max_variance)
+        self.ctx.check(self.lib.octl_forest_point_to_plane_device(self.handle, xyz_dptr, int(n), int(min_points), mv,
+                                                                  node_dptr, row_dptr, dist_dptr))
 
     @property
     def perm(self) -> np.ndarray:

@@ -1393,6 +1393,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
                           "there and raises IndexError when such a leaf is subdivided (octree.py:94-98)");
   if (max_depth <= 0) max_depth = 63;
   f->fast_order_valid = false;  // (the block table is about to change)
+  f->pooled_valid = false;
   f->max_block_hint = INT64_MAX;
   BuildTrace trace;
   trace.on = ctx->opt.trace_build != 0;

@@ -308,6 +308,8 @@ struct KTimer {
 int octl_collect_timings(octl_ctx* ctx);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// byte offsets of the parts of a packed scratch buffer: every part starts 256-byte aligned
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // workgroups of 256 threads for n items, one item per thread (n = 0: no workgroup - the caller guards or clamps)
 static inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n, 256); }
 // bits needed to hold max_value (0 for 0)

@@ -110,6 +110,17 @@ struct octl_forest {
   bool split_stats_valid = false;
   int64_t split_stats_nodes = 0;
 
+  // octl_forest_pooled_leaf_stats (query.hip): one plane per leaf over a selection of poses.  pl_rows holds the result
+  // table of the last call as it is downloaded ([node i32 | count i64 | mean 3 | cov 6 | eigval 3 | eigvec 9], every
+  // part 256-byte aligned for pl_cap rows), pl_plane the 64-byte rows octl_forest_point_to_plane gathers
+  // {nx, ny, nz, mx, my, mz, lambda0, (double)count}, pl_node_row the row of every scheme node (-1: none).  Valid
+  // while contents and scheme are the ones the call saw: every entry point that changes either clears pooled_valid.
+  DevBuf pl_rows, pl_plane, pl_node_row, pl_sort, pl_hist;
+  bool pooled_valid = false;
+  int64_t pl_n = 0, pl_cap = 0;
+  std::vector<uint8_t> pl_sel;  // the pose selection of that call (empty: every pose)
+  DevBuf q_stage;               // staging of the host forms of the queries (points in, answers out)
+
   // leaf-ordered arrays of the last build
   DevBuf ord_idx;    // u32 [n_ord] store index of the point at storage position i
   DevBuf xyz_ord;    // f64 [n_ord][3]

@@ -25,20 +25,12 @@
 #include "build_common.h"
 #include "forest.h"
 #include "ref_arith.h"
+#include "scheme_walk.h"
 
 namespace {
 
 constexpr uint64_t KEY_MISS = 1ull << 63;
 constexpr uint64_t KEY_DEAD = ~0ull;
-
-__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t x) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ int slot_of(const int64_t* __restrict__ pose_off, int n_poses, int64_t i) {
   int lo = 0, hi = n_poses;  // largest p with pose_off[p] <= i
@@ -60,9 +52,7 @@ __global__ __launch_bounds__(256) void k_lin_to_code(const uint64_t* __restrict_
   code[v] = vkey_pack((int64_t)qx + m0, (int64_t)qy + m1, (int64_t)qz + m2, org);
 }
 
-// One new point: voxel (grid/grid.py:72-76), root by binary search, walk to the leaf
-// (octree/octree.py:67-100: idx = floor((p - corner) / (edge / 2)) per axis, child 4 ix + 2 iy + iz,
-// restated as exact comparisons on the same rounded differences, see compute_path in build.hip).
+// One new point: voxel, root and leaf by the walk of scheme_walk.h (shared with the queries of query.hip).
 __global__ __launch_bounds__(256) void k_inc_place(const double* __restrict__ xyz,
                                                    const uint8_t* __restrict__ alive, int64_t first,
                                                    int64_t n_new, int mode, double L, VoxOrg org,
@@ -82,48 +72,22 @@ __global__ __launch_bounds__(256) void k_inc_place(const double* __restrict__ xy
     return;
   }
   const double px = xyz[3 * i + 0], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
-  int qx = 0, qy = 0, qz = 0;
-  if (mode == 0) {
-    const double fx = floor_div_exact(px, L), fy = floor_div_exact(py, L), fz = floor_div_exact(pz, L);
-    const double lim = (double)OCTL_VOX_ABS_LIMIT;
-    if (!((fabs(fx) < lim) && (fabs(fy) < lim) && (fabs(fz) < lim) &&
-          vkey_in_window((int64_t)fx, (int64_t)fy, (int64_t)fz, org))) {  // also NaN
-      atomicExch(&small[SM_ERR], (uint32_t)(-OCTL_E_DOMAIN));
-      key[j] = KEY_DEAD;
-      return;
-    }
-    qx = (int)fx;
-    qy = (int)fy;
-    qz = (int)fz;
+  int32_t node = 0;
+  uint64_t code = 0;
+  const int status = scheme_walk(px, py, pz, mode, L, org, vcode, V, first_child, corner, edge, &node, &code);
+  if (status == WALK_DOMAIN) {
+    atomicExch(&small[SM_ERR], (uint32_t)(-OCTL_E_DOMAIN));
+    key[j] = KEY_DEAD;
+    return;
   }
-  const uint64_t code = vkey_pack(qx, qy, qz, org);
-  const int64_t r = lower_bound_u64(vcode, V, code);
-  if (r >= V || vcode[r] != code) {
+  if (status == WALK_MISS) {
     key[j] = KEY_MISS | code;
     atomicAdd(&small[SM_INC_MISS], 1u);
     return;
   }
-  int32_t node = (int32_t)r;
-  int32_t fc = first_child[node];
-  // (children are numbered behind their parents, so the walk ends; the bound only guards against a
-  //  damaged table - the general path then reports it)
-  for (int depth = 0; fc >= 0; ++depth) {
-    if (depth >= 64) {
-      atomicAdd(&small[SM_INC_BAD], 1u);
-      break;
-    }
-    const double cx = corner[3 * (int64_t)node + 0], cy = corner[3 * (int64_t)node + 1],
-                 cz = corner[3 * (int64_t)node + 2], e = edge[node];
-    const double h = e / 2.0;
-    const double ax = px - cx, ay = py - cy, az = pz - cz;
-    const bool ok = (ax >= 0.0) && (ax < e) && (ay >= 0.0) && (ay < e) && (az >= 0.0) && (az < e);
-    if (!ok) {  // the reference raises IndexError or picks a wrong child: left to the general path
-      atomicAdd(&small[SM_INC_BAD], 1u);
-      break;
-    }
-    node = fc + ((ax >= h ? 4 : 0) | (ay >= h ? 2 : 0) | (az >= h ? 1 : 0));
-    fc = first_child[node];
-  }
+  // WALK_OUTSIDE: the reference raises IndexError or picks a wrong child: left to the general path, which also
+  // reports a damaged table (WALK_DEEP)
+  if (status != WALK_LEAF) atomicAdd(&small[SM_INC_BAD], 1u);
   key[j] = (uint64_t)(uint32_t)node;
 }
 

@@ -211,8 +211,6 @@ __global__ __launch_bounds__(256) void k_sym3_eigen(const double* __restrict__ c
   for (int k = 0; k < 9; ++k) eigvec[9 * i + k] = v[k];
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int octl_forest_leaf_stats(octl_forest* f, const int32_t* block_ids, int64_t nb, int64_t* count,
@@ -310,5 +308,235 @@ extern "C" int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t 
   HIP_TRY(ctx, hipMemcpyAsync(eigval, base + o_w, (size_t)n * 24, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(eigvec, base + o_v, (size_t)n * 72, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
+  return OCTL_OK;
+}
+
+// ---- pooled planes: one plane per leaf over a selection of poses (octl_forest_pooled_leaf_stats) ----------------------
+// A map plane pools the poses that observed the leaf.  The (leaf, pose) blocks of the selected poses are grouped by
+// leaf on the device - sort of (node << slot bits | slot, block id), head flags, exclusive scan: row r = the r-th
+// leaf in ascending node id - and every leaf is reduced by one wave:
+//   anchor a = the leaf's centre, corner + edge / 2 (what split_planar.hip shifts by: the points of a leaf lie within
+//   edge / 2 of it unless map_leaf_points moved them),
+//   S = the leaf's blocks in ascending slot order, each block the sum over its chunks c = 0, 1, ... of P_c
+//       (chunk_sums above, d = p - a), the first block's sums taken as they are and every later one added to them,
+//   mean = a + S_d / n, cov = S_dd / n - (S_d / n)(S_d / n)^T (finish above), then sym3_eigen per row.
+// A leaf's bits depend on its own points and on the selection only.  The table stays on the device (forest.h) for
+// octl_forest_point_to_plane.
+namespace {
+
+__global__ __launch_bounds__(256) void k_pool_keys(const int32_t* __restrict__ blk_node,
+                                                   const int32_t* __restrict__ blk_slot, int64_t nb,
+                                                   const uint8_t* __restrict__ sel, int n_sel, int sbits, int kbits,
+                                                   uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nb) return;
+  const int32_t s = blk_slot[b];
+  const bool on = !sel || (s >= 0 && s < n_sel && sel[s] != 0);
+  // (an unselected block sorts behind every selected one: bit kbits is above any (node, slot) key)
+  key[b] = on ? (((uint64_t)(uint32_t)blk_node[b] << sbits) | (uint64_t)(uint32_t)s) : (1ull << kbits);
+  val[b] = (uint32_t)b;
+}
+
+__global__ __launch_bounds__(256) void k_pool_heads(const uint64_t* __restrict__ key, int64_t nb, int sbits, int kbits,
+                                                    uint32_t* __restrict__ heads) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb) return;
+  const uint64_t k = key[i];
+  heads[i] = ((k >> kbits) == 0 && (i == 0 || (key[i - 1] >> sbits) != (k >> sbits))) ? 1u : 0u;
+}
+
+// one wave per sorted position; the wave of a leaf's first block reduces the whole leaf
+__global__ __launch_bounds__(256) void k_pool_moments(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val,
+                                                      const uint32_t* __restrict__ row_of, int64_t nb, int sbits,
+                                                      int kbits, const uint32_t* __restrict__ blk_start,
+                                                      const int32_t* __restrict__ blk_size,
+                                                      const double* __restrict__ xyz,
+                                                      const double* __restrict__ corner,
+                                                      const double* __restrict__ edge, int64_t n_rows,
+                                                      int32_t* __restrict__ node_out, int64_t* __restrict__ count,
+                                                      double* __restrict__ mean, double* __restrict__ cov) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= nb) return;
+  const int lane = threadIdx.x & 63;
+  const uint64_t k = key[i];
+  if ((k >> kbits) != 0) return;
+  const uint64_t node = k >> sbits;
+  if (i > 0 && (key[i - 1] >> sbits) == node) return;
+  const int64_t row = row_of[i];
+  if (row >= n_rows) return;  // (never: the tables are sized from the scan's total)
+  const double h = edge[node] / 2.0;
+  const double ax = corner[3 * node + 0] + h, ay = corner[3 * node + 1] + h, az = corner[3 * node + 2] + h;
+  Sums S;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) S.s[q] = 0.0;
+  int64_t n_all = 0;
+  for (int64_t j = i; j < nb && (key[j] >> sbits) == node; ++j) {
+    const uint32_t b = val[j];
+    const int64_t s = blk_start[b];
+    const int32_t n = blk_size[b];
+    Sums B = chunk_sums(xyz, s, min(n, LS_CHUNK), ax, ay, az, lane);
+    for (int32_t c0 = LS_CHUNK; c0 < n; c0 += LS_CHUNK)
+      fold(B, chunk_sums(xyz, s + c0, min(n - c0, LS_CHUNK), ax, ay, az, lane));
+    if (j == i) S = B; else fold(S, B);
+    n_all += n;
+  }
+  if (lane == 0) {
+    node_out[row] = (int32_t)node;
+    count[row] = n_all;
+    finish(S, n_all, ax, ay, az, mean + 3 * row, cov + 6 * row);
+  }
+}
+
+// one lane per row: eigen-decomposition, the 64-byte plane row of octl_forest_point_to_plane, node -> row
+__global__ __launch_bounds__(256) void k_pool_eigen(int64_t n_rows, const int32_t* __restrict__ node,
+                                                    const int64_t* __restrict__ count, const double* __restrict__ mean,
+                                                    const double* __restrict__ cov, double* __restrict__ eigval,
+                                                    double* __restrict__ eigvec, double* __restrict__ plane,
+                                                    int32_t* __restrict__ node_row) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  double c6[6], w[3], v[9];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c6[k] = cov[6 * r + k];
+  sym3_eigen(c6, w, v);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) eigval[3 * r + k] = w[k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) eigvec[9 * r + k] = v[k];
+  double* p = plane + 8 * r;
+  p[0] = v[0], p[1] = v[3], p[2] = v[6];
+  p[3] = mean[3 * r + 0], p[4] = mean[3 * r + 1], p[5] = mean[3 * r + 2];
+  p[6] = w[0];
+  p[7] = (double)count[r];
+  node_row[node[r]] = (int32_t)r;
+}
+
+// layout of f->pl_rows for `cap` rows
+struct PoolLayout {
+  size_t o_count, o_mean, o_cov, o_w, o_v, total;
+  explicit PoolLayout(int64_t cap) {
+    const size_t c = (size_t)std::max<int64_t>(cap, 1);
+    o_count = align256(c * 4);
+    o_mean = o_count + align256(c * 8);
+    o_cov = o_mean + align256(c * 24);
+    o_w = o_cov + align256(c * 48);
+    o_v = o_w + align256(c * 24);
+    total = o_v + align256(c * 72);
+  }
+};
+
+int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t nb = f->n_blocks, n_nodes = f->nodes[f->cur].n;
+  const int n_poses = (int)f->pose_off.size() - 1;
+  f->pooled_valid = false;
+  OCTL_TRY(devbuf_reserve(ctx, f->pl_node_row, (size_t)std::max<int64_t>(n_nodes, 1) * 4));
+  if (n_nodes > 0) HIP_TRY(ctx, hipMemsetAsync(f->pl_node_row.p, 0xFF, (size_t)n_nodes * 4, st));
+  int64_t n_rows = 0;
+  if (nb > 0) {
+    const int sbits = std::max(1, bits_for((uint64_t)std::max(n_poses, 1)));
+    const int kbits = sbits + std::max(1, bits_for((uint64_t)n_nodes));
+    // f->pl_sort: [key u64 x2 | val u32 x2 | heads u32 (+8: the scan's tail) | selection u8 | scan total u32]
+    const size_t o_key1 = align256((size_t)nb * 8), o_val0 = 2 * o_key1, o_val1 = o_val0 + align256((size_t)nb * 4);
+    const size_t o_heads = o_val1 + align256((size_t)nb * 4), o_sel = o_heads + align256(((size_t)nb + 8) * 4);
+    const size_t o_total = o_sel + align256((size_t)std::max(n_poses, 1));
+    OCTL_TRY(devbuf_reserve(ctx, f->pl_sort, o_total + 256));
+    char* base = static_cast<char*>(f->pl_sort.p);
+    uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base), reinterpret_cast<uint64_t*>(base + o_key1)};
+    uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(base + o_val0), reinterpret_cast<uint32_t*>(base + o_val1)};
+    uint32_t* heads = reinterpret_cast<uint32_t*>(base + o_heads);
+    uint8_t* sel_d = reinterpret_cast<uint8_t*>(base + o_sel);
+    uint32_t* total_d = reinterpret_cast<uint32_t*>(base + o_total);
+    if (!sel.empty()) HIP_TRY(ctx, hipMemcpyAsync(sel_d, sel.data(), sel.size(), hipMemcpyHostToDevice, st));
+    {
+      KTimer t(ctx, "pool_group");
+      OCTL_LAUNCH(k_pool_keys, dim3(grid_for(nb)), dim3(256), 0, st, (const int32_t*)f->blk_node.as<int32_t>(),
+                  (const int32_t*)f->blk_slot.as<int32_t>(), nb, sel.empty() ? (const uint8_t*)nullptr : sel_d,
+                  (int)sel.size(), sbits, kbits, keys[0], vals[0]);
+      HIP_TRY(ctx, hipGetLastError());
+      int res = 0;
+      OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys, vals, nb, kbits + 1, f->pl_hist, &res));
+      OCTL_LAUNCH(k_pool_heads, dim3(grid_for(nb)), dim3(256), 0, st, (const uint64_t*)keys[res], nb, sbits, kbits,
+                  heads);
+      HIP_TRY(ctx, hipGetLastError());
+      OCTL_TRY(octl_exclusive_scan_u32(ctx, heads, heads, nb, total_d));
+      keys[0] = keys[res];
+      vals[0] = vals[res];
+    }
+    uint32_t total = 0;
+    OCTL_TRY(octl_readback(ctx, total_d, 1, &total));
+    n_rows = total;
+    if (n_rows > 0) {
+      const PoolLayout lay(n_rows);
+      OCTL_TRY(devbuf_reserve(ctx, f->pl_rows, lay.total));
+      OCTL_TRY(devbuf_reserve(ctx, f->pl_plane, (size_t)n_rows * 64));
+      char* rb = static_cast<char*>(f->pl_rows.p);
+      int32_t* node_d = reinterpret_cast<int32_t*>(rb);
+      int64_t* cnt_d = reinterpret_cast<int64_t*>(rb + lay.o_count);
+      double* mean_d = reinterpret_cast<double*>(rb + lay.o_mean);
+      double* cov_d = reinterpret_cast<double*>(rb + lay.o_cov);
+      {
+        KTimer t(ctx, "pool_moments");
+        const NodeTable& nt = f->nodes[f->cur];
+        OCTL_LAUNCH(k_pool_moments, dim3((unsigned)ceil_div(nb, 4)), dim3(256), 0, st, (const uint64_t*)keys[0],
+                    (const uint32_t*)vals[0], (const uint32_t*)heads, nb, sbits, kbits,
+                    (const uint32_t*)f->blk_start.as<uint32_t>(), (const int32_t*)f->blk_size.as<int32_t>(),
+                    (const double*)f->xyz_ord.as<double>(), (const double*)nt.corner.as<double>(),
+                    (const double*)nt.edge.as<double>(), n_rows, node_d, cnt_d, mean_d, cov_d);
+        HIP_TRY(ctx, hipGetLastError());
+      }
+      {
+        KTimer t(ctx, "pool_eigen");
+        OCTL_LAUNCH(k_pool_eigen, dim3(grid_for(n_rows)), dim3(256), 0, st, n_rows, (const int32_t*)node_d,
+                    (const int64_t*)cnt_d, (const double*)mean_d, (const double*)cov_d,
+                    reinterpret_cast<double*>(rb + lay.o_w), reinterpret_cast<double*>(rb + lay.o_v),
+                    f->pl_plane.as<double>(), f->pl_node_row.as<int32_t>());
+        HIP_TRY(ctx, hipGetLastError());
+      }
+    }
+  }
+  f->pl_n = f->pl_cap = n_rows;
+  f->pl_sel = sel;
+  f->pooled_valid = true;
+  return OCTL_OK;
+}
+
+}  // namespace
+
+extern "C" int octl_forest_pooled_leaf_stats(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int64_t cap,
+                                             int32_t* node, int64_t* count, double* mean, double* cov6, double* eigval,
+                                             double* eigvec, int64_t* n_leaves) {
+  if (!f || !n_leaves) return OCTL_E_INVALID;
+  OCTL_TRY(forest_settle(f));
+  octl_ctx* ctx = f->ctx;
+  if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "pooled_leaf_stats before build");
+  const int n_poses = (int)f->pose_off.size() - 1;
+  if (slot_sel && n_sel != n_poses)
+    return octl_set_error(ctx, OCTL_E_INVALID, "slot selection has %d entries for %d poses", n_sel, n_poses);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint8_t> sel;
+  if (slot_sel) sel.assign(slot_sel, slot_sel + n_poses);
+  // (a fill behind a size query finds the table the query made: the same selection on an unchanged forest)
+  if (!(f->pooled_valid && f->pl_sel == sel)) OCTL_TRY(pooled_compute(f, sel));
+  *n_leaves = f->pl_n;
+  const int64_t n = f->pl_n;
+  if (n <= 0 || cap < n) return OCTL_OK;
+  hipStream_t st = ctx->stream;
+  const PoolLayout lay(f->pl_cap);
+  const char* rb = static_cast<const char*>(f->pl_rows.p);
+  bool any = false;
+  auto down = [&](void* dst, size_t off, size_t bytes) -> hipError_t {
+    if (!dst) return hipSuccess;
+    any = true;
+    return hipMemcpyAsync(dst, rb + off, bytes, hipMemcpyDeviceToHost, st);
+  };
+  HIP_TRY(ctx, down(node, 0, (size_t)n * 4));
+  HIP_TRY(ctx, down(count, lay.o_count, (size_t)n * 8));
+  HIP_TRY(ctx, down(mean, lay.o_mean, (size_t)n * 24));
+  HIP_TRY(ctx, down(cov6, lay.o_cov, (size_t)n * 48));
+  HIP_TRY(ctx, down(eigval, lay.o_w, (size_t)n * 24));
+  HIP_TRY(ctx, down(eigvec, lay.o_v, (size_t)n * 72));
+  if (any) HIP_TRY(ctx, hipStreamSynchronize(st));
   return OCTL_OK;
 }

@@ -224,8 +224,6 @@ __global__ void k_node_lambda(NodePtrs nd, int64_t first, int64_t n_new, int32_t
   lambda[first + j] = w[0];
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int planar_level_stats(octl_forest* f, const PlanarRule& rule, NodeTable& nt, int64_t first_new, int64_t n_new,

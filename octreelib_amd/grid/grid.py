@@ -18,6 +18,7 @@ from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, VisualizationConfig
 from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
+from octreelib_amd.query import HostMap, LeafPlanes, PointToPlane
 
 __all__ = ["Grid", "GridConfig"]
 
@@ -101,6 +102,53 @@ class Grid(GridBase):
         slot = self._slots[pose_number]
         self._forest.ensure_built()
         return self._forest.leaf_stats(self._forest.slot_blocks(slot))
+
+    # -- queries: no reference counterpart (octreelib_amd/query.py holds the host definitions) ----------------------
+    def _host_map(self) -> HostMap:
+        plug = self._plug
+        keys = sorted(plug._managers)
+        roots = [(np.array(k, dtype=np.float64), float(plug._L)) for k in keys]
+        leaves = {p: plug.get_leaf_points(p, False) for p in plug._pose_voxels}
+        return HostMap(0, float(plug._L), roots, leaves)
+
+    def _query_slots(self, pose_numbers):
+        if self._plug is not None:
+            for p in pose_numbers or ():
+                self._plug._pose_voxels[p]   # KeyError for an unknown pose
+            return pose_numbers
+        return None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+
+    def locate(self, points) -> np.ndarray:
+        """int32 node id of the scheme leaf that every query point falls into - the leaf a point inserted as a late
+        pose would land in; LeafView.node of get_leaf_points is the id to match against - or -1: no top-level voxel
+        there, outside the voxel domain, not finite.  Read-only, one kernel.  Any (n, 3) array-like."""
+        if self._plug is not None:
+            return self._host_map().locate(points)
+        return self._forest.locate(points)
+
+    def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
+        """One least-squares plane per leaf over the given poses (None: all), all their points pooled: a LeafPlanes in
+        ascending node id.  KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().leaf_planes(sel)
+        return self._forest.leaf_planes(sel)
+
+    def point_to_plane(self, points, pose_numbers: Optional[List[int]] = None, min_points: int = 8,
+                       max_variance: Optional[float] = None) -> PointToPlane:
+        """Leaf, plane row and signed distance to the pooled plane of its own leaf for every query point; row -1 and
+        distance NaN where the point has no leaf or the leaf no accepted plane (fewer than min_points pooled points,
+        smallest eigenvalue above max_variance).  One fused kernel; the pooled planes are recomputed only when the
+        grid has changed or the pose selection is another one."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().point_to_plane(points, sel, min_points, max_variance)
+        return self._forest.point_to_plane(points, sel, min_points, max_variance)
+
+    def node_cubes(self):
+        """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""
+        nd = self._host_map().nodes if self._plug is not None else self._forest.nodes
+        return nd["corner"].copy(), nd["edge"].copy()
 
     # grid.py:234-242: all managers in first-creation order, DFS order inside a manager
     def get_points(self, pose_number: int):

@@ -91,6 +91,33 @@ class Octree(OctreeBase, Generic[T]):
         self._forest.ensure_built()
         return self._forest.leaf_stats(self._forest.slot_blocks(self._slot))
 
+    # -- queries: no reference counterpart (octreelib_amd/query.py holds the host definitions) ------------------
+    def _query_ready(self):
+        if self._slot is None:
+            self._slot = self._forest.add_pose(np.empty((0, 3)))
+
+    def locate(self, points) -> np.ndarray:
+        """int32 node id of the leaf every query point falls into (LeafView.node), -1 outside the cube or for a
+        point that is not finite.  Read-only, one kernel."""
+        self._query_ready()
+        return self._forest.locate(points)
+
+    def leaf_planes(self):
+        """One least-squares plane per non-empty leaf, in ascending node id (a LeafPlanes)."""
+        self._query_ready()
+        return self._forest.leaf_planes(None)
+
+    def point_to_plane(self, points, min_points: int = 8, max_variance=None):
+        """Leaf, plane row and signed distance to the plane of its own leaf for every query point."""
+        self._query_ready()
+        return self._forest.point_to_plane(points, None, min_points, max_variance)
+
+    def node_cubes(self):
+        """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""
+        self._query_ready()
+        nd = self._forest.nodes
+        return nd["corner"].copy(), nd["edge"].copy()
+
     @property
     def n_points(self):
         return 0 if self._slot is None else self._forest.n_points(self._slot)

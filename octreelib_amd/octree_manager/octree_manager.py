@@ -14,6 +14,7 @@ from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.internal.voxel import Voxel, VoxelBase
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase
+from octreelib_amd.query import HostMap, LeafPlanes, PointToPlane
 
 __all__ = ["OctreeManager"]
 
@@ -106,6 +107,47 @@ class OctreeManager(VoxelBase):
         slot = self._slots[pose_number]
         self._forest.ensure_built()
         return self._forest.leaf_stats(self._forest.slot_blocks(slot))
+
+    # -- queries: no reference counterpart (octreelib_amd/query.py holds the host definitions) ----------------------
+    def _host_map(self) -> HostMap:
+        roots = [(np.asarray(self.corner_min, dtype=np.float64), float(self.edge_length))]
+        leaves = {p: self._plug.get_leaf_points(False, p) for p in self._plug.octrees}
+        return HostMap(1, float(self.edge_length), roots, leaves)
+
+    def _query_slots(self, pose_numbers):
+        if self._plug is not None:
+            for p in pose_numbers or ():
+                self._plug.octrees[p]   # KeyError for an unknown pose
+            return pose_numbers
+        return None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+
+    def locate(self, points) -> np.ndarray:
+        """int32 node id of the scheme leaf every query point falls into (LeafView.node), -1 outside the cube or
+        for a point that is not finite.  Read-only, one kernel."""
+        if self._plug is not None:
+            return self._host_map().locate(points)
+        return self._forest.locate(points)
+
+    def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
+        """One least-squares plane per leaf over the given poses (None: all), their points pooled; ascending node id.
+        KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().leaf_planes(sel)
+        return self._forest.leaf_planes(sel)
+
+    def point_to_plane(self, points, pose_numbers: Optional[List[int]] = None, min_points: int = 8,
+                       max_variance: Optional[float] = None) -> PointToPlane:
+        """Leaf, plane row and signed distance to the pooled plane of its own leaf for every query point."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().point_to_plane(points, sel, min_points, max_variance)
+        return self._forest.point_to_plane(points, sel, min_points, max_variance)
+
+    def node_cubes(self):
+        """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""
+        nd = self._host_map().nodes if self._plug is not None else self._forest.nodes
+        return nd["corner"].copy(), nd["edge"].copy()
 
     def get_points(self, pose_number: Optional[int] = None):
         if self._plug is not None:
