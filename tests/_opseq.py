@@ -1,0 +1,752 @@
+"""
+Seeded random operation sequences over the whole API, drawn with the oracle in the loop (no GPU needed).
+
+generate(seed) returns a Sequence: the LOG - a list of plain dicts that fully determines the sequence (clouds by
+generator parameters, RANSAC tables by their np.random.seed, criteria by their parameters, map functions by name) -
+and, per step, the oracle-side expected observation (per pose: leaf table in list order with an order-independent
+64-bit digest of every leaf's rows, and the counters) plus what the model knows about the library's own state (is
+the pooled plane table of the device still valid, what split_stats must show).  Model.replay(container, log) builds a
+fresh model from a log; this is how a model is forked (the oracle's trees cannot be deep-copied).
+
+The container, the first subdivision kind and one "motif" (a transition that must occur with nothing mutating in
+between) are fixed by the seed's number so that the seed set covers them; everything else is drawn.
+
+Domain guard (INTEGRATION.md "Limits of the parity domain").  Preconditions that follow from the
+container and the state alone decide which kinds can be drawn at all (an Octree has no poses, RANSAC needs pose
+numbers 0..n-1, nothing re-keys points after rows were displaced, ...).  A drawn operation is then applied to the
+model and REJECTED - the model is rebuilt by replaying the log, the draw is counted - when
+  * a re-subdivide is not equal-or-finer (an internal node of the old scheme is a leaf of the new one),
+  * a NotPlanar rule evaluated a node within 1e-9 e^2 of its threshold (tests/_util._oracle_nodes),
+  * points are no longer distinct within a pose or across the poses that drive a scheme,
+  * an in-place transforming map moved a row out of its leaf's cube.
+An opaque filter that empties nothing stays in: the library evaluates it on the host and then makes no device call, so
+the pooled plane table stays valid, which the model books (a point-count filter always runs on the device and always
+invalidates it).
+K of a count-driven re-subdivide is drawn below the smallest count the scheme poses have in any internal node of the
+current scheme, which makes it equal-or-finer by construction.
+Not drawn at all: map functions that reorder a leaf's own rows (the library keeps insertion order for a selection
+of a leaf's rows, the reference the returned order - visible to a later RANSAC), a displacing map anywhere but as
+the last mutating operation.
+"""
+
+import functools
+
+import numpy as np
+
+from octreelib_amd.criteria import MaxPoints, NotPlanar
+from oracle import octree_np as onp
+from oracle import ransac_np as rnp
+from tests._util import _longdouble_lambda, _oracle_nodes, _scheme_nodes
+from tests.test_gpu_fuzz import _cloud
+
+SEEDS = list(range(24))
+UTM = np.array([5.0e6, 4.0e5, 100.0])
+MANAGER_POSES = [7, 2, 5, 0, 9, 4]
+MUTATING = ("insert", "extend", "subdivide_count", "subdivide_planar_count", "subdivide_planar", "subdivide_callable",
+            "filter_count", "filter_opaque", "filter_subset", "map_select", "map_transform", "apply_mask", "ransac")
+READ_ONLY = ("leaf_statistics", "locate", "leaf_planes", "point_to_plane", "node_cubes", "get_leaf_points",
+             "counters", "split_stats")
+SUBDIVIDES = ("subdivide_count", "subdivide_planar_count", "subdivide_planar", "subdivide_callable")
+FILTERS = ("filter_count", "filter_opaque", "filter_subset")
+TRANSITIONS = ("ransac>leaf_planes", "ransac>subdivide", "ransac>insert", "filter>insert", "filter>point_to_plane",
+               "map_transform>subdivide", "map_select>ransac", "leaf_planes(S)>insert>point_to_plane(S)",
+               "planar>count>split_stats", "extend>leaf_statistics", "point_to_plane>ransac>point_to_plane",
+               "two_ransac")
+# container and motif (index into TRANSITIONS) by seed % 12; the second entry is for seeds >= 12
+_CONTAINER = {0: "grid", 1: "grid", 2: "grid", 3: "manager", 4: ("octree", "octree"), 5: ("octree", "grid"), 6: "grid",
+              7: "manager", 8: ("grid", "manager"), 9: ("manager", "octree"), 10: "grid", 11: "grid"}
+_MOTIF = {0: ["ransac", "leaf_planes"], 1: ["ransac", "subdivide_count"], 2: ["ransac", "insert"],
+          3: ["filter_count", "insert"], 4: ["filter_opaque", "point_to_plane"],
+          5: ["map_transform", "subdivide_count"], 6: ["map_select", "ransac"],
+          7: ["leaf_planes", "insert", "point_to_plane"],
+          8: ["subdivide_planar_count", "subdivide_count", "split_stats"], 9: ["extend", "leaf_statistics"],
+          10: ["point_to_plane", "ransac", "point_to_plane"], 11: ["ransac", "get_leaf_points", "ransac"]}
+
+
+def cloud_edge(container):
+    """The length the clouds of a container are scaled by: they span [-2, 2) of it."""
+    return container["edge"] if container["kind"] == "grid" else container["edge"] / 4.0
+
+
+class Rejected(Exception):
+    """The drawn operation leaves the parity domain."""
+
+
+# ---- clouds, criteria, functions: everything a log record names ---------------------------------------------------
+def make_cloud(c):
+    """The cloud of a record {"seed", "n", "edge", "utm", "form"} in the form the library is given; the model
+    receives model_cloud() of it."""
+    rng = np.random.default_rng([c["seed"], 0xC10D])
+    pts = _cloud(rng, c["n"], c["edge"], planar=True)
+    if c.get("cube"):    # one cube with a negative corner: p - corner must not round up to the cube's edge
+        pts = np.minimum(pts, 2.0 * c["edge"] * (1.0 - 2.0 ** -20))
+    if c["utm"]:
+        pts = np.unique(pts + UTM, axis=0)
+        rng.shuffle(pts)
+    if c["form"] == "f32":
+        hi = np.float32(2.0 * c["edge"] * (1.0 - 2.0 ** -20))
+        p32 = np.minimum(pts.astype(np.float32), hi)
+        _, first = np.unique(p32, axis=0, return_index=True)
+        return np.ascontiguousarray(p32[np.sort(first)])
+    if c["form"] == "fortran":
+        return np.asfortranarray(pts)
+    if c["form"] == "strided":
+        big = np.zeros((2 * len(pts), 4))
+        big[::2, :3] = pts
+        return big[::2, :3]
+    return pts
+
+
+def model_cloud(c):
+    return np.ascontiguousarray(make_cloud(c), dtype=np.float64)
+
+
+def _spread(points):
+    return float((points.max(axis=0) - points.min(axis=0)).max()) if len(points) else 0.0
+
+
+def build_criteria(spec):
+    """Subdivision criteria of a record: [["MaxPoints", K] | ["NotPlanar", mv, min_points, ddof] |
+    ["big_and_wide", n, w]] (the last one is opaque to the library's recogniser: the host level loop)."""
+    out = []
+    for s in spec:
+        if s[0] == "MaxPoints":
+            out.append(MaxPoints(s[1]))
+        elif s[0] == "NotPlanar":
+            out.append(NotPlanar(s[1], s[2], s[3]))
+        else:
+            out.append((lambda n, w: (lambda points: len(points) > n and _spread(points) > w))(s[1], s[2]))
+    return out
+
+
+def build_filter(spec):
+    """Filter criteria: ["ge", c] / ["lt", c] / ["between", lo, hi] are point-count comparisons the library
+    recognises; ["spread_lt", w] is opaque."""
+    if spec[0] == "ge":
+        c = spec[1]
+        return [lambda pts: len(pts) >= c]
+    if spec[0] == "lt":
+        c = spec[1]
+        return [lambda pts: len(pts) < c]
+    if spec[0] == "between":
+        lo, hi = spec[1], spec[2]
+        return [lambda pts: len(pts) >= lo, lambda pts: hi >= len(pts)]
+    w = spec[1]
+    return [lambda pts: _spread(pts) < w]
+
+
+def build_map(name, edge):
+    if name == "every_other":
+        return lambda pts: pts[::2]
+    if name == "first_half":
+        return lambda pts: pts[: (len(pts) + 1) // 2]
+    if name == "upper_z":
+        return lambda pts: pts[pts[:, 2] >= np.median(pts[:, 2])]
+    if name == "toward_mean":       # stays inside the leaf's cube (checked on the model)
+        return lambda pts: pts + 0.25 * (pts.mean(axis=0) - pts)
+    if name == "shift_z":           # rows leave their cubes: only as the last mutating operation
+        return lambda pts: pts + np.array([0.0, 0.0, 0.4 * edge]) if len(pts) % 2 else pts
+    raise KeyError(name)
+
+
+def _mix(x):
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def leaf_digests(rows, sizes):
+    """Per leaf (n, sum, xor) of a 64-bit hash of every row's bits (-0.0 folded into +0.0): equal exactly when the
+    leaves hold the same multisets of rows (up to a 2^-64 collision), whatever the order inside a leaf."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    if len(sizes) == 0:
+        return []
+    u = (np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 3) + 0.0).view(np.uint64)
+    with np.errstate(over="ignore"):
+        h = _mix(u[:, 0] + np.uint64(0x9E3779B97F4A7C15))
+        h = _mix(h ^ u[:, 1])
+        h = _mix(h ^ u[:, 2])
+        starts = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+        s = np.add.reduceat(h, starts)
+    x = np.bitwise_xor.reduceat(h, starts)
+    return [(int(n), int(a), int(b)) for n, a, b in zip(sizes.tolist(), s.tolist(), x.tolist())]
+
+
+# ---- the model ---------------------------------------------------------------------------------------------------------
+class Model:
+    """The oracle behind one container: OGrid / OManager / OTree, with the bookkeeping the library keeps on its own
+    (validity of the pooled table at the C ABI, what split_stats shows)."""
+
+    def __init__(self, container):
+        self.c = container
+        kind = container["kind"]
+        if kind == "grid":
+            self.o = onp.OGrid(container["edge"])
+        elif kind == "manager":
+            self.o = onp.OManager(np.array(container["corner"], dtype=np.float64), float(container["edge"]))
+        else:
+            self.o = onp.OTree(np.array(container["corner"], dtype=np.float64), np.float64(container["edge"]))
+        self.kind = kind
+        self.poses = []
+        self.displaced = False
+        self.pooled = False          # the device holds a valid pooled table
+        self.pooled_key = None
+        self.stats = "none"          # "none" | "nan" | record of the last planar build
+        self.stats_fresh = False     # nothing has mutated since that build
+        self.untouched = False
+        self.n_ransac = 0
+        self.closest = np.inf        # NotPlanar margin over every node a rule evaluated, in e^2
+        self.flags = {"depth2": False, "emptied": False, "late100": False}
+
+    @classmethod
+    def replay(cls, container, log):
+        m = cls(container)
+        for op in log:
+            m.apply(op)
+        return m
+
+    # -- structure ----------------------------------------------------------------------------------------------------
+    def trees_of(self, p):
+        if self.kind == "grid":
+            return [self.o.managers[k].octrees[p] for k in self.o.pose_voxels[p]]
+        if self.kind == "manager":
+            return [self.o.octrees[p]]
+        return [self.o]
+
+    def scheme_trees(self):
+        if self.kind == "grid":
+            return [m.scheme for m in self.o.managers.values()]
+        return [self.o.scheme] if self.kind == "manager" else [self.o]
+
+    def managers(self):
+        return list(self.o.managers.values()) if self.kind == "grid" else [self.o]
+
+    def counters(self, p):
+        if self.kind == "octree":
+            return [self.o.n_nodes, self.o.n_leaves, self.o.n_points]
+        return [self.o.n_nodes(p), self.o.n_leaves(p), self.o.n_points(p)]
+
+    def leaf_rows(self, p, non_empty=True):
+        return [(np.asarray(v.corner, dtype=np.float64), float(v.edge), t.points[v.idx])
+                for t in self.trees_of(p) for v in t.leaves(non_empty)]
+
+    def pose_rows(self, p):
+        parts = [r for _, _, r in self.leaf_rows(p)]
+        return np.vstack(parts) if parts else np.empty((0, 3))
+
+    def observe(self):
+        out = {}
+        for p in self.poses:
+            leaves = self.leaf_rows(p)
+            dig = leaf_digests(np.vstack([r for _, _, r in leaves]) if leaves else np.empty((0, 3)),
+                               [len(r) for _, _, r in leaves])
+            out[p] = ([(((c + 0.0).tobytes(), np.float64(e).tobytes()), d) for (c, e, _), d in zip(leaves, dig)],
+                      self.counters(p))
+        return out
+
+    def internal_nodes(self, poses=None):
+        """{(corner bytes, edge): points of the given poses (None: all) below the node} of every internal node."""
+        out = {}
+
+        def walk(node, tree, acc):
+            if node.children is None:
+                return len(node.idx) if acc else 0
+            n = sum(walk(ch, tree, acc) for ch in node.children)
+            key = ((np.asarray(node.corner, dtype=np.float64) + 0.0).tobytes(), float(node.edge))
+            out[key] = out.get(key, 0) + n
+            return n
+
+        if self.kind == "octree":
+            walk(self.o.root, self.o, True)
+            return out
+        for m in self.managers():
+            if m.scheme.root.children is None:
+                continue
+            walk(m.scheme.root, m.scheme, False)      # (every internal node, also where no pose has points)
+            for p, t in m.octrees.items():
+                if poses is None or p in poses:
+                    walk(t.root, t, True)
+        return out
+
+    def n_leaves_total(self):
+        return sum(len(t.cached) for t in self.scheme_trees())
+
+    def max_depth(self):
+        e0 = float(self.c["edge"])
+        return max((int(round(np.log2(e0 / float(v.edge)))) for t in self.scheme_trees() for v in t.cached.values()),
+                   default=0)
+
+    # -- checks ---------------------------------------------------------------------------------------------------------
+    def _distinct(self, poses):
+        rows = [self.pose_rows(p) for p in poses]
+        rows = np.vstack(rows) if rows else np.empty((0, 3))
+        if len(np.unique(rows, axis=0)) != len(rows):
+            raise Rejected("points are not distinct")
+
+    def _planar_record(self, plane, K, trees=None):
+        """_oracle_nodes on the fresh scheme trees: the margin condition, and what split_stats must show."""
+        trees = self.scheme_trees() if trees is None else trees
+        try:
+            nodes, _ = _oracle_nodes(trees, plane, K)
+        except AssertionError as e:
+            if "scene unusable" in str(e):
+                raise Rejected(str(e))
+            raise
+        rec = {}
+        allrows = None
+        if self.kind != "octree":
+            allrows = {}
+            for m in self.managers():
+                rows = [t.points[t.get_idx()] for t in m.octrees.values()]
+                _, lst = _scheme_nodes(m.scheme, np.vstack(rows))
+                for c, e, _, idx in lst:
+                    allrows[((c + 0.0).tobytes(), e)] = len(idx)
+        for k, (e, n, lam, internal, rows) in nodes.items():
+            ref = _longdouble_lambda(rows, plane.ddof)[0] if n >= plane.min_points else np.nan
+            if n >= plane.min_points:
+                self.closest = min(self.closest, abs(lam - plane.max_variance) / (e * e))
+            rec[k] = (e, n, ref, bool(internal), n if allrows is None else allrows[k])
+        return rec
+
+    # -- operations -------------------------------------------------------------------------------------------------------
+    def apply(self, op):
+        kind = op["op"]
+        if kind in MUTATING:
+            self.untouched = False
+            getattr(self, "_" + kind.split("_")[0])(op)
+            if not self.untouched:
+                self.pooled = False
+                self.pooled_key = None
+            if kind not in ("subdivide_planar", "subdivide_planar_count"):
+                self.stats_fresh = False
+            if self.max_depth() >= 2:
+                self.flags["depth2"] = True
+        elif kind in ("leaf_planes", "point_to_plane"):
+            self.pooled = True
+            self.pooled_key = None if op["poses"] is None else tuple(sorted(op["poses"]))
+
+    def _insert(self, op):
+        p, pts = op["pose"], model_cloud(op["cloud"])
+        late = self.n_leaves_total()
+        if self.kind == "octree":
+            self.o.insert_points(pts)
+        else:
+            self.o.insert_points(p, pts)
+        self.poses.append(p)
+        self._distinct([p])
+        if late >= 100:
+            self.flags["late100"] = True
+
+    def _extend(self, op):
+        p, pts = op["pose"], model_cloud(op["cloud"])
+        late = self.n_leaves_total()
+        if self.kind == "octree":
+            self.o.insert_points(pts)
+        else:
+            self.o.insert_points(p, pts)
+        self._distinct([p])
+        if late >= 100:
+            self.flags["late100"] = True
+
+    def _subdivide(self, op):
+        spec, poses = op["crit"], op["poses"]
+        self._distinct(self.poses if poses is None else poses)
+        before = set(self.internal_nodes())
+        crit = spec[0][1] if len(spec) == 1 and spec[0][0] == "MaxPoints" else build_criteria(spec)
+        plane = next((c for c in (crit if isinstance(crit, list) else []) if isinstance(c, NotPlanar)), None)
+        K = min((s[1] for s in spec if s[0] == "MaxPoints"), default=-1)
+        if self.kind == "octree":
+            if plane is not None:      # dry run on the tree's current rows: the margin must hold before the model moves
+                dry = onp.OTree(self.o.corner, self.o.edge)
+                dry.insert_points(self.o.get_points())
+                dry.subdivide(crit)
+                rec = self._planar_record(plane, K, [dry])
+            self.o.subdivide(crit)
+        else:
+            self.o.subdivide(crit, poses)
+            if plane is not None:
+                rec = self._planar_record(plane, K)
+        if not before <= set(self.internal_nodes()):
+            raise Rejected("the new scheme is not equal-or-finer")
+        self.stats = rec if plane is not None else "nan"
+        self.stats_fresh = plane is not None
+
+    def _filter(self, op):
+        crit = build_filter(op["crit"])
+        before = sum(self.counters(p)[1] for p in self.poses)
+        if self.kind == "grid":
+            self.o.filter(crit)
+        elif self.kind == "manager":
+            self.o.filter(crit, op.get("poses"))
+        else:
+            self.o.filter(crit)
+        after = sum(self.counters(p)[1] for p in self.poses)
+        if after < before:
+            self.flags["emptied"] = True
+        elif op["op"] == "filter_opaque":
+            self.untouched = True      # (evaluated on the host, nothing to remove: the library makes no device call)
+
+    def _map(self, op):
+        fn = build_map(op["fn"], cloud_edge(self.c))
+        if self.kind == "octree":
+            self.o.map_leaf_points(fn)
+        else:
+            self.o.map_leaf_points(fn, op["poses"])
+        if op["fn"] == "shift_z":
+            self.displaced = True
+            return
+        if op["op"] == "map_transform":
+            for p in self.poses:
+                for c, e, rows in self.leaf_rows(p):
+                    if len(rows) and not np.all((rows - c) // e == 0):
+                        raise Rejected("a row left its leaf's cube")
+                self._distinct([p])
+
+    def _apply(self, op):
+        p = op["pose"]
+        tree = self.trees_of(p)[0]
+        before = tree.n_leaves
+        mask = np.random.default_rng([op["seed"], 0x3A5C]).random(tree.n_points) < op["keep"]
+        tree.apply_mask(mask)
+        if tree.n_leaves < before:
+            self.flags["emptied"] = True
+
+    def _ransac(self, op):
+        np.random.seed(op["np_seed"])
+        table = np.random.random((op["H"], 6))
+        n = len(self.poses)
+        before = sum(self.counters(p)[1] for p in self.poses)
+        for i in range(0, n, op["ppb"]):
+            batch = list(range(i, min(i + op["ppb"], n)))
+            clouds, sizes = [], []
+            for p in batch:
+                for _, _, rows in self.leaf_rows(p):
+                    clouds.append(rows)
+                    sizes.append(len(rows))
+            if not clouds:
+                continue
+            mask = rnp.evaluate(np.vstack(clouds), np.array(sizes, dtype=np.int32), table, op["thr"])
+            off = 0
+            for p in batch:
+                m = self.o.n_points(p)
+                self.o.apply_mask(p, mask[off: off + m])
+                off += m
+        self.n_ransac += 1
+        if sum(self.counters(p)[1] for p in self.poses) < before:
+            self.flags["emptied"] = True
+
+
+# ---- the generator ---------------------------------------------------------------------------------------------------
+class Sequence:
+    def __init__(self, seed, container, log, obs, meta, draws, rejected, flags, closest):
+        self.seed, self.container, self.log, self.obs, self.meta = seed, container, log, obs, meta
+        self.draws, self.rejected, self.flags, self.closest = draws, rejected, flags, closest
+
+    def printed(self, upto=None):
+        ops = self.log if upto is None else self.log[: upto + 1]
+        return "\n".join([f"seed {self.seed} container {self.container}"] + [f"  {i:2d} {op}" for i, op in enumerate(ops)])
+
+
+def _container(seed, rng):
+    c = _CONTAINER[seed % 12]
+    kind = c if isinstance(c, str) else c[seed // 12 % 2]
+    if kind == "grid":
+        utm = seed % 12 in (2, 10)
+        return {"kind": "grid", "edge": 1 if utm else int(rng.choice([1, 2, 5])), "utm": utm}
+    s = int(rng.choice([1, 2]))
+    return {"kind": kind, "corner": [-2.0 * s] * 3, "edge": 4.0 * s, "utm": False}
+
+
+class _Generator:
+    def __init__(self, seed):
+        self.seed = seed
+        self.rng = np.random.default_rng([seed, 0x0B5E9])
+        self.container = _container(seed, self.rng)
+        self.kind = self.container["kind"]
+        self.model = Model(self.container)
+        self.log, self.obs, self.meta = [], [], []
+        self.draws = self.rejected = 0
+        self.cloud_seed = 1000 * seed
+        self.cloud_edge = cloud_edge(self.container)
+        self.f32 = seed % 3 == 0 and not self.container["utm"] or seed % 12 in (4, 7)
+        self.pose_order = ([1, 0, 2, 3, 4, 5] if seed % 4 == 1 else list(range(6))) if self.kind == "grid" \
+            else MANAGER_POSES
+        self.max_poses = 1 if self.kind == "octree" else int(self.rng.integers(4, 6))   # (a motif may add the sixth)
+        self.in_motif = False
+        self.shallow = seed % 12 in (1, 5)
+        self.first_subdivide = "subdivide_count" if self.shallow else SUBDIVIDES[seed % 4]
+
+    # -- parameters of one operation of a kind, or None when its precondition does not hold ---------------------------
+    def _cloud_record(self, small=False):
+        self.cloud_seed += 1
+        form = "f64"
+        r = self.rng.random()
+        if self.f32 and r < 0.6:
+            form = "f32"
+        elif r > 0.8:
+            form = "fortran" if r > 0.9 else "strided"
+        n = int(self.rng.integers(2000, 4000 if small else 9000))
+        return {"seed": self.cloud_seed, "n": n, "edge": self.cloud_edge, "utm": self.container["utm"], "form": form,
+                "cube": self.kind != "grid"}
+
+    def _subset(self, always=False):
+        poses = self.model.poses
+        if self.kind == "octree" or len(poses) < 2 or (not always and self.rng.random() < 0.5):
+            return None
+        k = int(self.rng.integers(1, len(poses)))
+        return sorted(int(p) for p in self.rng.choice(poses, k, replace=False))
+
+    def _count_k(self, poses):
+        """K of a count rule that is equal-or-finer than the current scheme, None when there is none >= 4."""
+        nodes = self.model.internal_nodes(poses)
+        if not nodes:
+            if self.shallow:      # few, dense internal nodes: a re-subdivide stays possible after points have left
+                return int(self.rng.integers(200, 250))
+            return int(self.rng.integers(30, 250)) if self.kind == "grid" else int(self.rng.integers(16, 48))
+        cmin = min(nodes.values())
+        if cmin < 3:
+            return None
+        return int(self.rng.integers(max(2, cmin // 2), cmin))
+
+    def params(self, kind):
+        m, rng = self.model, self.rng
+        has_points = bool(m.poses) and any(m.counters(p)[2] > 0 for p in m.poses)
+        split = bool(m.internal_nodes())
+        if kind == "insert":
+            if len(m.poses) >= (self.max_poses if not self.in_motif else 1 if self.kind == "octree" else 6):
+                return None
+            return {"op": kind, "pose": self.pose_order[len(m.poses)], "cloud": self._cloud_record()}
+        if kind == "extend":
+            if self.kind == "grid" or not m.poses or m.displaced:
+                return None
+            return {"op": kind, "pose": int(rng.choice(m.poses)), "cloud": self._cloud_record(small=True)}
+        if kind in SUBDIVIDES:
+            if not has_points or m.displaced or (self.kind == "octree" and split):
+                return None
+            if not split and kind != self.first_subdivide and self.first_subdivide is not None:
+                kind = self.first_subdivide
+            poses = self._subset()
+            e2 = float(self.cloud_edge) ** 2
+            plane = ["NotPlanar", float(rng.choice([2.5e-4, 1.0e-3])) * e2, int(rng.choice([8, 16])), int(rng.integers(0, 2))]
+            if kind == "subdivide_planar":
+                if split:
+                    return None
+                return {"op": kind, "crit": [plane], "poses": poses}
+            if kind == "subdivide_callable":
+                if split:
+                    k = self._count_k(poses)
+                    crit = None if k is None else [["big_and_wide", k, 0.0]]
+                else:
+                    crit = [["big_and_wide", int(rng.integers(30, 120)), 0.05 * float(self.cloud_edge)]]
+                return None if crit is None else {"op": kind, "crit": crit, "poses": poses}
+            k = self._count_k(poses)
+            if k is None and poses is not None:
+                poses, k = None, self._count_k(None)
+            if k is None:
+                return None
+            if kind == "subdivide_planar_count":
+                return {"op": kind, "crit": [plane, ["MaxPoints", max(k, 60) if not split else k]], "poses": poses}
+            return {"op": kind, "crit": [["MaxPoints", k]], "poses": poses}
+        if kind in FILTERS:
+            if not has_points or (kind == "filter_subset" and (self.kind != "manager" or len(m.poses) < 2)):
+                return None
+            if kind == "filter_opaque":
+                sp = [_spread(r) for p in m.poses for _, _, r in m.leaf_rows(p)]
+                if len(sp) < 4:
+                    return None
+                crit = ["spread_lt", float(np.quantile(sp, float(rng.uniform(0.6, 0.9))))]
+            else:
+                crit = [["ge", int(rng.integers(3, 9))], ["lt", int(rng.integers(40, 200))],
+                        ["between", int(rng.integers(2, 6)), int(rng.integers(60, 300))]][int(rng.integers(0, 3))]
+            op = {"op": kind, "crit": crit}
+            if kind == "filter_subset":
+                op["poses"] = self._subset(always=True)
+            return op
+        if kind in ("map_select", "map_transform"):
+            if not has_points or m.displaced:
+                return None
+            fn = str(rng.choice(["every_other", "first_half", "upper_z"])) if kind == "map_select" else "toward_mean"
+            return {"op": kind, "fn": fn, "poses": self._subset()}
+        if kind == "apply_mask":
+            if self.kind == "grid" or not has_points:
+                return None
+            return {"op": kind, "pose": int(rng.choice(m.poses)), "seed": int(rng.integers(1 << 30)),
+                    "keep": float(rng.choice([0.5, 0.7, 0.9]))}
+        if kind == "ransac":
+            if self.kind != "grid" or not has_points or m.n_ransac >= 2 or sorted(m.poses) != list(range(len(m.poses))):
+                return None
+            return {"op": kind, "H": int(rng.choice([64, 256, 1024])), "thr": float(rng.choice([0.01, 0.02])),
+                    "ppb": int(rng.integers(1, 4)), "np_seed": int(rng.integers(1 << 30))}
+        # read-only
+        if not m.poses:
+            return None
+        if kind in ("leaf_statistics", "get_leaf_points"):
+            return {"op": kind, "pose": int(rng.choice(m.poses))}
+        if kind == "locate":
+            return {"op": kind, "seed": int(rng.integers(1 << 30)), "n": 300}
+        if kind == "leaf_planes":
+            return {"op": kind, "poses": self._subset()}
+        if kind == "point_to_plane":
+            return {"op": kind, "poses": self._subset(), "seed": int(rng.integers(1 << 30)), "n": 300,
+                    "min_points": int(rng.choice([1, 8, 16])),
+                    "max_variance": [None, 1e-3 * float(self.cloud_edge) ** 2][int(rng.integers(0, 2))]}
+        return {"op": kind}
+
+    # -- one step -------------------------------------------------------------------------------------------------------
+    def step(self, kind, fix=None):
+        """Draw parameters for `kind` until the model accepts them (at most 4 times); False when the kind cannot be
+        drawn in this state."""
+        for _ in range(4):
+            op = self.params(kind)
+            if op is None:
+                return False
+            if fix:
+                op.update(fix)
+            self.draws += 1
+            try:
+                self.model.apply(op)
+            except Rejected:
+                self.rejected += 1
+                flags, closest = self.model.flags, self.model.closest
+                self.model = Model.replay(self.container, self.log)
+                self.model.flags, self.model.closest = flags, min(closest, self.model.closest)
+                continue
+            self.log.append(op)
+            mutating = op["op"] in MUTATING
+            self.obs.append(self.model.observe() if mutating or not self.obs else self.obs[-1])
+            st = self.model.stats
+            self.meta.append({"mutating": mutating, "pooled": self.model.pooled,
+                              "stats": st if isinstance(st, str) or self.model.stats_fresh else "stale"})
+            return True
+        return False
+
+    def reads(self, lo, hi, avoid=()):
+        for _ in range(int(self.rng.integers(lo, hi + 1))):
+            kinds = [k for k in READ_ONLY if k not in avoid]
+            self.step(str(self.rng.choice(kinds)))
+
+    def run(self):
+        rng = self.rng
+        n0 = 1 if self.kind == "octree" else int(rng.integers(1, 4))
+        for _ in range(n0):
+            self.step("insert")
+        self.reads(0, 1)
+        motif = list(_MOTIF[self.seed % 12])
+        if self.seed % 12 == 5 and self.kind == "octree":      # (an octree subdivides once: the motif comes first)
+            self._motif(motif)
+            motif = None
+        self.step(self.first_subdivide)
+        self.first_subdivide = None
+        self.reads(1, 2)
+        if self.kind == "octree":
+            self.step("extend")
+        else:
+            self.step("insert")      # a late pose into the scheme
+        self.reads(1, 1)
+        weights = {"insert": 2, "extend": 3, "subdivide_count": 3, "subdivide_planar_count": 2, "subdivide_planar": 1,
+                   "subdivide_callable": 2, "filter_count": 5, "filter_opaque": 3, "filter_subset": 3, "map_select": 3,
+                   "map_transform": 2, "apply_mask": 8, "ransac": 2}
+        if self.kind == "manager":
+            weights.update({"filter_subset": 8, "insert": 1})
+        n_mut = int(rng.integers(3, 7))
+        at = 0 if self.shallow else int(rng.integers(0, 2))
+        for i in range(n_mut):
+            if motif is not None and i == at:
+                self._motif(motif)
+                motif = None
+                self.reads(1, 1)
+                continue
+            if len(self.log) >= (12 if self.kind == "grid" else 9) and motif is None:
+                break
+            kinds = list(weights)
+            w = np.array([weights[k] for k in kinds], dtype=float)
+            for _ in range(6):
+                if self.step(str(rng.choice(kinds, p=w / w.sum()))):
+                    break
+            self.reads(1, 2)
+        if self.kind == "grid" and self.seed % 2 == 0:
+            self.step("filter_opaque")
+        if self.kind != "manager" and self.seed % 2 == 1:
+            self.step("map_select")
+        if self.kind == "manager":
+            self.step("filter_subset")
+        if self.kind != "grid":
+            self.step("apply_mask")
+            self.reads(1, 1)
+        if not self.model.flags["emptied"]:
+            self.step("filter_count", {"crit": ["ge", 6]})
+        if self.seed % 4 == 3 and self.model.poses and not self.model.displaced and len(self.log) <= 18:
+            # rows displaced out of their cubes: the last mutating operation, only statistics and queries follow
+            self.step("map_transform", {"fn": "shift_z", "poses": None})
+            for k in ("point_to_plane", "leaf_statistics")[: 20 - len(self.log)]:
+                self.step(k)
+        return Sequence(self.seed, self.container, self.log, self.obs, self.meta, self.draws, self.rejected,
+                        self.model.flags, self.model.closest)
+
+    def _motif(self, kinds):
+        subset = None
+        self.in_motif = True
+        for k in kinds:
+            fix = None
+            if self.seed % 12 == 7 and k in ("leaf_planes", "point_to_plane"):
+                if subset is None:
+                    subset = self._subset(always=True) or [self.model.poses[0]]
+                fix = {"poses": subset}
+            ok = self.step(k, fix)
+            assert ok, f"seed {self.seed}: motif step {k} cannot be drawn\n" + \
+                "\n".join(str(o) for o in self.log)
+        self.in_motif = False
+
+
+@functools.lru_cache(maxsize=None)
+def generate(seed):
+    return _Generator(seed).run()
+
+
+# ---- what the logs must cover ------------------------------------------------------------------------------------------
+def transitions(log):
+    """The names of TRANSITIONS that occur in a log with nothing mutating in between."""
+    found = set()
+    mut = [i for i, op in enumerate(log) if op["op"] in MUTATING]
+    fam = lambda k: "subdivide" if k in SUBDIVIDES else "filter" if k in FILTERS else k
+
+    def reads_after(i):
+        out = []
+        for op in log[i + 1:]:
+            if op["op"] in MUTATING:
+                break
+            out.append(op)
+        return out
+
+    for a, i in enumerate(mut):
+        k = fam(log[i]["op"])
+        nxt = log[mut[a + 1]] if a + 1 < len(mut) else None
+        after = reads_after(i)
+        names = [op["op"] for op in after]
+        if k == "ransac" and "leaf_planes" in names:
+            found.add("ransac>leaf_planes")
+        if k == "extend" and "leaf_statistics" in names:
+            found.add("extend>leaf_statistics")
+        if k == "filter":
+            pooled = [n for n in names if n in ("leaf_planes", "point_to_plane")]
+            if pooled and pooled[0] == "point_to_plane":
+                found.add("filter>point_to_plane")
+        if nxt is not None:
+            pair = f"{k}>{fam(nxt['op'])}"
+            if pair in ("ransac>subdivide", "ransac>insert", "filter>insert", "map_transform>subdivide",
+                        "map_select>ransac"):
+                found.add(pair)
+            if log[i]["op"] in ("subdivide_planar", "subdivide_planar_count") and nxt["op"] == "subdivide_count" \
+                    and "split_stats" in [op["op"] for op in reads_after(mut[a + 1])]:
+                found.add("planar>count>split_stats")
+        if k in ("insert", "ransac"):
+            before = [op for op in log[(mut[a - 1] + 1 if a else 0): i] if op["op"] in ("leaf_planes", "point_to_plane")]
+            pooled = [op for op in after if op["op"] in ("leaf_planes", "point_to_plane")]
+            if before and pooled and pooled[0]["op"] == "point_to_plane":
+                if k == "insert" and before[-1]["poses"] is not None and before[-1]["poses"] == pooled[0]["poses"]:
+                    found.add("leaf_planes(S)>insert>point_to_plane(S)")
+                if k == "ransac" and before[-1]["op"] == "point_to_plane":
+                    found.add("point_to_plane>ransac>point_to_plane")
+    if sum(op["op"] == "ransac" for op in log) >= 2:
+        found.add("two_ransac")
+    return found

@@ -24,7 +24,8 @@ from octreelib_amd.grid import Grid, GridConfig
 from octreelib_amd.octree import Octree, OctreeConfig
 from octreelib_amd.octree_manager import OctreeManager
 from oracle import octree_np as onp
-from tests._util import assert_same_leaves, canon_from_list
+from tests._util import (_longdouble_lambda, _oracle_nodes, _scheme_nodes, assert_same_leaves,
+                         canon_from_list)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,68 +46,12 @@ def _views_table(leaves, pts):
                             for v in leaves])
 
 
-def _descend(node, points, idx, out):
-    """(corner, edge, internal, idx) of every node below `node`, with the oracle's own child arithmetic."""
-    out.append((np.asarray(node.corner, dtype=np.float64), float(node.edge), node.children is not None, idx))
-    if node.children is None:
-        return
-    d = ((points[idx] - node.corner) // (node.edge / 2)).astype(int)
-    child = 4 * d[:, 0] + 2 * d[:, 1] + d[:, 2]
-    for j, ch in enumerate(node.children):
-        _descend(ch, points, idx[child == j], out)
-
-
-def _scheme_nodes(scheme_tree, points=None):
-    pts = scheme_tree.points if points is None else points
-    out = []
-    _descend(scheme_tree.root, pts, np.arange(len(pts)), out)
-    return pts, out
-
-
-def _oracle_nodes(scheme_trees, crit, K):
-    """Every node of the oracle's scheme trees as key -> (edge, n, lambda, internal, rows), after asserting the
-    scene's condition: nothing evaluated within 1e-9 e^2 of the threshold, and the tree is what the predicate says."""
-    nodes, closest, evaluated = {}, math.inf, 0
-    for t in scheme_trees:
-        pts, lst = _scheme_nodes(t)
-        for corner, e, internal, idx in lst:
-            rows = pts[idx]
-            lam = crit.smallest_eigenvalue(rows)
-            if len(idx) >= crit.min_points:
-                evaluated += 1
-                closest = min(closest, abs(lam - crit.max_variance) / (e * e))
-            assert internal == (len(idx) > K >= 0 or (len(idx) >= crit.min_points and lam > crit.max_variance))
-            nodes[((corner + 0.0).tobytes(), e)] = (e, len(idx), lam, internal, rows)
-    assert closest > 1e-9, f"scene unusable: a statistic lies {closest:.3g} e^2 from the threshold"
-    return nodes, evaluated
-
-
 def _device_nodes(forest):
     nd = forest.nodes
     cnt, lam = forest.split_stats()
     keys = [((nd["corner"][i] + 0.0).tobytes(), float(nd["edge"][i])) for i in range(len(cnt))]
     assert len(set(keys)) == len(keys)
     return keys, cnt, lam, nd["first_child"] >= 0
-
-
-def _longdouble_lambda(rows, ddof):
-    p = np.asarray(rows, dtype=np.longdouble)
-    d = p - p.sum(axis=0) / len(p)
-    cov = np.array([[(d[:, a] * d[:, b]).sum() for b in range(3)] for a in range(3)]) / (len(p) - ddof)
-    # the smallest root of the characteristic cubic, refined in longdouble from LAPACK's f64 value
-    c = cov.astype(np.float64)
-    s = 1.0 / max(np.abs(c).max(), 1e-300)
-    lam = np.longdouble(np.linalg.eigvalsh(c * s)[0] / s)
-    a, b, cc, dd, e, f = cov[0, 0], cov[0, 1], cov[0, 2], cov[1, 1], cov[1, 2], cov[2, 2]
-    fro = np.sqrt((cov * cov).sum())
-    for _ in range(4):   # (a Newton step is taken only where it is a refinement: not across a near-double root)
-        x, y, z = a - lam, dd - lam, f - lam
-        det = x * (y * z - e * e) - b * (b * z - e * cc) + cc * (b * e - y * cc)
-        ddet = -((y * z - e * e) + (x * z - cc * cc) + (x * y - b * b))
-        if ddet == 0 or abs(det / ddet) > 16 * EPS * fro:
-            break
-        lam = lam - det / ddet
-    return float(lam), float(np.sqrt((cov * cov).sum()))
 
 
 def _check_arithmetic(forest, oracle_nodes, crit, K, all_counts=None):
