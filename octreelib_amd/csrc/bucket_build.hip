@@ -90,10 +90,13 @@ struct LinParams {
   int exact_digits;  // 0: child digits always level by level (OCTL_NO_EXACT_DIGITS, tests)
   // A single pass whose geometry was formed by geom_from_box: bucket = lin / width for ANY width <= 4096 (round 6:
   // the box is padded by a margin so that a scene drifting by a voxel keeps its geometry, and a padded box's key
-  // count is no power of two times the bucket count).  winv = fl(1 / width) and whalf = winv / 2:
-  // trunc(fma(lin, winv, whalf)) = floor((lin + 0.5) / width) = floor(lin / width) exactly for lin < 2^24 - the true
-  // value is at least 0.5 / width >= 2^-13 away from an integer, the rounding errors are below 2^-27.
-  // winv == 0: the shift form (host-formed geometries: two passes, single cubes, OCTL_SYNC_GEOM).
+  // count is no power of two times the bucket count).  winv = fl(1 / width) and whalf = winv / 2, evaluated in f64:
+  // trunc(fma(lin, winv, whalf)) = floor((lin + 0.5) / width) = floor(lin / width) exactly.  geom_from_box holds the
+  // width to <= 4096 and the buckets to <= 4096, so lin < 2^24; the exact (lin + 0.5) / width is at least
+  // 0.5 / width >= 2^-13 away from an integer, and the f64 evaluation is off by a few ulp of a value below 2^12
+  // (~2^-40): far less.
+  // winv == 0: the shift form (host-formed geometries: two passes, single cubes, OCTL_SYNC_GEOM); those never
+  // evaluate the fma.
   uint32_t width;
   double winv, whalf;
 };
@@ -179,7 +182,7 @@ __host__ __device__ inline void geom_from_box(const int32_t* tb, bool domain_err
       const uint64_t R = nx * ny * nz;
       const uint64_t Rt = (uint64_t)((int64_t)tb[3] - tb[0] + 1) * (uint64_t)((int64_t)tb[4] - tb[1] + 1) *
                           (uint64_t)((int64_t)tb[5] - tb[2] + 1);
-      // (the host sizes its tables for as many buckets, see bucket_build_impl)
+      // (the host sizes its tables for as many buckets, see plan_geometry)
       const uint64_t cap = geom_bucket_cap(ask.want);
       // keys per bucket: `target` points in a box that is full ...
       const uint64_t n = ask.n_alive > 0 ? (uint64_t)ask.n_alive : 1;
@@ -2412,52 +2415,218 @@ __global__ __launch_bounds__(256, OWN_SCAN ? 4 : BF_WAVES) void k_bucket_finish(
   }  // pieces
 }
 
-int ceil_log2_u64(uint64_t v) {
-  int b = 0;
-  while (b < 64 && ((uint64_t)1 << b) < v) ++b;
-  return b;
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+// (A/B on the headline scene, tools/ab_build.sh: 8 records per thread 0.264 ms, 16: 0.284, 4: 0.295, 12 with 3
+//  workgroups per CU: 0.329 - the kernel is latency bound at 2 waves per SIMD, 254 VGPRs with 16 records)
+#define OCTL_PT_IPT 8
+#define OCTL_PT_WGS 2
+constexpr int PT_IPT = OCTL_PT_IPT;  // (records per thread and tile of the partition kernels; -D for experiments)
+constexpr int PT_TILE = PT_THREADS * PT_IPT;
+
+int domain_error(octl_ctx* ctx) {
+  return octl_set_error(ctx, OCTL_E_DOMAIN,
+                        "a point has a non-finite coordinate or a top-level voxel index outside +-%d", OCTL_VOX_ABS_LIMIT);
+}
+// supertiles: one round of workgroups (`wgs` per CU) over the items, at most 16 tiles each
+uint32_t supertiles(octl_ctx* ctx, int64_t items, int wgs, int* tiles) {
+  *tiles = (int)std::min<int64_t>(16, std::max<int64_t>(1, ceil_div(ceil_div(items, PT_TILE), (int64_t)octl_ctx_cus(ctx) * wgs)));
+  return (uint32_t)ceil_div(items, (int64_t)*tiles * PT_TILE);
+}
+// f->bk_table: [supertile][digit] table of *elems words | the same digit-major (scanned: the buckets' starts) | tail_words
+// of the caller's (the bucket bounds of two passes, the prefix partition's flag)
+int part_table_reserve(octl_forest* f, size_t cells, size_t tail_words, size_t* elems) {
+  *elems = (cells + 1 + 15) & ~(size_t)15;
+  return devbuf_reserve(f->ctx, f->bk_table, (2 * *elems + tail_words + 16) * 4);
+}
+// the partition table's transposes + scan as ONE launch (k_table_scan), the hint's validation inside it
+bool tables_fused(const octl_ctx* ctx, uint32_t nst) { return !ctx->opt.no_fused_tables && nst <= TS_MAX_ROWS; }
+
+// One stable partition pass on one digit: histogram, table scan, scatter.
+struct PartPass {
+  const PartRec* recs = nullptr;    // the source: the records of the previous pass, or nullptr = the store
+  int64_t n = 0;                    // items of the source
+  const uint8_t* alive = nullptr;   // (store) nullptr: every stored point is alive
+  const uint8_t* scheme = nullptr;  // (store) BucketBuildArgs::scheme_dev
+  LinParams lp;
+  GeomDev* gdev = nullptr;          // the geometry record on the device, or nullptr: lp is final
+  // (store) the pass runs under a hinted geometry, finds the cloud's box on its way and validates the hint: 0 no,
+  int validate = 0;                 // 1 a single-pass hint (geom_validate_body), 2 a two-pass hint (geom_validate2_body)
+  const GeomAsk* ask = nullptr;     // what a validation is held against; nullptr: no box, no geometry to validate
+  int32_t* bad_flag = nullptr;      // (store, no hint) k_part_hist's flag word for points outside the cube, nullable
+  uint32_t nst = 0, nd = 0;         // supertiles (rows of the table, `tiles` tiles each), digits
+  int tiles = 1;
+  size_t tab_elems = 0;             // part_table_reserve
+  bool own_scan = false;            // the scatter kernel's workgroups scan the table themselves (ScatterOwnScan)
+  PartRec* out = nullptr;
+  const char *t_hist = nullptr, *t_scan = nullptr, *t_scatter = nullptr;  // KTimer labels; no t_scan: inside t_hist
+};
+
+hipError_t transpose_u32(hipStream_t st, const uint32_t* in, uint32_t R, uint32_t Cc, uint32_t* out) {
+  OCTL_LAUNCH(k_transpose_u32, dim3((Cc + 63) / 64, (R + 63) / 64), dim3(256), 0, st, in, R, Cc, out);
+  return hipGetLastError();
 }
 
-}  // namespace
-
-// Complete build of a fresh forest (no previous scheme): *done = 1 when the scheme, the leaf-ordered
-// arrays, pos_node and the block table are complete; *done = 0 when this path does not apply (the
-// caller then runs the general path; nothing it relies on has been modified).
-static int bucket_build_impl(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, int* done,
-                             std::vector<octl_forest::LevelSeg>* segs, int64_t* n_internal, int* levels,
-                             int64_t* n_voxels, int64_t* n_blocks, int64_t* pending, BucketBuildGeom* geom,
-                             bool force_sync);
-
-int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, int* done,
-                        std::vector<octl_forest::LevelSeg>* segs, int64_t* n_internal, int* levels,
-                        int64_t* n_voxels, int64_t* n_blocks, int64_t* pending, BucketBuildGeom* geom) {
-  return bucket_build_impl(f, a, nt, done, segs, n_internal, levels, n_voxels, n_blocks, pending, geom, false);
+int partition_scan(octl_forest* f, const PartPass& p, bool fused) {
+  octl_ctx* ctx = f->ctx;
+  uint32_t *table = f->bk_table.as<uint32_t>(), *table_dm = table + p.tab_elems;
+  if (fused) {
+    const unsigned g = (p.nd + TS_COLS - 1) / TS_COLS;
+    uint64_t* status = nullptr;
+    uint32_t epoch = 0;
+    OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
+    OCTL_LAUNCH(k_table_scan, dim3(g), dim3(TS_THREADS), 0, ctx->stream, table, p.nst, p.nd, table_dm, status, epoch,
+                       p.validate, p.ask ? (const int32_t*)f->bbox_dev.as<int32_t>() : (const int32_t*)nullptr,
+                       p.ask ? *p.ask : GeomAsk{0, 0, 0, 0}, p.lp, p.gdev);
+    HIP_TRY(ctx, hipGetLastError());
+  } else {
+    HIP_TRY(ctx, transpose_u32(ctx->stream, table, p.nst, p.nd, table_dm));
+    OCTL_TRY(octl_exclusive_scan_u32(ctx, table_dm, table_dm, (int64_t)p.nd * p.nst, nullptr));
+    HIP_TRY(ctx, transpose_u32(ctx->stream, table_dm, p.nd, p.nst, table));
+  }
+  return OCTL_OK;
 }
 
-static int bucket_build_impl(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, int* done,
-                             std::vector<octl_forest::LevelSeg>* segs, int64_t* n_internal, int* levels,
-                             int64_t* n_voxels, int64_t* n_blocks, int64_t* pending, BucketBuildGeom* geom,
-                             bool force_sync) {
+// *bstart / *bstride: the first record of digit d in p.out is (*bstart)[d * *bstride]
+int partition_pass(octl_forest* f, const PartPass& p, const uint32_t** bstart, uint32_t* bstride) {
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
-  *done = 0;
-  // (a rejected hint and a sparse scene make this function call itself, at most twice in a row by design: anything
-  //  deeper is a bug that would otherwise end as a stack overflow)
-  struct Depth {
-    int& d;
-    explicit Depth(int& x) : d(x) { ++d; }
-    ~Depth() { --d; }
-  };
-  static thread_local int retry_depth = 0;
-  Depth guard(retry_depth);
-  if (retry_depth > 4) return octl_set_error(ctx, OCTL_E_STATE, "bucket build: the geometry retries do not terminate");
-  const int64_t N = f->n_store, n_alive = f->n_alive;
-  // (OCTL_NO_BUCKET_BUILD: tests compare this path with the level-synchronous one)
-  if (n_alive <= 0 || !f->bbox_dev.p || ctx->opt.no_bucket_build) return OCTL_OK;
-  // a single cube (bare Octree / OctreeManager) is ONE bucket: beyond what the oversize launch takes it is the
-  // level loop's job from the start
-  if (f->mode == 1 && n_alive > 65535) return OCTL_OK;
-  const int n_poses = (int)f->pose_off.size() - 1;
+  const uint32_t nst = p.nst, nd = p.nd;
+  const bool fused = tables_fused(ctx, nst);
+  uint32_t *table = f->bk_table.as<uint32_t>(), *table_dm = table + p.tab_elems;
+  const int32_t* bbox = p.ask ? (const int32_t*)f->bbox_dev.as<int32_t>() : nullptr;
+  {
+    KTimer t(ctx, p.t_hist);
+    if (p.recs) {
+      OCTL_LAUNCH(k_part_hist_rec, dim3(nst), dim3(PH_THREADS), 0, st, (const uint4*)p.recs, p.n, p.lp,
+                         (const GeomDev*)p.gdev, nst, nd, (int64_t)p.tiles * PT_TILE, table);
+    } else {
+      const bool lone = f->edge == 1.0;
+      auto kh = p.validate ? (lone ? k_part_hist<true, true> : k_part_hist<true, false>)
+                           : (lone ? k_part_hist<false, true> : k_part_hist<false, false>);
+      OCTL_LAUNCH(kh, dim3(nst), dim3(PH_THREADS), 0, st, (const double*)f->xyz.as<double>(), p.alive, p.n, p.lp,
+                         (const GeomDev*)p.gdev, nst, nd, (int64_t)p.tiles * PT_TILE, table,
+                         p.validate ? f->bbox_dev.as<int32_t>() : p.bad_flag);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (p.validate) {
+      f->bbox_pending = false;  // (the box is on the device now, whatever becomes of the hint)
+      if (fused) {
+        // (k_table_scan validates the hint on its way)
+      } else if (p.validate == 1)
+        OCTL_LAUNCH(k_geom_validate, dim3(1), dim3(64), 0, st, bbox, *p.ask, p.lp, p.gdev);
+      else
+        OCTL_LAUNCH(k_geom_validate2, dim3(1), dim3(64), 0, st, bbox, *p.ask, p.gdev);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!p.t_scan) OCTL_TRY(partition_scan(f, p, fused));
+  }
+  if (p.t_scan && !p.own_scan) {
+    KTimer t(ctx, p.t_scan);
+    OCTL_TRY(partition_scan(f, p, fused));
+  }
+  {
+    KTimer t(ctx, p.t_scatter);
+    ScatterOwnScan own;
+    std::memset(&own, 0, sizeof(own));
+    if (p.own_scan) own = ScatterOwnScan{table_dm, p.validate, bbox, *p.ask, p.lp, p.gdev};
+    if (!p.recs) {
+      auto ks = p.own_scan ? k_part_scatter<PT_IPT, false, 8, true>
+                           : (nd <= 256u ? k_part_scatter<PT_IPT, false, 8> : k_part_scatter<PT_IPT, false, PT_BITS>);
+      OCTL_LAUNCH(ks, dim3(nst), dim3(PT_THREADS), 0, st, (const double*)f->xyz.as<double>(), p.alive, p.n, p.lp,
+                         (const GeomDev*)p.gdev, nst, nd, p.tiles, (const uint32_t*)table,
+                         (const int64_t*)f->pose_off_dev.as<int64_t>(), (int)f->pose_off.size() - 1, p.scheme, p.out, own);
+    } else {
+      auto ks = nd <= 256u ? k_part_scatter<PT_IPT, true, 8> : k_part_scatter<PT_IPT, true, PT_BITS>;
+      OCTL_LAUNCH(ks, dim3(nst), dim3(PT_THREADS), 0, st, (const double*)p.recs, (const uint8_t*)nullptr, p.n, p.lp,
+                         (const GeomDev*)p.gdev, nst, nd, p.tiles, (const uint32_t*)table, (const int64_t*)nullptr, 0,
+                         (const uint8_t*)nullptr, p.out, own);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  *bstart = table_dm;
+  *bstride = fused ? 1u : nst;   // (k_table_scan leaves the buckets' starts as a plain array)
+  return OCTL_OK;
+}
+
+// (go on | the caller runs the general path | build again, the geometry formed on the device | ... on the host)
+enum BuildVerdict { BV_GO, BV_GENERAL, BV_AGAIN_ASYNC, BV_AGAIN_HOST };
+
+// The state of one attempt.  Nothing in here outlives the attempt: what carries over to the next attempt or the next
+// build is in the forest (bbox_pending) and the context (geom_hint*, geom_sparse, had_chunks, spec_*).
+struct BucketBuild {
+  octl_forest* f;
+  octl_ctx* ctx;
+  hipStream_t st;        // ctx->stream
+  uint32_t* small;       // the scalar block
+  // the plan (plan_geometry)
+  GeomAsk ask;           // want, n_alive, target, margin
+  bool async_geom;
+  bool hinted;           // single pass: the geometry is formed on the device, the hint replaces the box pass
+  bool hinted2;          // two passes: the HOST forms the geometry from the hint's box instead of waiting for the box
+  GeomDev hint;
+  int bb[6], tb[6];      // the box of the linear keys (padded) | the true voxel box
+  uint64_t ny, nz;
+  int s, bits_a;
+  uint32_t nb, nd_a, nd_b, nst_a, nst_b;   // buckets; digits and supertiles of the first / the second pass
+  int tiles_a, tiles_b;
+  bool two_pass;
+  LinParams lp, lp_pass1;
+  // device pointers (partition, build_buckets)
+  size_t tab_elems;
+  GeomDev* gdev;
+  const PartRec* recs;
+  const uint32_t* bstart;
+  uint32_t bstride;
+  uint32_t *bk_tot, *bk_scan, *ck_tot;
+  ChunkDesc* ck_desc;
+  uint2* ck_of_bucket;
+  BkParams bp;
+  NodeParams np;
+  bool chunks_beside;    // ctx->had_chunks as this attempt found it
+  // the speculative finish and the capacities it ran under
+  bool spec_want, spec_own_scan, spec_order, spec_launched;
+  int64_t spec_node_cap, spec_vox_cap, spec_blk_cap;
+  uint32_t sm[64];       // the scalar block as the totals kernel mirrored it
+};
+int mirror_words(const BucketBuild& b) {
+  static_assert(SM_GEOM == 64, "the geometry record is read back together with the 64 scalars in front of it");
+  return (int)(64 + (b.gdev ? sizeof(GeomDev) / 4 : 0));
+}
+
+// The context's hint for its next build: *hint, and whether a build of f for `want` buckets may run under it.
+bool hint_load(const octl_ctx* ctx, const octl_forest* f, uint64_t want, GeomDev* hint) {
+  std::memcpy(hint, ctx->geom_hint, sizeof(*hint));
+  return ctx->geom_hint_valid && ctx->geom_hint_want == want && hint->lp.mode == f->mode && hint->lp.L == f->edge &&
+         hint->lp.c0x == f->corner[0] && hint->lp.c0y == f->corner[1] && hint->lp.c0z == f->corner[2] &&
+         !ctx->opt.no_geom_hint && hint->lp.exact_digits == (ctx->opt.no_exact_digits ? 0 : 1);
+}
+void hint_store(octl_ctx* ctx, const GeomDev& g, bool two_pass, uint64_t want) {
+  static_assert(sizeof(GeomDev) <= sizeof(octl_ctx::geom_hint), "hint storage");
+  std::memset(ctx->geom_hint, 0, sizeof(ctx->geom_hint));
+  std::memcpy(ctx->geom_hint, &g, sizeof(g));
+  ctx->geom_hint_valid = g.valid != 0;
+  ctx->geom_hint_two_pass = two_pass;
+  ctx->geom_hint_want = want;
+}
+// The geometry record as the totals kernel mirrored it, and what an invalid one asks of the host.
+int geom_read(octl_ctx* ctx, GeomDev* g, BuildVerdict* v) {
+  std::memcpy(g, static_cast<char*>(ctx->small_host) + SM_GEOM * 4, sizeof(*g));
+  *v = BV_GO;
+  if (g->valid) return OCTL_OK;
+  if (g->reason == GEOM_DOMAIN) return domain_error(ctx);
+  *v = g->reason == GEOM_EMPTY ? BV_GENERAL : (g->reason == GEOM_REHASH ? BV_AGAIN_ASYNC : BV_AGAIN_HOST);
+  return OCTL_OK;
+}
+
+// How many buckets, whose geometry, under which hint, in which passes.  Host arithmetic - and, for a cloud taken in
+// place without a usable hint, the box pass; for a host-formed geometry the wait for the box.
+int plan_geometry(BucketBuild& b, bool force_sync, BuildVerdict* v) {
+  octl_forest* f = b.f;
+  octl_ctx* ctx = b.ctx;
+  const int64_t n_alive = f->n_alive;
+  *v = BV_GO;
   // buckets: runs of consecutive voxel keys, sized for ~2500 points on average (~1250 in a small cloud)
   // (OCTL_BUCKET_POINTS: tests force many small buckets - and with them the two-pass partition - on small clouds)
   // (a small cloud fills few workgroups and its kernels are chains of latencies, not bytes: half the bucket shortens
@@ -2469,618 +2638,490 @@ static int bucket_build_impl(octl_forest* f, const BucketBuildArgs& a, NodeTable
   // One partition pass (want <= 4096 buckets): the key geometry is formed on the device (k_bucket_geom) and
   // the host does not wait for the bounding box; all 4096 buckets exist then, the ones behind the last
   // voxel key are empty.  (OCTL_SYNC_GEOM: tests run the host-side form on small clouds too.)
-  const bool async_geom = !force_sync && !ctx->geom_sparse && want <= (uint64_t)PT_BINS && !ctx->opt.sync_geom;
+  b.async_geom = !force_sync && !ctx->geom_sparse && want <= (uint64_t)PT_BINS && !ctx->opt.sync_geom;
   // voxels of slack around the true box in the geometry of the keys (geom_from_box): a scene that drifts by up to
   // that much per scan keeps fitting the previous scan's geometry.  OCTL_GEOM_MARGIN: 0 = the shipped margin of one
   // voxel, N > 0 = N voxels, negative = none (the tight box of rounds 2-5).  A single cube has no voxels to drift over.
   const int margin = f->mode != 0 ? 0
                                   : (ctx->opt.geom_margin == 0 ? 1 : (int)std::min<int64_t>(64, std::max<int64_t>(0, ctx->opt.geom_margin)));
-  GeomAsk ask;
-  ask.want = want;
-  ask.n_alive = n_alive;
-  ask.target = (uint32_t)target;
-  ask.margin = margin;
+  b.ask = GeomAsk{want, n_alive, (uint32_t)target, margin};
   // a cloud taken in place has not been through the box pass: with the geometry of the context's previous
   // single-pass build as a hint the histogram pass finds the box itself (k_part_hist<true>, k_geom_validate);
   // without one the box pass runs now
-  bool hinted = false;   // single pass: the geometry is formed on the device, the hint replaces the box pass
-  bool hinted2 = false;  // two passes: the HOST forms the geometry from the hint's box instead of waiting for the box
-  GeomDev hint;
   if (f->bbox_pending) {
-    std::memcpy(&hint, ctx->geom_hint, sizeof(hint));
-    const bool usable = ctx->geom_hint_valid && ctx->geom_hint_want == want && hint.lp.mode == f->mode &&
-                        hint.lp.L == f->edge && hint.lp.c0x == f->corner[0] && hint.lp.c0y == f->corner[1] &&
-                        hint.lp.c0z == f->corner[2] && !ctx->opt.no_geom_hint &&
-                        hint.lp.exact_digits == (ctx->opt.no_exact_digits ? 0 : 1);
-    hinted = async_geom && usable && !ctx->geom_hint_two_pass;
-    hinted2 = !async_geom && !force_sync && usable && ctx->geom_hint_two_pass && f->mode == 0;
-    if (!hinted && !hinted2) OCTL_TRY(store_compute_bbox(f));
+    const bool usable = hint_load(ctx, f, want, &b.hint);
+    b.hinted = b.async_geom && usable && !ctx->geom_hint_two_pass;
+    b.hinted2 = !b.async_geom && !force_sync && usable && ctx->geom_hint_two_pass && f->mode == 0;
+    if (!b.hinted && !b.hinted2) OCTL_TRY(store_compute_bbox(f));
   }
   // every stored point is alive (nothing was removed since the poses were added): the flags are not read
   if (f->n_alive != f->n_store) OCTL_TRY(alive_ensure(f));
-  const uint8_t* alive_p = f->n_alive == f->n_store ? nullptr : f->alive.as<uint8_t>();
-  int bb[6] = {0, 0, 0, 0, 0, 0};   // the box of the linear keys (padded)
-  int tb[6] = {0, 0, 0, 0, 0, 0};   // the true voxel box
-  uint64_t ny = 1, nz = 1;
-  int s = 0;
+  b.ny = b.nz = 1;
   // (single pass with the geometry formed on the device: tables and grids for geom_bucket_cap(want) buckets -
   //  geom_from_box holds the geometry to that - instead of always 4096: a 100 k-point scan has 128)
-  uint32_t nb = async_geom ? (uint32_t)geom_bucket_cap(want) : (uint32_t)PT_BINS;
-  bool two_pass = false;
-  if (!async_geom) {
-    if (hinted2) {
+  b.nb = b.async_geom ? (uint32_t)geom_bucket_cap(want) : (uint32_t)PT_BINS;
+  // The geometry formed on the host (two passes, a sparse scene, a single cube, OCTL_SYNC_GEOM): from the hint's box, or
+  // from the true one, for which the host waits.  (Every `return OCTL_OK` in here: not this path's case.)
+  if (!b.async_geom) {
+    int *bb = b.bb, *tb = b.tb;
+    *v = BV_GENERAL;
+    if (b.hinted2) {
       // the (padded) box of the context's previous two-pass build: validated on the device by the histogram pass itself
-      std::memcpy(bb, hint.bb, sizeof(bb));
-      std::memcpy(tb, hint.tb, sizeof(tb));
+      std::memcpy(bb, b.hint.bb, sizeof(b.bb));
+      std::memcpy(tb, b.hint.tb, sizeof(b.tb));
     } else {
       // ---- voxel bounding box (kept by the ingest kernel; the copy was enqueued with the last ingest) ------
       int32_t* bbox_host = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->small_host) + MIRROR_BBOX_WORD * 4);
-      HIP_TRY(ctx, hipMemcpyAsync(bbox_host, f->bbox_dev.p, 32, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx, hipStreamSynchronize(st));
-      std::memcpy(tb, bbox_host, sizeof(tb));
-      if (bbox_host[6])
-        return octl_set_error(ctx, OCTL_E_DOMAIN,
-                              "a point has a non-finite coordinate or a top-level voxel index outside +-%d",
-                              OCTL_VOX_ABS_LIMIT);
+      HIP_TRY(ctx, hipMemcpyAsync(bbox_host, f->bbox_dev.p, 32, hipMemcpyDeviceToHost, b.st));
+      HIP_TRY(ctx, hipStreamSynchronize(b.st));
+      std::memcpy(tb, bbox_host, sizeof(b.tb));
+      if (bbox_host[6]) return domain_error(ctx);
       if (tb[0] > tb[3]) return OCTL_OK;
       geom_pad_box(tb, margin, bb);
     }
     if (bb[0] > bb[3]) return OCTL_OK;
     const uint64_t nx = (uint64_t)(bb[3] - bb[0] + 1);
-    ny = (uint64_t)(bb[4] - bb[1] + 1);
-    nz = (uint64_t)(bb[5] - bb[2] + 1);
-    if (nx * ny > (1ull << 32) || nx * ny * nz >= (1ull << 32)) return OCTL_OK;  // keys would not fit 32 bits
-    const uint64_t R = nx * ny * nz;
+    b.ny = (uint64_t)(bb[4] - bb[1] + 1);
+    b.nz = (uint64_t)(bb[5] - bb[2] + 1);
+    if (nx * b.ny > (1ull << 32) || nx * b.ny * b.nz >= (1ull << 32)) return OCTL_OK;  // keys would not fit 32 bits
+    const uint64_t R = nx * b.ny * b.nz;
     // the host-formed geometry keeps buckets of 2^s keys (two passes split the bucket number's bits); s follows the
     // TRUE box - padding a 128^3 box crosses a power of two and would double every bucket (one rank's 125 M-point
     // shard: k_bucket_build 3.7 -> 4.9 ms, the chunk kernels 1.7 -> 4.4 ms) - the padded keys only add buckets
     const uint64_t Rt = (uint64_t)((int64_t)tb[3] - tb[0] + 1) * (uint64_t)((int64_t)tb[4] - tb[1] + 1) *
                         (uint64_t)((int64_t)tb[5] - tb[2] + 1);
-    s = std::min(12, std::max(0, ceil_log2_u64(Rt) - ceil_log2_u64(want)));
-    if (((R - 1) >> s) + 1 > ((uint64_t)PT_BINS << PT_BITS)) return OCTL_OK;  // a sparse scene: too many keys
-    nb = (uint32_t)(((R - 1) >> s) + 1);
-    two_pass = nb > (uint32_t)PT_BINS;
-    if (hinted2 && !two_pass)  // (cannot happen: same box, same `want`)
-      return bucket_build_impl(f, a, nt, done, segs, n_internal, levels, n_voxels, n_blocks, pending, geom, true);
+    b.s = std::min(12, std::max(0, geom_ceil_log2(Rt) - geom_ceil_log2(want)));
+    if (((R - 1) >> b.s) + 1 > ((uint64_t)PT_BINS << PT_BITS)) return OCTL_OK;  // a sparse scene: too many keys
+    b.nb = (uint32_t)(((R - 1) >> b.s) + 1);
+    b.two_pass = b.nb > (uint32_t)PT_BINS;
+    if (b.hinted2 && !b.two_pass) {  // (cannot happen: same box, same `want`)
+      *v = BV_AGAIN_HOST;
+      return OCTL_OK;
+    }
     // (a SPARSE scene - more keys per wanted bucket than the 12-bit clamp on a bucket's key range allows - makes the
     //  context skip the single-pass attempt next time; judged on the true box: the padding alone never does)
-    ctx->geom_sparse = ((Rt - 1) >> s) + 1 > (uint64_t)PT_BINS && want <= (uint64_t)PT_BINS;
+    ctx->geom_sparse = ((Rt - 1) >> b.s) + 1 > (uint64_t)PT_BINS && want <= (uint64_t)PT_BINS;
     // Thin buckets: the 12-bit clamp on a bucket's key range left them under half their target.  A workgroup per
     // bucket is mostly set-up then, and the cost grows with the BOX (10 M points in 1024 x 1024 x 64 voxels:
     // 2.46 ms, in 8192 x 8192 x 64: 37 ms), while the level loop's depends on the points alone (1.5-1.7 ms for
     // every box measured): it takes these scenes.
-    if (two_pass && (uint64_t)n_alive * 2 < (uint64_t)nb * target) return OCTL_OK;
+    if (b.two_pass && (uint64_t)f->n_alive * 2 < (uint64_t)b.nb * target) return OCTL_OK;
+    *v = BV_GO;
   }
-
-  LinParams lp;
-  lp.mode = f->mode;
-  lp.L = f->edge;
-  lp.c0x = f->corner[0];
-  lp.c0y = f->corner[1];
-  lp.c0z = f->corner[2];
-  lp.minx = bb[0];
-  lp.miny = bb[1];
-  lp.minz = bb[2];
-  lp.ny = (uint32_t)ny;
-  lp.nz = (uint32_t)nz;
-  lp.shift = s;
-  lp.dshift = s;
-  lp.dmask = 0xFFFFFFFFu;
-  lp.raw_vp = 0;
-  lp.exact_digits = ctx->opt.no_exact_digits ? 0 : 1;
-  lp.width = 1u << s;   // (host-formed geometry: the shift form; geom_from_box overwrites these on the device)
-  lp.winv = 0.0;
-  lp.whalf = 0.0;
-  uint32_t* small = ctx->small.as<uint32_t>();
-  // supertiles: one round of workgroups (2 per CU) over the cloud, at most 16 tiles each
-  const int cus = octl_ctx_cus(ctx);
-// (A/B on the headline scene, tools/ab_build.sh: 8 records per thread 0.264 ms, 16: 0.284, 4: 0.295, 12 with 3
-//  workgroups per CU: 0.329 - the kernel is latency bound at 2 waves per SIMD, 254 VGPRs with 16 records)
-#define OCTL_PT_IPT 8
-#define OCTL_PT_WGS 2
-  constexpr int PT_IPT = OCTL_PT_IPT;  // (records per thread and tile of the partition kernels; -D for experiments)
-  constexpr int tile = PT_THREADS * PT_IPT;
-  auto supertiles = [&](int64_t items, int* st_tiles) {
-    // (a pass with at most 256 digits keeps 3 KB of counters: three workgroups per CU instead of two)
-    const int wgs = two_pass ? std::max(OCTL_PT_WGS, 3) : OCTL_PT_WGS;
-    *st_tiles = (int)std::min<int64_t>(16, std::max<int64_t>(1, ceil_div(ceil_div(items, tile), (int64_t)cus * wgs)));
-    return (uint32_t)ceil_div(items, (int64_t)*st_tiles * tile);
-  };
-  int st_tiles_a = 1, st_tiles_b = 1;
-  const uint32_t nst_a = supertiles(N, &st_tiles_a);
-  const uint32_t nst_b = two_pass ? supertiles(n_alive, &st_tiles_b) : 0;
+  // (a pass with at most 256 digits keeps 3 KB of counters: three workgroups per CU instead of two)
+  const int wgs = b.two_pass ? std::max(OCTL_PT_WGS, 3) : OCTL_PT_WGS;
+  b.nst_a = supertiles(ctx, f->n_store, wgs, &b.tiles_a);
+  b.nst_b = b.two_pass ? supertiles(ctx, n_alive, wgs, &b.tiles_b) : 0;
   // Two passes split the bucket number's bits EVENLY (low half first, both passes stable): a tile of 4096
   // records then leaves runs of ~16 records (512 B) per digit in both passes.  (Round 2 took 12 bits first: one
   // record per digit and tile - isolated 32-byte stores at 2 TB/s, 0.61 ms per 10 M points at 125 M.)
-  const int bits_a = two_pass ? std::min(PT_BITS, (ceil_log2_u64(nb) + 1) / 2) : 0;
-  const uint32_t nd_a = two_pass ? (1u << bits_a) : nb;                // digits of the first pass
-  const uint32_t nd_b = two_pass ? ((nb - 1) >> bits_a) + 1 : 0;       // digits of the second pass
-  // ---- scratch ------------------------------------------------------------------------------------------------
+  b.bits_a = b.two_pass ? std::min(PT_BITS, (geom_ceil_log2(b.nb) + 1) / 2) : 0;
+  b.nd_a = b.two_pass ? (1u << b.bits_a) : b.nb;                // digits of the first pass
+  b.nd_b = b.two_pass ? ((b.nb - 1) >> b.bits_a) + 1 : 0;       // digits of the second pass
+  // the key parameters, with the digit of the first pass
+  LinParams& lp = b.lp;
+  lp.mode = f->mode, lp.L = f->edge;
+  lp.c0x = f->corner[0], lp.c0y = f->corner[1], lp.c0z = f->corner[2];
+  lp.minx = b.bb[0], lp.miny = b.bb[1], lp.minz = b.bb[2];
+  lp.ny = (uint32_t)b.ny, lp.nz = (uint32_t)b.nz;
+  lp.shift = lp.dshift = b.s;
+  lp.dmask = b.two_pass ? (b.nd_a - 1u) : 0xFFFFFFFFu, lp.raw_vp = b.two_pass ? 1 : 0;
+  lp.exact_digits = ctx->opt.no_exact_digits ? 0 : 1;
+  lp.width = 1u << b.s;   // (host-formed geometry: the shift form; geom_from_box overwrites these on the device)
+  lp.winv = lp.whalf = 0.0;
+  b.lp_pass1 = lp;
+  return OCTL_OK;
+}
+
+// Scratch, the geometry record on the device, then one or two passes into b.recs / b.bstart / b.bstride.
+// (SM_BK_FLAGS / SM_BK_TOTAL / SM_BK_TODO are zero: forest_build has reset the scalar block)
+int partition(BucketBuild& b, const BucketBuildArgs& a) {
+  octl_forest* f = b.f;
+  octl_ctx* ctx = b.ctx;
+  const int64_t n_alive = f->n_alive;
   OCTL_TRY(devbuf_reserve(ctx, f->part_xyz[0], (size_t)n_alive * sizeof(PartRec)));
-  if (two_pass) OCTL_TRY(devbuf_reserve(ctx, f->part_xyz[1], (size_t)n_alive * sizeof(PartRec)));
-  // [supertile][digit] table | the same digit-major (scanned: the buckets' starts) | bucket bounds (two passes)
-  const size_t tab_elems = (std::max((size_t)nd_a * nst_a, (size_t)nd_b * nst_b) + 1 + 15) & ~(size_t)15;
-  // the partition table's transposes + scan as ONE launch (k_table_scan), the hint's validation inside it
-  const bool fused_a = !ctx->opt.no_fused_tables && nst_a <= TS_MAX_ROWS;
-  const bool fused_b = !ctx->opt.no_fused_tables && two_pass && nst_b <= TS_MAX_ROWS;
-  OCTL_TRY(devbuf_reserve(ctx, f->bk_table, (2 * tab_elems + (two_pass ? nb + 1 : 0) + 16) * 4));
+  if (b.two_pass) OCTL_TRY(devbuf_reserve(ctx, f->part_xyz[1], (size_t)n_alive * sizeof(PartRec)));
+  // (behind the two tables: the bucket bounds of two passes)
+  OCTL_TRY(part_table_reserve(f, std::max((size_t)b.nd_a * b.nst_a, (size_t)b.nd_b * b.nst_b),
+                              b.two_pass ? b.nb + 1 : 0, &b.tab_elems));
   // per-bucket totals: raw | scanned (apart: buckets beyond 4096 points add theirs later, and the scan runs again)
-  const size_t tot_elems = (((size_t)BK_ROWS * nb + 8) + 15) & ~(size_t)15;
+  const size_t tot_elems = (((size_t)BK_ROWS * b.nb + 8) + 15) & ~(size_t)15;
   OCTL_TRY(devbuf_reserve(ctx, f->bk_tot, 2 * tot_elems * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->bk_vox, (size_t)n_alive * 12));
-  OCTL_TRY(devbuf_reserve(ctx, f->bk_node, (size_t)n_alive * 12));
-  OCTL_TRY(devbuf_reserve(ctx, f->leafinfo, (size_t)n_alive * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->ord_idx, (size_t)n_alive * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->xyz_ord, (size_t)n_alive * 24));
-  OCTL_TRY(devbuf_reserve(ctx, f->pos_node, (size_t)n_alive * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->blk_node, (size_t)n_alive * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->blk_slot, (size_t)n_alive * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->blk_start, (size_t)n_alive * 4));
-  OCTL_TRY(devbuf_reserve(ctx, f->blk_size, (size_t)n_alive * 4));
-  uint32_t* table = f->bk_table.as<uint32_t>();
-  uint32_t* table_dm = table + tab_elems;  // digit-major
-  auto transpose = [&](const uint32_t* in, uint32_t R, uint32_t Cc, uint32_t* out) {
-    OCTL_LAUNCH(k_transpose_u32, dim3((Cc + 63) / 64, (R + 63) / 64), dim3(256), 0, st, in, R, Cc, out);
-    return hipGetLastError();
-  };
-  // (SM_BK_FLAGS / SM_BK_TOTAL / SM_BK_TODO are zero: forest_build has reset the scalar block)
-  // ---- partition ----------------------------------------------------------------------------------------------
-  lp.dshift = s;
-  lp.dmask = two_pass ? (nd_a - 1u) : 0xFFFFFFFFu;
-  lp.raw_vp = two_pass ? 1 : 0;
-  const LinParams lp_pass1 = lp;
-  GeomDev* gdev = nullptr;
-  if (async_geom) {
-    gdev = reinterpret_cast<GeomDev*>(small + SM_GEOM);
-    if (hinted) {
+  const std::pair<DevBuf*, int> per_point[] = {  // (bytes per point; in this order)
+      {&f->bk_vox, 12},  {&f->bk_node, 12}, {&f->leafinfo, 4}, {&f->ord_idx, 4},   {&f->xyz_ord, 24},
+      {&f->pos_node, 4}, {&f->blk_node, 4}, {&f->blk_slot, 4}, {&f->blk_start, 4}, {&f->blk_size, 4}};
+  for (const auto& pp : per_point) OCTL_TRY(devbuf_reserve(ctx, *pp.first, (size_t)n_alive * pp.second));
+  b.bk_tot = f->bk_tot.as<uint32_t>();
+  b.bk_scan = b.bk_tot + tot_elems;
+  if (b.async_geom || b.hinted2) b.gdev = reinterpret_cast<GeomDev*>(b.small + SM_GEOM);
+  if (b.async_geom) {
+    if (b.hinted) {
       // (normally in place already: k_build_begin copied it with the scalar block)
-      if (!ctx->geom_hint_staged) OCTL_LAUNCH(k_geom_set, dim3(1), dim3(64), 0, st, hint, gdev);
+      if (!ctx->geom_hint_staged) OCTL_LAUNCH(k_geom_set, dim3(1), dim3(64), 0, b.st, b.hint, b.gdev);
     } else {
-      LinParams base = lp;
-      base.dshift = s;
-      OCTL_LAUNCH(k_bucket_geom, dim3(1), dim3(64), 0, st, (const int32_t*)f->bbox_dev.as<int32_t>(), ask, base, gdev);
+      OCTL_LAUNCH(k_bucket_geom, dim3(1), dim3(64), 0, b.st, (const int32_t*)f->bbox_dev.as<int32_t>(), b.ask, b.lp,
+                         b.gdev);
     }
     HIP_TRY(ctx, hipGetLastError());
-  } else if (hinted2) {
+  } else if (b.hinted2) {
     // the record holds the geometry the HOST formed from the hint's box (first-pass digit parameters); the kernels
     // of the first pass read it from there, everything behind it only looks at `valid`
-    gdev = reinterpret_cast<GeomDev*>(small + SM_GEOM);
     GeomDev g2;
     std::memset(&g2, 0, sizeof(g2));
-    g2.lp = lp_pass1;
-    std::memcpy(g2.bb, bb, sizeof(bb));
-    std::memcpy(g2.tb, tb, sizeof(tb));
+    g2.lp = b.lp_pass1;
+    std::memcpy(g2.bb, b.bb, sizeof(b.bb));
+    std::memcpy(g2.tb, b.tb, sizeof(b.tb));
     g2.valid = 1;
-    OCTL_LAUNCH(k_geom_set, dim3(1), dim3(64), 0, st, g2, gdev);
+    OCTL_LAUNCH(k_geom_set, dim3(1), dim3(64), 0, b.st, g2, b.gdev);
     HIP_TRY(ctx, hipGetLastError());
   }
-  auto table_scan = [&](uint32_t nst, uint32_t nd, uint32_t* bucket_start, int validate) {
-    const unsigned g = (nd + TS_COLS - 1) / TS_COLS;
-    uint64_t* status = nullptr;
-    uint32_t epoch = 0;
-    OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
-    OCTL_LAUNCH(k_table_scan, dim3(g), dim3(TS_THREADS), 0, st, table, nst, nd, bucket_start, status, epoch,
-                       validate, (const int32_t*)f->bbox_dev.as<int32_t>(), ask, lp, gdev);
-    HIP_TRY(ctx, hipGetLastError());
-    return (int)OCTL_OK;
-  };
-  {
-    KTimer t(ctx, "part_hist");
-    if (hinted || hinted2) {
-      auto kh = f->edge == 1.0 ? k_part_hist<true, true> : k_part_hist<true, false>;
-      OCTL_LAUNCH(kh, dim3(nst_a), dim3(PH_THREADS), 0, st, (const double*)f->xyz.as<double>(),
-                         alive_p, N, lp, (const GeomDev*)gdev, nst_a, nd_a, (int64_t)st_tiles_a * tile, table,
-                         f->bbox_dev.as<int32_t>());
-      HIP_TRY(ctx, hipGetLastError());
-      f->bbox_pending = false;  // (the box is on the device now, whatever becomes of the hint)
-      if (fused_a) {
-        // (k_table_scan validates the hint on its way)
-      } else if (hinted)
-        OCTL_LAUNCH(k_geom_validate, dim3(1), dim3(64), 0, st, (const int32_t*)f->bbox_dev.as<int32_t>(), ask,
-                           lp, gdev);
-      else
-        OCTL_LAUNCH(k_geom_validate2, dim3(1), dim3(64), 0, st, (const int32_t*)f->bbox_dev.as<int32_t>(), ask,
-                           gdev);
-    } else {
-      auto kh = f->edge == 1.0 ? k_part_hist<false, true> : k_part_hist<false, false>;
-      OCTL_LAUNCH(kh, dim3(nst_a), dim3(PH_THREADS), 0, st, (const double*)f->xyz.as<double>(),
-                         alive_p, N, lp, (const GeomDev*)gdev, nst_a, nd_a, (int64_t)st_tiles_a * tile, table,
-                         (int32_t*)nullptr);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  PartPass p;
+  p.n = f->n_store;
+  p.alive = f->n_alive == f->n_store ? nullptr : f->alive.as<uint8_t>();
+  p.scheme = a.scheme_dev;
+  p.lp = b.lp, p.gdev = b.gdev, p.ask = &b.ask;
+  p.validate = b.hinted ? 1 : (b.hinted2 ? 2 : 0);
+  p.nst = b.nst_a, p.nd = b.nd_a, p.tiles = b.tiles_a, p.tab_elems = b.tab_elems;
   // (a small table: the scatter kernel's workgroups scan it themselves - ScatterOwnScan)
-  const bool own_scan_a = fused_a && !two_pass && !hinted2 && nd_a <= 256u && nst_a <= PS_OWN_MAX_ROWS;
-  if (!own_scan_a) {
-    KTimer t(ctx, "part_scan");
-    if (fused_a) {
-      OCTL_TRY(table_scan(nst_a, nd_a, table_dm, hinted ? 1 : (hinted2 ? 2 : 0)));
-    } else {
-      HIP_TRY(ctx, transpose(table, nst_a, nd_a, table_dm));
-      OCTL_TRY(octl_exclusive_scan_u32(ctx, table_dm, table_dm, (int64_t)nd_a * nst_a, nullptr));
-      HIP_TRY(ctx, transpose(table_dm, nd_a, nst_a, table));
-    }
-  }
-  {
-    KTimer t(ctx, "part_scatter");
-    auto ks = own_scan_a ? k_part_scatter<PT_IPT, false, 8, true>
-                         : (nd_a <= 256u ? k_part_scatter<PT_IPT, false, 8> : k_part_scatter<PT_IPT, false, PT_BITS>);
-    ScatterOwnScan own;
-    std::memset(&own, 0, sizeof(own));
-    if (own_scan_a) {
-      own.bucket_start = table_dm;
-      own.validate = hinted ? 1 : 0;
-      own.bbox = (const int32_t*)f->bbox_dev.as<int32_t>();
-      own.ask = ask;
-      own.base = lp;
-      own.g = gdev;
-    }
-    OCTL_LAUNCH(ks, dim3(nst_a), dim3(PT_THREADS), 0, st,
-                       (const double*)f->xyz.as<double>(), alive_p, N, lp,
-                       (const GeomDev*)gdev, nst_a, nd_a, st_tiles_a, (const uint32_t*)table,
-                       (const int64_t*)f->pose_off_dev.as<int64_t>(), n_poses, a.scheme_dev,
-                       f->part_xyz[0].as<PartRec>(), own);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  const PartRec* recs = f->part_xyz[0].as<PartRec>();
-  const uint32_t* bstart = table_dm;
-  uint32_t bstride = fused_a ? 1u : nst_a;   // (k_table_scan leaves the buckets' starts as a plain array)
-  if (two_pass) {
-    // second (more significant) digit over the records of the first pass, then the bucket bounds
-    lp.dshift = s + bits_a;
-    lp.dmask = 0xFFFFFFFFu;
-    lp.raw_vp = 0;
-    {
-      KTimer t(ctx, "part_hist");
-      OCTL_LAUNCH(k_part_hist_rec, dim3(nst_b), dim3(PH_THREADS), 0, st,
-                         (const uint4*)f->part_xyz[0].as<uint4>(), n_alive, lp, (const GeomDev*)gdev, nst_b, nd_b,
-                         (int64_t)st_tiles_b * tile, table);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    {
-      KTimer t(ctx, "part_scan");
-      if (fused_b) {
-        OCTL_TRY(table_scan(nst_b, nd_b, table_dm, 0));
-      } else {
-        HIP_TRY(ctx, transpose(table, nst_b, nd_b, table_dm));
-        OCTL_TRY(octl_exclusive_scan_u32(ctx, table_dm, table_dm, (int64_t)nd_b * nst_b, nullptr));
-        HIP_TRY(ctx, transpose(table_dm, nd_b, nst_b, table));
-      }
-    }
-    {
-      KTimer t(ctx, "part_scatter");
-      auto ks = nd_b <= 256u ? k_part_scatter<PT_IPT, true, 8> : k_part_scatter<PT_IPT, true, PT_BITS>;
-      OCTL_LAUNCH(ks, dim3(nst_b), dim3(PT_THREADS), 0, st,
-                         (const double*)f->part_xyz[0].as<double>(), (const uint8_t*)nullptr, n_alive, lp,
-                         (const GeomDev*)gdev, nst_b, nd_b, st_tiles_b, (const uint32_t*)table, (const int64_t*)nullptr, 0,
-                         (const uint8_t*)nullptr, f->part_xyz[1].as<PartRec>(), ScatterOwnScan{});
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    uint32_t* bounds = table + 2 * tab_elems;
-    {
-      KTimer t(ctx, "bucket_bounds");
-      OCTL_LAUNCH(k_bucket_bounds, dim3((unsigned)ceil_div((int64_t)nb + 1, 256)), dim3(256), 0, st,
-                         (const uint4*)f->part_xyz[1].as<uint4>(), (uint32_t)n_alive, lp, (const GeomDev*)gdev, nb, bounds);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    recs = f->part_xyz[1].as<PartRec>();
-    bstart = bounds;
-    bstride = 1;
-  }
-  // ---- buckets ------------------------------------------------------------------------------------------------
-  BkParams bp;
-  bp.lp = lp;
-  bp.K = a.K;
-  bp.bstride = bstride;
-  bp.nb = nb;
-  bp.n_alive = (uint32_t)n_alive;
-  bp.n_poses = n_poses;
-  bp.all_scheme = a.scheme_dev ? 0 : 1;
-  uint32_t* bk_tot = f->bk_tot.as<uint32_t>();
-  uint32_t* bk_scan = bk_tot + tot_elems;
+  p.own_scan = tables_fused(ctx, b.nst_a) && !b.two_pass && !b.hinted2 && b.nd_a <= 256u && b.nst_a <= PS_OWN_MAX_ROWS;
+  p.out = f->part_xyz[0].as<PartRec>();
+  p.t_hist = "part_hist", p.t_scan = "part_scan", p.t_scatter = "part_scatter";
+  OCTL_TRY(partition_pass(f, p, &b.bstart, &b.bstride));
+  b.recs = p.out;
+  if (!b.two_pass) return OCTL_OK;
+  // second (more significant) digit over the records of the first pass, then the bucket bounds
+  b.lp.dshift = b.s + b.bits_a, b.lp.dmask = 0xFFFFFFFFu, b.lp.raw_vp = 0;
+  p.recs = b.recs, p.n = n_alive;
+  p.alive = p.scheme = nullptr;
+  p.lp = b.lp;
+  p.validate = 0, p.own_scan = false;
+  p.nst = b.nst_b, p.nd = b.nd_b, p.tiles = b.tiles_b;
+  p.out = f->part_xyz[1].as<PartRec>();
+  OCTL_TRY(partition_pass(f, p, &b.bstart, &b.bstride));
+  uint32_t* bounds = f->bk_table.as<uint32_t>() + 2 * b.tab_elems;
+  KTimer t(ctx, "bucket_bounds");
+  OCTL_LAUNCH(k_bucket_bounds, dim3((unsigned)ceil_div((int64_t)b.nb + 1, 256)), dim3(256), 0, b.st,
+                     (const uint4*)f->part_xyz[1].as<uint4>(), (uint32_t)n_alive, b.lp, (const GeomDev*)b.gdev, b.nb, bounds);
+  HIP_TRY(ctx, hipGetLastError());
+  b.recs = p.out, b.bstart = bounds, b.bstride = 1;
+  return OCTL_OK;
+}
+
+// the over-full buckets: the plan, then one workgroup per chunk
+int launch_chunks(BucketBuild& b, hipStream_t on) {
+  octl_forest* f = b.f;
+  OCTL_LAUNCH(k_bucket_plan, dim3(b.nb), dim3(BB_THREADS), 0, on, b.recs, b.bstart, b.bp, (const GeomDev*)b.gdev,
+                     b.ck_desc, b.ck_of_bucket, b.bk_tot, b.small);
+  HIP_TRY(b.ctx, hipGetLastError());
+  // one workgroup per chunk; the list's length is on the device, the grid strides over it
+  OCTL_LAUNCH(k_bucket_chunks, dim3((unsigned)std::min<int64_t>(2 * (int64_t)octl_ctx_cus(b.ctx), CK_CAP)),
+                     dim3(BB_THREADS), 0, on, b.recs, b.bstart, b.bp, (const GeomDev*)b.gdev,
+                     (const ChunkDesc*)b.ck_desc, b.ck_tot, (const int64_t*)f->pose_off_dev.as<int64_t>(),
+                     f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>(), f->leafinfo.as<uint32_t>(),
+                     f->bk_vox.as<uint32_t>(), f->bk_node.as<uint32_t>(), b.bk_tot, b.small);
+  HIP_TRY(b.ctx, hipGetLastError());
+  return OCTL_OK;
+}
+
+// One workgroup per bucket, the chunk kernels beside it when the context's previous build needed them; then
+// k_bucket_finish's parameters as far as they are known before the totals, and whether it is worth launching
+// speculatively, in front of the host's look at them (NodeParams::spec_geom).
+int build_buckets(BucketBuild& b, const BucketBuildArgs& a) {
+  octl_forest* f = b.f;
+  octl_ctx* ctx = b.ctx;
+  b.bp = BkParams{b.lp, a.K, b.bstride, b.nb, (uint32_t)f->n_alive, (int)f->pose_off.size() - 1, a.scheme_dev ? 0 : 1};
   // chunk plan of the buckets with more than BB_CAP points: [descriptors CK_CAP | totals CK_CAP x BK_ROWS | range per bucket]
   const size_t ck_off_tot = (size_t)CK_CAP * sizeof(ChunkDesc);
   const size_t ck_off_bkt = ck_off_tot + (size_t)CK_CAP * BK_ROWS * 4;
-  OCTL_TRY(devbuf_reserve(ctx, f->bk_chunks, ck_off_bkt + (size_t)nb * 8 + 16));
-  ChunkDesc* ck_desc = reinterpret_cast<ChunkDesc*>(f->bk_chunks.p);
-  uint32_t* ck_tot = reinterpret_cast<uint32_t*>(static_cast<char*>(f->bk_chunks.p) + ck_off_tot);
-  uint2* ck_of_bucket = reinterpret_cast<uint2*>(static_cast<char*>(f->bk_chunks.p) + ck_off_bkt);
+  OCTL_TRY(devbuf_reserve(ctx, f->bk_chunks, ck_off_bkt + (size_t)b.nb * 8 + 16));
+  b.ck_desc = reinterpret_cast<ChunkDesc*>(f->bk_chunks.p);
+  b.ck_tot = reinterpret_cast<uint32_t*>(static_cast<char*>(f->bk_chunks.p) + ck_off_tot);
+  b.ck_of_bucket = reinterpret_cast<uint2*>(static_cast<char*>(f->bk_chunks.p) + ck_off_bkt);
   // The over-full buckets (plan, then one workgroup per chunk) and the normal ones (k_bucket_build) touch disjoint
   // buckets, rows of bk_tot and output ranges.  An even scene has none of the former: k_bucket_build counts them
   // (SM_BK_OVERFULL) and the host launches the two chunk kernels only when the totals say that there are some - then
   // the totals are scanned again (round 5; before: two empty launches per build).  A context whose PREVIOUS build had
   // such buckets (a skewed scene, scan after scan) launches them right away on its side stream, NEXT TO
   // k_bucket_build, as round 4 did: a chunk is one workgroup's whole bucket build, worth hiding.
-  const bool chunks_beside = ctx->had_chunks;
-  auto launch_chunks = [&](hipStream_t on) {
-    OCTL_LAUNCH(k_bucket_plan, dim3(nb), dim3(BB_THREADS), 0, on, recs, bstart, bp, (const GeomDev*)gdev, ck_desc,
-                       ck_of_bucket, bk_tot, small);
-    HIP_TRY(ctx, hipGetLastError());
-    // one workgroup per chunk; the list's length is on the device, the grid strides over it
-    OCTL_LAUNCH(k_bucket_chunks, dim3((unsigned)std::min<int64_t>(2 * (int64_t)cus, CK_CAP)), dim3(BB_THREADS), 0, on,
-                       recs, bstart, bp, (const GeomDev*)gdev, (const ChunkDesc*)ck_desc, ck_tot,
-                       (const int64_t*)f->pose_off_dev.as<int64_t>(), f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>(),
-                       f->leafinfo.as<uint32_t>(), f->bk_vox.as<uint32_t>(), f->bk_node.as<uint32_t>(), bk_tot, small);
-    HIP_TRY(ctx, hipGetLastError());
-    return (int)OCTL_OK;
-  };
+  b.chunks_beside = ctx->had_chunks;
   {
     KTimer t(ctx, "bucket_build");
-    hipStream_t side = st;
+    hipStream_t side = b.st;
     bool on_side = false;
-    if (chunks_beside && octl_ctx_side_stream(ctx) && hipEventRecord(ctx->self_gate, st) == hipSuccess &&
+    if (b.chunks_beside && octl_ctx_side_stream(ctx) && hipEventRecord(ctx->self_gate, b.st) == hipSuccess &&
         hipStreamWaitEvent(ctx->self_stream, ctx->self_gate, 0) == hipSuccess) {
       side = ctx->self_stream;
       on_side = true;
     }
-    if (chunks_beside) OCTL_TRY(launch_chunks(side));
-    OCTL_LAUNCH(k_bucket_build, dim3(nb), dim3(BB_THREADS), 0, st, recs, bstart, bp,
-                       (const GeomDev*)gdev, (const int64_t*)f->pose_off_dev.as<int64_t>(), f->ord_idx.as<uint32_t>(),
-                       f->xyz_ord.as<double>(), f->leafinfo.as<uint32_t>(), f->bk_vox.as<uint32_t>(), f->bk_node.as<uint32_t>(),
-                       bk_tot, small, chunks_beside ? 0 : 1);
+    if (b.chunks_beside) OCTL_TRY(launch_chunks(b, side));
+    OCTL_LAUNCH(k_bucket_build, dim3(b.nb), dim3(BB_THREADS), 0, b.st, b.recs, b.bstart, b.bp, (const GeomDev*)b.gdev,
+                       (const int64_t*)f->pose_off_dev.as<int64_t>(), f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>(),
+                       f->leafinfo.as<uint32_t>(), f->bk_vox.as<uint32_t>(), f->bk_node.as<uint32_t>(), b.bk_tot, b.small,
+                       b.chunks_beside ? 0 : 1);
     HIP_TRY(ctx, hipGetLastError());
     if (on_side) {
       HIP_TRY(ctx, hipEventRecord(ctx->self_done, side));
-      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->self_done, 0));
+      HIP_TRY(ctx, hipStreamWaitEvent(b.st, ctx->self_done, 0));
     }
   }
-  static_assert(SM_GEOM == 64, "the geometry record is read back together with the 64 scalars in front of it");
-  const int mirror_words = (int)(64 + (gdev ? sizeof(GeomDev) / 4 : 0));
-  uint32_t sm[64];
-  // k_bucket_finish, launched the ordinary way (behind the host's look at the totals) or speculatively (in front of
-  // it: NodeParams::spec_geom)
-  NodePtrs nd_launch;
-  // (own_scan_seq != 0: the launch scans the totals itself and publishes them under that wait sequence number)
-  auto launch_finish = [&](const NodeParams& np, bool with_chunk_map, uint32_t own_scan_seq = 0) {
-    KTimer t(ctx, "bucket_nodes");
-    const size_t lds = own_scan_seq ? ((size_t)BK_ROWS * nb + 1) * 4 : 0;
-    auto kern = own_scan_seq ? k_bucket_finish<true> : k_bucket_finish<false>;
-    OCTL_LAUNCH(kern, dim3(nb), dim3(256), lds, st, nd_launch, np, bstart,
-                       (const uint32_t*)bk_scan, (const uint32_t*)(small + SM_BK_TOTAL),
-                       (const uint32_t*)f->leafinfo.as<uint32_t>(), (const uint32_t*)f->ord_idx.as<uint32_t>(),
-                       (const uint32_t*)f->bk_vox.as<uint32_t>(), (const uint32_t*)f->bk_node.as<uint32_t>(),
-                       (const int64_t*)f->pose_off_dev.as<int64_t>(), (const ChunkDesc*)ck_desc, (const uint32_t*)ck_tot,
-                       (const uint2*)(with_chunk_map ? ck_of_bucket : nullptr), f->pos_node.as<int32_t>(),
-                       f->vlin_dev.as<uint64_t>(), f->blk_node.as<int32_t>(), f->blk_slot.as<int32_t>(),
-                       f->blk_start.as<uint32_t>(), f->blk_size.as<int32_t>(), small,
-                       (const uint32_t*)(own_scan_seq ? bk_tot : nullptr), bk_scan,
-                       static_cast<uint32_t*>(ctx->small_host), mirror_words, own_scan_seq);
-    return hipGetLastError();
-  };
-  NodeParams np;
-  std::memset(&np, 0, sizeof(np));
-  np.lp = lp;
-  np.bstride = bstride;
-  np.nb = nb;
-  np.n_alive = (uint32_t)n_alive;
-  np.n_poses = n_poses;
-  np.all_scheme = bp.all_scheme;
-  np.cur_epoch = a.cur_epoch;
-  np.old_fc = a.old_fc;
-  np.old_epoch = a.old_epoch;
-  np.old_vcode = a.old_vcode;
-  np.old_voxels = a.old_voxels;
-  // Speculative k_bucket_finish (see NodeParams): a fresh scheme under a geometry record on the device and tables sized from the context's previous bucket build (ctx->spec_*: 25 % above what that one
-  // needed).  OCTL_NO_SPEC_FINISH: never.
-  bool spec_launched = false;
-  int64_t spec_node_cap = 0, spec_vox_cap = 0, spec_blk_cap = 0;
-  const bool spec_order = n_poses == 1 && !ctx->opt.no_fast_order;
+  NodeParams& np = b.np;
+  np.lp = b.lp;
+  np.bstride = b.bstride, np.nb = b.nb, np.n_alive = (uint32_t)f->n_alive;
+  np.n_poses = b.bp.n_poses, np.all_scheme = b.bp.all_scheme, np.cur_epoch = a.cur_epoch;
+  np.old_fc = a.old_fc, np.old_epoch = a.old_epoch, np.old_vcode = a.old_vcode, np.old_voxels = a.old_voxels;
+  // Speculative k_bucket_finish (see NodeParams): a fresh scheme under a geometry record on the device and tables sized
+  // from the context's previous bucket build (ctx->spec_*: 25 % above what that one needed).  OCTL_NO_SPEC_FINISH: never.
+  b.spec_order = np.n_poses == 1 && !ctx->opt.no_fast_order;
   // (the voxel origin is only read against a previous scheme: NodeParams::org)
-  const bool spec_want = async_geom && gdev && !a.old_fc && !a.old_vcode && ctx->spec_nodes > 0 &&
-                         !ctx->opt.no_spec_finish;
+  b.spec_want = b.async_geom && b.gdev && !a.old_fc && !a.old_vcode && ctx->spec_nodes > 0 && !ctx->opt.no_spec_finish;
   // (few buckets: the speculative launch scans the totals itself - no k_bucket_scan_totals in front of it)
-  const bool own_scan = spec_want && !ctx->opt.no_fused_tables && (uint32_t)BK_ROWS * nb <= (uint32_t)BF_SCAN_MAX;
-  auto spec_finish = [&](uint32_t own_scan_seq) {
+  b.spec_own_scan = b.spec_want && !ctx->opt.no_fused_tables && (uint32_t)BK_ROWS * b.nb <= (uint32_t)BF_SCAN_MAX;
+  return OCTL_OK;
+}
+
+// k_bucket_finish, launched the ordinary way (behind the host's look at the totals) or speculatively (in front of it)
+// (own_scan_seq != 0: the launch scans the totals itself and publishes them under that wait sequence number)
+int launch_finish(const BucketBuild& b, NodeTable& nt, const NodeParams& np, bool with_chunk_map, uint32_t own_scan_seq) {
+  octl_forest* f = b.f;
+  KTimer t(b.ctx, "bucket_nodes");
+  const size_t lds = own_scan_seq ? ((size_t)BK_ROWS * b.nb + 1) * 4 : 0;
+  auto kern = own_scan_seq ? k_bucket_finish<true> : k_bucket_finish<false>;
+  OCTL_LAUNCH(kern, dim3(b.nb), dim3(256), lds, b.st, node_ptrs(nt), np, b.bstart,
+                     (const uint32_t*)b.bk_scan, (const uint32_t*)(b.small + SM_BK_TOTAL),
+                     (const uint32_t*)f->leafinfo.as<uint32_t>(), (const uint32_t*)f->ord_idx.as<uint32_t>(),
+                     (const uint32_t*)f->bk_vox.as<uint32_t>(), (const uint32_t*)f->bk_node.as<uint32_t>(),
+                     (const int64_t*)f->pose_off_dev.as<int64_t>(), (const ChunkDesc*)b.ck_desc, (const uint32_t*)b.ck_tot,
+                     (const uint2*)(with_chunk_map ? b.ck_of_bucket : nullptr), f->pos_node.as<int32_t>(),
+                     f->vlin_dev.as<uint64_t>(), f->blk_node.as<int32_t>(), f->blk_slot.as<int32_t>(),
+                     f->blk_start.as<uint32_t>(), f->blk_size.as<int32_t>(), b.small,
+                     (const uint32_t*)(own_scan_seq ? b.bk_tot : nullptr), b.bk_scan,
+                     static_cast<uint32_t*>(b.ctx->small_host), mirror_words(b), own_scan_seq);
+  HIP_TRY(b.ctx, hipGetLastError());
+  return OCTL_OK;
+}
+
+// raw totals -> scanned totals + the build's scalars in the pinned mirror; the host polls for them (b.sm)
+int scan_totals(BucketBuild& b, NodeTable& nt, bool with_spec) {
+  octl_forest* f = b.f;
+  octl_ctx* ctx = b.ctx;
+  uint32_t* mirror = static_cast<uint32_t*>(ctx->small_host);
+  const uint32_t wait_seq = octl_wait_next_seq(ctx);
+  if (!(with_spec && b.spec_own_scan)) {
+    KTimer t(ctx, "bucket_scan");
+    if (!ctx->opt.no_fused_tables) {
+      const uint32_t n_tot = (uint32_t)BK_ROWS * b.nb;
+      const unsigned g = (n_tot + BT_TILE - 1) / BT_TILE;
+      uint64_t* status = nullptr;
+      uint32_t epoch = 0;
+      OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
+      OCTL_LAUNCH(k_bucket_scan_totals, dim3(g), dim3(BT_THREADS), 0, b.st, (const uint32_t*)b.bk_tot, b.bk_scan, n_tot,
+                         b.nb, status, epoch, b.small, mirror, mirror_words(b), wait_seq);
+    } else {
+      OCTL_TRY(octl_exclusive_scan_u32(ctx, b.bk_tot, b.bk_scan, (int64_t)BK_ROWS * b.nb, b.small + SM_BK_TOTAL));
+      OCTL_LAUNCH(k_bucket_totals, dim3(1), dim3(64), 0, b.st, (const uint32_t*)b.bk_scan, b.nb,
+                         (const uint32_t*)(b.small + SM_BK_TOTAL), b.small, mirror, mirror_words(b), wait_seq);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (with_spec) {  // the speculative finish, sized from the context's previous build
     // (a table that held the previous build is taken as it is - growing a live buffer waits for the stream, and the
     //  kernel checks the real capacities anyway; one that did not is sized 25 % above that build)
     // (the previous build's counts, in proportion to the points: a scan ten times larger is not given tables that
     //  the ordinary launch would have to grow right away)
-    const double scale = (double)n_alive / (double)std::max<int64_t>(ctx->spec_points, 1);
+    const double scale = (double)f->n_alive / (double)std::max<int64_t>(ctx->spec_points, 1);
     auto expect = [&](int64_t prev) { return (int64_t)std::ceil((double)prev * scale); };
     const int64_t e_nodes = expect(ctx->spec_nodes), e_vox = expect(ctx->spec_vox), e_blocks = expect(ctx->spec_blocks);
     if (nt.cap < e_nodes) OCTL_TRY(nodes_reserve(ctx, nt, e_nodes + e_nodes / 4 + 64));
     if (f->vlin_dev.cap < (size_t)e_vox * 8) OCTL_TRY(devbuf_reserve(ctx, f->vlin_dev, (size_t)(e_vox + e_vox / 4 + 64) * 8));
-    if (spec_order && f->fast_order.cap < (size_t)e_blocks * 4)
+    if (b.spec_order && f->fast_order.cap < (size_t)e_blocks * 4)
       OCTL_TRY(devbuf_reserve(ctx, f->fast_order, (size_t)(e_blocks + e_blocks / 4 + 64) * 4));
-    spec_node_cap = nt.cap;
-    spec_vox_cap = (int64_t)(f->vlin_dev.cap / 8);
-    spec_blk_cap = spec_order ? (int64_t)(f->fast_order.cap / 4) : ((int64_t)1 << 40);
-    nd_launch = node_ptrs(nt);
-    NodeParams sp = np;
-    sp.node_cap = spec_node_cap;
+    b.spec_node_cap = nt.cap;
+    b.spec_vox_cap = (int64_t)(f->vlin_dev.cap / 8);
+    b.spec_blk_cap = b.spec_order ? (int64_t)(f->fast_order.cap / 4) : ((int64_t)1 << 40);
+    NodeParams sp = b.np;
+    sp.node_cap = b.spec_node_cap, sp.vox_cap = b.spec_vox_cap, sp.blk_cap = b.spec_blk_cap;
     sp.write_pos = 0;
-    sp.order_out = spec_order ? f->fast_order.as<int32_t>() : nullptr;
+    sp.order_out = b.spec_order ? f->fast_order.as<int32_t>() : nullptr;
     sp.org = f->vorg;
-    sp.spec_geom = gdev;
-    sp.spec_chunks = chunks_beside ? 1 : 0;
-    sp.vox_cap = spec_vox_cap;
-    sp.blk_cap = spec_blk_cap;
-    HIP_TRY(ctx, launch_finish(sp, chunks_beside, own_scan_seq));
-    spec_launched = true;
-    return (int)OCTL_OK;
-  };
-  // raw totals -> scanned totals + the build's scalars in the pinned mirror; the host polls for them
-  auto scan_totals = [&](bool with_spec) {
-    const uint32_t wait_seq = octl_wait_next_seq(ctx);
-    if (!(with_spec && own_scan)) {
-      KTimer t(ctx, "bucket_scan");
-      if (!ctx->opt.no_fused_tables) {
-        const uint32_t n_tot = (uint32_t)BK_ROWS * nb;
-        const unsigned g = (n_tot + BT_TILE - 1) / BT_TILE;
-        uint64_t* status = nullptr;
-        uint32_t epoch = 0;
-        OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
-        OCTL_LAUNCH(k_bucket_scan_totals, dim3(g), dim3(BT_THREADS), 0, st, (const uint32_t*)bk_tot, bk_scan, n_tot,
-                           nb, status, epoch, small, static_cast<uint32_t*>(ctx->small_host), mirror_words, wait_seq);
-      } else {
-        OCTL_TRY(octl_exclusive_scan_u32(ctx, bk_tot, bk_scan, (int64_t)BK_ROWS * nb, small + SM_BK_TOTAL));
-        OCTL_LAUNCH(k_bucket_totals, dim3(1), dim3(64), 0, st, (const uint32_t*)bk_scan, nb,
-                           (const uint32_t*)(small + SM_BK_TOTAL), small, static_cast<uint32_t*>(ctx->small_host),
-                           mirror_words, wait_seq);
-      }
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    if (with_spec) OCTL_TRY(spec_finish(own_scan ? wait_seq : 0u));
-    // (the totals kernel writes the scalars and then its flag into the pinned mirror)
-    const int flag = MIRROR_FLAG_BUILD;
-    // (polling budget: behind an asynchronous apply_mask the previous scan's RANSAC may still be running in front of
-    //  this build - 2.2 ms at 10 M points; falling back to a stream synchronisation would also wait for the
-    //  speculative finish that was enqueued to run BESIDE this wait)
-    OCTL_TRY(octl_wait_mirror_flags(ctx, &flag, 1, wait_seq, 500 + n_alive / 2000));
-    std::memcpy(sm, ctx->small_host, sizeof(sm));
-    return (int)OCTL_OK;
-  };
-  OCTL_TRY(scan_totals(spec_want));
-  if (hinted2) {
-    GeomDev g;
-    std::memcpy(&g, static_cast<char*>(ctx->small_host) + SM_GEOM * 4, sizeof(g));
-    if (!g.valid) {
-      if (g.reason == GEOM_DOMAIN)
-        return octl_set_error(ctx, OCTL_E_DOMAIN,
-                              "a point has a non-finite coordinate or a top-level voxel index outside +-%d",
-                              OCTL_VOX_ABS_LIMIT);
-      if (g.reason == GEOM_EMPTY) return OCTL_OK;
+    sp.spec_geom = b.gdev, sp.spec_chunks = b.chunks_beside ? 1 : 0;
+    OCTL_TRY(launch_finish(b, nt, sp, b.chunks_beside, b.spec_own_scan ? wait_seq : 0u));
+    b.spec_launched = true;
+  }
+  // (the totals kernel writes the scalars and then its flag into the pinned mirror)
+  const int flag = MIRROR_FLAG_BUILD;
+  // (polling budget: behind an asynchronous apply_mask the previous scan's RANSAC may still be running in front of
+  //  this build - 2.2 ms at 10 M points; falling back to a stream synchronisation would also wait for the
+  //  speculative finish that was enqueued to run BESIDE this wait)
+  OCTL_TRY(octl_wait_mirror_flags(ctx, &flag, 1, wait_seq, 500 + f->n_alive / 2000));
+  std::memcpy(b.sm, ctx->small_host, sizeof(b.sm));
+  return OCTL_OK;
+}
+
+// What the geometry record says now that the totals are here: the verdict on a hint, the next build's hint, and - for
+// a geometry formed on the device - the geometry itself (b.lp, b.bb, b.tb).
+int interpret_geometry(BucketBuild& b, BuildVerdict* v) {
+  octl_ctx* ctx = b.ctx;
+  GeomDev g;
+  *v = BV_GO;
+  if (b.hinted2) {
+    OCTL_TRY(geom_read(ctx, &g, v));
+    if (*v == BV_AGAIN_ASYNC || *v == BV_AGAIN_HOST) {
       // the hinted box did not hold: the true one is on the device now, the host-side form builds again from it
       ctx->geom_hint_valid = false;
-      return bucket_build_impl(f, a, nt, done, segs, n_internal, levels, n_voxels, n_blocks, pending, geom, true);
+      *v = BV_AGAIN_HOST;
     }
-    std::memcpy(tb, g.tb, sizeof(tb));   // the true box this cloud turned out to have
+    if (*v != BV_GO) return OCTL_OK;
+    std::memcpy(b.tb, g.tb, sizeof(b.tb));   // the true box this cloud turned out to have
   }
-  if (!async_geom && two_pass && f->mode == 0) {
+  if (!b.async_geom && b.two_pass && b.f->mode == 0) {
     // the true box of this two-pass build, padded, is the box of the context's next one (the keys of THIS build
     // stay relative to bb; a scene that drifts is followed scan by scan)
-    GeomDev g;
     std::memset(&g, 0, sizeof(g));
-    g.lp = lp_pass1;
-    geom_pad_box(tb, margin, g.bb);
-    std::memcpy(g.tb, tb, sizeof(tb));
+    g.lp = b.lp_pass1;
+    geom_pad_box(b.tb, b.ask.margin, g.bb);
+    std::memcpy(g.tb, b.tb, sizeof(b.tb));
     g.valid = 1;
-    static_assert(sizeof(GeomDev) <= sizeof(ctx->geom_hint), "hint storage");
-    std::memcpy(ctx->geom_hint, &g, sizeof(g));
-    ctx->geom_hint_valid = true;
-    ctx->geom_hint_two_pass = true;
-    ctx->geom_hint_want = want;
+    hint_store(ctx, g, true, b.ask.want);
   }
-  if (async_geom) {
-    GeomDev g;
-    std::memcpy(&g, static_cast<char*>(ctx->small_host) + SM_GEOM * 4, sizeof(g));
-    if (!g.valid) {
-      if (g.reason == GEOM_DOMAIN)
-        return octl_set_error(ctx, OCTL_E_DOMAIN,
-                              "a point has a non-finite coordinate or a top-level voxel index outside +-%d",
-                              OCTL_VOX_ABS_LIMIT);
-      if (g.reason == GEOM_EMPTY) return OCTL_OK;
-      // the hinted geometry did not hold (the scene jumped by more than the margin, or its density changed): the
-      // box is on the device now, the build runs again from it - one histogram pass and one round trip lost
-      if (g.reason == GEOM_REHASH)
-        return bucket_build_impl(f, a, nt, done, segs, n_internal, levels, n_voxels, n_blocks, pending, geom, false);
-      // not a single-pass case after all (a sparse scene): the host-side form decides
-      return bucket_build_impl(f, a, nt, done, segs, n_internal, levels, n_voxels, n_blocks, pending, geom, true);
-    }
+  if (b.async_geom) {
+    // GEOM_REHASH, BV_AGAIN_ASYNC: the hinted geometry did not hold (the scene jumped by more than the margin, or its
+    // density changed): the box is on the device now, the build runs again from it - one histogram pass and one
+    // round trip lost.  GEOM_RETRY, BV_AGAIN_HOST: not a single-pass case after all (a sparse scene): the host-side
+    // form decides
+    OCTL_TRY(geom_read(ctx, &g, v));
+    if (*v != BV_GO) return OCTL_OK;
     // the next build's hint: the geometry of THIS cloud's true box (the same function the device evaluates) - under a
     // hint that held, the box the histogram pass found on its way; the scene is followed scan by scan
-    {
-      LinParams base = lp;
-      GeomDev nh;
-      geom_from_box(g.tb, false, ask, base, nh);
-      static_assert(sizeof(GeomDev) <= sizeof(ctx->geom_hint), "hint storage");
-      std::memset(ctx->geom_hint, 0, sizeof(ctx->geom_hint));
-      std::memcpy(ctx->geom_hint, &nh, sizeof(nh));
-      ctx->geom_hint_valid = nh.valid != 0;
-      ctx->geom_hint_two_pass = false;
-      ctx->geom_hint_want = want;
-    }
-    lp = g.lp;
-    std::memcpy(bb, g.bb, sizeof(bb));
-    std::memcpy(tb, g.tb, sizeof(tb));
-    ny = lp.ny;
-    nz = lp.nz;
+    GeomDev nh;
+    geom_from_box(g.tb, false, b.ask, b.lp, nh);
+    hint_store(ctx, nh, false, b.ask.want);
+    b.lp = g.lp;
+    std::memcpy(b.bb, g.bb, sizeof(b.bb));
+    std::memcpy(b.tb, g.tb, sizeof(b.tb));
+    b.ny = b.lp.ny, b.nz = b.lp.nz;
   }
-  // the packed voxel keys of everything that follows (k_bucket_finish's walk over the previous scheme, the
-  // incremental insertion, the host's voxel list) are relative to the origin this fixes on the first build
-  if (f->mode == 0) OCTL_TRY(forest_fix_origin(f, tb));
-  // buckets beyond 4096 points that nobody has built yet: plan + chunks now, then the totals once more
-  const bool overfull = sm[SM_BK_OVERFULL] > 0;
-  if (overfull && !chunks_beside && !sm[SM_BK_FLAGS]) {
-    {
-      KTimer t(ctx, "bucket_build");
-      OCTL_TRY(launch_chunks(st));
-    }
-    OCTL_TRY(scan_totals(false));
-  }
-  ctx->had_chunks = overfull;
+  return OCTL_OK;
+}
+
+// The totals are final: the level segments, k_bucket_finish unless the speculative launch has done its work, and
+// the result.  r->done stays 0 when the build is the general path's after all.
+int finish_and_commit(BucketBuild& b, const BucketBuildArgs& a, NodeTable& nt, bool overfull, BucketBuildResult* r) {
+  octl_forest* f = b.f;
+  octl_ctx* ctx = b.ctx;
+  const uint32_t* sm = b.sm;
   if (sm[SM_BK_FLAGS]) return OCTL_OK;  // some bucket / voxel does not fit: the caller runs the general path
   const int64_t V = sm[SM_NVOX];
   int64_t n_int = 0;
   int depth = 0;
-  segs->assign(1, octl_forest::LevelSeg{0, V, 0});
+  r->segs.assign(1, octl_forest::LevelSeg{0, V, 0});
   for (int l = 0; l < BB_LEVELS; ++l) {
     if (sm[SM_BK_LEVEL + l] == 0) break;
     n_int += sm[SM_BK_LEVEL + l];
     depth = l + 1;
-    segs->push_back(octl_forest::LevelSeg{V + 8 * (n_int - (int64_t)sm[SM_BK_LEVEL + l]), V + 8 * n_int, l + 1});
+    r->segs.push_back(octl_forest::LevelSeg{V + 8 * (n_int - (int64_t)sm[SM_BK_LEVEL + l]), V + 8 * n_int, l + 1});
   }
   if (depth > a.max_depth) return octl_set_error(ctx, OCTL_E_DEPTH, "maximum depth %d exceeded", a.max_depth);
   const int64_t total = V + 8 * n_int;
   if (total >= ((int64_t)1 << 31)) return octl_set_error(ctx, OCTL_E_NOMEM, "more than 2^31 scheme nodes");
   // the listing order of the blocks falls out of the same kernel for the common case: one pose, a fresh
   // scheme (one epoch), nothing left to the level loop, no bucket beyond what the kernel ranks in LDS
-  const bool fast_order = n_poses == 1 && !a.old_fc && sm[SM_BK_TODO] == 0 && sm[SM_BK_NOORDER] == 0 &&
+  const bool fast_order = b.np.n_poses == 1 && !a.old_fc && sm[SM_BK_TODO] == 0 && sm[SM_BK_NOORDER] == 0 &&
                           !ctx->opt.no_fast_order;
   // the speculative launch did the work iff the words it looked at on the device - the same ones as in `sm` - passed
-  // (the geometry record is valid here: the invalid cases have returned above)
-  const bool spec_held = spec_launched && sm[SM_BK_TODO] == 0 && sm[SM_BK_NOORDER] == 0 &&
-                         (chunks_beside || !overfull) && V <= spec_vox_cap && (int64_t)sm[SM_NBLOCKS] <= spec_blk_cap &&
-                         total <= spec_node_cap;
-  ctx->spec_points = n_alive;
-  ctx->spec_nodes = total;
-  ctx->spec_vox = V;
-  ctx->spec_blocks = sm[SM_NBLOCKS];
-  if (spec_launched) (spec_held ? g_octl_spec_held : g_octl_spec_missed).fetch_add(1, std::memory_order_relaxed);
+  // (the geometry record is valid here: the invalid cases have left the attempt)
+  const bool spec_held = b.spec_launched && sm[SM_BK_TODO] == 0 && sm[SM_BK_NOORDER] == 0 &&
+                         (b.chunks_beside || !overfull) && V <= b.spec_vox_cap &&
+                         (int64_t)sm[SM_NBLOCKS] <= b.spec_blk_cap && total <= b.spec_node_cap;
+  ctx->spec_points = f->n_alive, ctx->spec_nodes = total, ctx->spec_vox = V, ctx->spec_blocks = sm[SM_NBLOCKS];
+  if (b.spec_launched) (spec_held ? g_octl_spec_held : g_octl_spec_missed).fetch_add(1, std::memory_order_relaxed);
   if (!spec_held) {
     OCTL_TRY(nodes_reserve(ctx, nt, total));
     OCTL_TRY(devbuf_reserve(ctx, f->vlin_dev, (size_t)std::max<int64_t>(V, 1) * 8));
-    nd_launch = node_ptrs(nt);
     // (first_child = -1 / epoch = 0 of every node: written by k_bucket_finish with the node's other fields)
-    np.lp = lp;
-    np.node_cap = nt.cap;
+    NodeParams& np = b.np;
+    np.lp = b.lp, np.node_cap = nt.cap, np.org = f->vorg;
     np.write_pos = sm[SM_BK_TODO] > 0;
-    np.org = f->vorg;
     np.order_out = nullptr;
     if (fast_order) {
       OCTL_TRY(devbuf_reserve(ctx, f->fast_order, (size_t)std::max<uint32_t>(sm[SM_NBLOCKS], 1) * 4));
       np.order_out = f->fast_order.as<int32_t>();
     }
-    HIP_TRY(ctx, launch_finish(np, overfull || chunks_beside));
+    OCTL_TRY(launch_finish(b, nt, np, overfull || b.chunks_beside, 0));
     // (block sizes: written by k_bucket_finish itself since round 5 - a block ends where the next head of its piece
     //  is, or with the piece)
   }
   if (a.old_vcode && a.old_voxels > 0) {
     // a voxel of the previous scheme that has lost all its points keeps its (empty) octree in the reference:
     // roots this path cannot make - the general path takes the build then (nothing is committed yet)
-    HIP_TRY(ctx, hipMemsetAsync(small + SM_BK_MISSING, 0, 4, st));
-    OCTL_LAUNCH(k_old_voxels_missing, dim3((unsigned)ceil_div(a.old_voxels, 256)), dim3(256), 0, st,
-                       a.old_vcode, a.old_voxels, (const uint64_t*)f->vlin_dev.as<uint64_t>(), V, lp,
-                       bb[3] - bb[0] + 1, f->vorg, small + SM_BK_MISSING);
+    HIP_TRY(ctx, hipMemsetAsync(b.small + SM_BK_MISSING, 0, 4, b.st));
+    OCTL_LAUNCH(k_old_voxels_missing, dim3((unsigned)ceil_div(a.old_voxels, 256)), dim3(256), 0, b.st,
+                       a.old_vcode, a.old_voxels, (const uint64_t*)f->vlin_dev.as<uint64_t>(), V, b.lp,
+                       b.bb[3] - b.bb[0] + 1, f->vorg, b.small + SM_BK_MISSING);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t missing = 0;
-    OCTL_TRY(octl_readback(ctx, small + SM_BK_MISSING, 1, &missing));
+    OCTL_TRY(octl_readback(ctx, b.small + SM_BK_MISSING, 1, &missing));
     if (missing) return OCTL_OK;
   }
   nt.n = total;
-  *n_internal = n_int;
-  *levels = depth;
-  *n_voxels = V;
-  *n_blocks = sm[SM_NBLOCKS];
-  *pending = sm[SM_BK_TODO];
-  geom->min[0] = bb[0];
-  geom->min[1] = bb[1];
-  geom->min[2] = bb[2];
-  geom->ny = ny;
-  geom->nz = nz;
-  geom->order_done = fast_order;
-  *done = 1;
+  r->n_internal = n_int, r->levels = depth, r->n_voxels = V;
+  r->n_blocks = sm[SM_NBLOCKS], r->pending = sm[SM_BK_TODO];
+  for (int k = 0; k < 3; ++k) r->geom.min[k] = b.bb[k];
+  r->geom.ny = b.ny, r->geom.nz = b.nz, r->geom.order_done = fast_order;
+  r->done = 1;
   return OCTL_OK;
+}
+
+}  // namespace
+
+// Complete build of a fresh forest (no previous scheme): r->done = 1 when the scheme, the leaf-ordered arrays,
+// pos_node and the block table are complete; r->done = 0 when this path does not apply (the caller then runs the
+// general path; nothing it relies on has been modified).
+int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, BucketBuildResult* r) {
+  octl_ctx* ctx = f->ctx;
+  r->done = 0;
+  // (OCTL_NO_BUCKET_BUILD: tests compare this path with the level-synchronous one)
+  if (f->n_alive <= 0 || !f->bbox_dev.p || ctx->opt.no_bucket_build) return OCTL_OK;
+  // a single cube (bare Octree / OctreeManager) is ONE bucket: beyond what the oversize launch takes it is the
+  // level loop's job from the start
+  if (f->mode == 1 && f->n_alive > 65535) return OCTL_OK;
+  // A rejected hint and a sparse scene make the build start over, at most twice in a row by design: anything beyond
+  // four attempts is a bug.  What an attempt leaves to the next one: f->bbox_pending (false once a histogram pass has
+  // found the box), ctx->geom_hint_valid, ctx->geom_sparse - everything else is formed again.
+  bool force_sync = false;
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    BucketBuild b{f, ctx, ctx->stream, ctx->small.as<uint32_t>()};  // (the rest: zero)
+    BuildVerdict v = BV_GO;
+    OCTL_TRY(plan_geometry(b, force_sync, &v));
+    if (v == BV_AGAIN_HOST) {  // (a two-pass hint whose box asks for one pass)
+      force_sync = true;
+      continue;
+    }
+    if (v != BV_GO) return OCTL_OK;
+    OCTL_TRY(partition(b, a));
+    OCTL_TRY(build_buckets(b, a));
+    OCTL_TRY(scan_totals(b, nt, b.spec_want));
+    OCTL_TRY(interpret_geometry(b, &v));
+    if (v == BV_AGAIN_ASYNC || v == BV_AGAIN_HOST) {  // (a hint that did not hold, a sparse scene: interpret_geometry)
+      force_sync = v == BV_AGAIN_HOST;
+      continue;
+    }
+    if (v != BV_GO) return OCTL_OK;
+    // the packed voxel keys of everything that follows (k_bucket_finish's walk over the previous scheme, the
+    // incremental insertion, the host's voxel list) are relative to the origin this fixes on the first build
+    if (f->mode == 0) OCTL_TRY(forest_fix_origin(f, b.tb));
+    // buckets beyond 4096 points that nobody has built yet: plan + chunks now, then the totals once more
+    const bool overfull = b.sm[SM_BK_OVERFULL] > 0;
+    if (overfull && !b.chunks_beside && !b.sm[SM_BK_FLAGS]) {
+      {
+        KTimer t(ctx, "bucket_build");
+        OCTL_TRY(launch_chunks(b, ctx->stream));
+      }
+      OCTL_TRY(scan_totals(b, nt, false));
+    }
+    ctx->had_chunks = overfull;
+    return finish_and_commit(b, a, nt, overfull, r);
+  }
+  return octl_set_error(ctx, OCTL_E_STATE, "bucket build: the geometry retries do not terminate");
 }
 
 // A big single cube (bare Octree / OctreeManager with millions of points) partitioned ONCE by the child digits of
@@ -3093,74 +3134,26 @@ static int bucket_build_impl(octl_forest* f, const BucketBuildArgs& a, NodeTable
 int forest_prefix_partition(octl_forest* f, int pm, const void** recs_out, const uint32_t** bstart, uint32_t* bstride,
                             const uint32_t** bad_flag) {
   octl_ctx* ctx = f->ctx;
-  hipStream_t st = ctx->stream;
   const int64_t N = f->n_store;
-  const int n_poses = (int)f->pose_off.size() - 1;
-  LinParams lp;
+  PartPass p;
+  LinParams& lp = p.lp;
   std::memset(&lp, 0, sizeof(lp));
-  lp.mode = 2;
-  lp.pm = pm;
-  lp.L = f->edge;
-  lp.c0x = f->corner[0];
-  lp.c0y = f->corner[1];
-  lp.c0z = f->corner[2];
+  lp.mode = 2, lp.pm = pm, lp.L = f->edge;
+  lp.c0x = f->corner[0], lp.c0y = f->corner[1], lp.c0z = f->corner[2];
   lp.ny = lp.nz = 1;
-  lp.shift = 0;
-  lp.dshift = 0;
   lp.dmask = 0xFFFFFFFFu;
-  lp.raw_vp = 0;
   lp.exact_digits = ctx->opt.no_exact_digits ? 0 : 1;
-  const uint32_t nd = 1u << (3 * pm);
-  const int cus = octl_ctx_cus(ctx);
-  constexpr int PT_IPT = OCTL_PT_IPT;
-  constexpr int tile = PT_THREADS * PT_IPT;
-  const int st_tiles = (int)std::min<int64_t>(16, std::max<int64_t>(1, ceil_div(ceil_div(N, tile), (int64_t)cus * OCTL_PT_WGS)));
-  const uint32_t nst = (uint32_t)ceil_div(N, (int64_t)st_tiles * tile);
+  p.n = N, p.nd = 1u << (3 * pm);
+  p.nst = supertiles(ctx, N, OCTL_PT_WGS, &p.tiles);
   OCTL_TRY(devbuf_reserve(ctx, f->part_xyz[0], (size_t)N * sizeof(PartRec)));
-  const size_t tab_elems = (((size_t)nd * nst) + 1 + 15) & ~(size_t)15;
-  OCTL_TRY(devbuf_reserve(ctx, f->bk_table, (2 * tab_elems + 16) * 4));
-  uint32_t* table = f->bk_table.as<uint32_t>();
-  uint32_t* table_dm = table + tab_elems;
-  uint32_t* flag = table + 2 * tab_elems;
-  HIP_TRY(ctx, hipMemsetAsync(flag, 0, 4, st));
-  const bool fused = !ctx->opt.no_fused_tables && nst <= TS_MAX_ROWS;   // (the table in one launch: k_table_scan)
-  auto transpose = [&](const uint32_t* in, uint32_t R, uint32_t Cc, uint32_t* out) {
-    OCTL_LAUNCH(k_transpose_u32, dim3((Cc + 63) / 64, (R + 63) / 64), dim3(256), 0, st, in, R, Cc, out);
-    return hipGetLastError();
-  };
-  {
-    KTimer t(ctx, "prefix_hist");
-    auto kh = f->edge == 1.0 ? k_part_hist<false, true> : k_part_hist<false, false>;
-    OCTL_LAUNCH(kh, dim3(nst), dim3(PH_THREADS), 0, st, (const double*)f->xyz.as<double>(), (const uint8_t*)nullptr,
-                       N, lp, (const GeomDev*)nullptr, nst, nd, (int64_t)st_tiles * tile, table,
-                       reinterpret_cast<int32_t*>(flag));
-    HIP_TRY(ctx, hipGetLastError());
-    if (fused) {
-      const unsigned g = (nd + TS_COLS - 1) / TS_COLS;
-      uint64_t* status = nullptr;
-      uint32_t epoch = 0;
-      OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
-      OCTL_LAUNCH(k_table_scan, dim3(g), dim3(TS_THREADS), 0, st, table, nst, nd, table_dm, status, epoch, 0,
-                         (const int32_t*)nullptr, GeomAsk{0, 0, 0, 0}, lp, (GeomDev*)nullptr);
-      HIP_TRY(ctx, hipGetLastError());
-    } else {
-      HIP_TRY(ctx, transpose(table, nst, nd, table_dm));
-      OCTL_TRY(octl_exclusive_scan_u32(ctx, table_dm, table_dm, (int64_t)nd * nst, nullptr));
-      HIP_TRY(ctx, transpose(table_dm, nd, nst, table));
-    }
-  }
-  {
-    KTimer t(ctx, "prefix_scatter");
-    auto ks = nd <= 256u ? k_part_scatter<PT_IPT, false, 8> : k_part_scatter<PT_IPT, false, PT_BITS>;
-    OCTL_LAUNCH(ks, dim3(nst), dim3(PT_THREADS), 0, st, (const double*)f->xyz.as<double>(), (const uint8_t*)nullptr, N,
-                       lp, (const GeomDev*)nullptr, nst, nd, st_tiles, (const uint32_t*)table,
-                       (const int64_t*)f->pose_off_dev.as<int64_t>(), n_poses, (const uint8_t*)nullptr,
-                       f->part_xyz[0].as<PartRec>(), ScatterOwnScan{});
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  OCTL_TRY(part_table_reserve(f, (size_t)p.nd * p.nst, 0, &p.tab_elems));
+  uint32_t* flag = f->bk_table.as<uint32_t>() + 2 * p.tab_elems;
+  HIP_TRY(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
+  p.bad_flag = reinterpret_cast<int32_t*>(flag);
+  p.out = f->part_xyz[0].as<PartRec>();
+  p.t_hist = "prefix_hist", p.t_scatter = "prefix_scatter";   // (prefix_hist: histogram and scan)
+  OCTL_TRY(partition_pass(f, p, bstart, bstride));
   *recs_out = f->part_xyz[0].p;
-  *bstart = table_dm;
-  *bstride = fused ? 1u : nst;   // (k_table_scan leaves the buckets' starts as a plain array)
   *bad_flag = flag;
   return OCTL_OK;
 }

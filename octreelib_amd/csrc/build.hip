@@ -1512,13 +1512,10 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
       ba.old_vcode = f->vcode_dev[0].as<uint64_t>();
       ba.old_voxels = f->n_voxels;
     }
-    BucketBuildGeom geom;
-    int done = 0, lv = 0;
-    int64_t ni = 0, nv = 0, nblk = 0, pending = 0;
-    std::vector<octl_forest::LevelSeg> segs;
-    OCTL_TRY(forest_bucket_build(f, ba, bt, &done, &segs, &ni, &lv, &nv, &nblk, &pending, &geom));
+    BucketBuildResult br;
+    OCTL_TRY(forest_bucket_build(f, ba, bt, &br));
     trace.mark("bucket build");
-    if (done && pending > 0) {
+    if (br.done && br.pending > 0) {
       // some voxels were left as single leaves (more than 4096 points, deeper than 6 levels, a point
       // outside its cube): the level loop subdivides exactly those roots, the rest of the build stands
       for (int b = 0; b < 2; ++b) {
@@ -1526,7 +1523,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
         OCTL_TRY(devbuf_reserve(ctx, f->pathbuf[b], (size_t)n_alive * 4));
       }
       LevelLoop L{f, &bt, K, 0, all_scheme, scheme_dev, ba.old_fc, ba.old_epoch, cur_epoch, max_depth, n_alive,
-                  true, 0, nv, 0, 0, &segs};
+                  true, 0, br.n_voxels, 0, 0, &br.segs};
       OCTL_TRY(run_level_loop(L));
       trace.mark("level loop (pending voxels)");
       if (L.n_internal > 0) {
@@ -1540,14 +1537,14 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
                            n_alive, f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>());
         HIP_TRY(ctx, hipGetLastError());
       }
-      ni += L.n_internal;
-      lv = std::max(lv, L.level);
+      br.n_internal += L.n_internal;
+      br.levels = std::max(br.levels, L.level);
       const int64_t n_ord_before = f->n_ord;
       f->n_ord = n_alive;
       OCTL_TRY(forest_make_blocks(f));
       uint32_t e = 0;
       OCTL_TRY(forest_finish_blocks(f, &e));
-      nblk = f->n_blocks;
+      br.n_blocks = f->n_blocks;
       if (e) {
         f->n_ord = n_ord_before;
         f->n_blocks = 0;
@@ -1557,27 +1554,27 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
                               "(the reference raises IndexError or picks a wrong child here)");
       }
     }
-    if (done) {
+    if (br.done) {
       f->cur ^= 1;
-      f->n_voxels = nv;
+      f->n_voxels = br.n_voxels;
       f->vkeys.clear();
       f->vkeys_stale = true;
-      f->vl_min[0] = geom.min[0]; f->vl_min[1] = geom.min[1]; f->vl_min[2] = geom.min[2];
-      f->vl_ny = geom.ny;
-      f->vl_nz = geom.nz;
-      f->level_segs.swap(segs);
+      f->vl_min[0] = br.geom.min[0]; f->vl_min[1] = br.geom.min[1]; f->vl_min[2] = br.geom.min[2];
+      f->vl_ny = br.geom.ny;
+      f->vl_nz = br.geom.nz;
+      f->level_segs.swap(br.segs);
       f->built = true;
       f->epoch = cur_epoch;
       f->n_ord = n_alive;
-      f->n_blocks = nblk;
-      f->n_internal = ni;
+      f->n_blocks = br.n_blocks;
+      f->n_internal = br.n_internal;
       // nodes inherit an older epoch only from a previous scheme that had internal nodes
       f->uniform_epoch = !(over_old && old_internal0 > 0);
-      f->max_depth_reached = lv;
+      f->max_depth_reached = br.levels;
       f->mask_valid = false;
       f->store_dirty = false;
       f->vcode_valid = false;
-      f->fast_order_valid = geom.order_done && pending == 0;
+      f->fast_order_valid = br.geom.order_done && br.pending == 0;
       // (count-driven from ALL poses: a leaf holds at most K points; what the level loop finished for the voxels left
       //  behind obeys the same rule)
       if (all_scheme && K >= 0) f->max_block_hint = K;
@@ -1586,12 +1583,12 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
       f->append_only = true;
       if (info) {
         info->n_points = n_alive;
-        info->n_voxels = nv;
+        info->n_voxels = br.n_voxels;
         info->n_nodes = bt.n;
-        info->n_internal = ni;
-        info->n_blocks = nblk;
-        info->max_depth = lv;
-        info->n_levels = lv;
+        info->n_internal = br.n_internal;
+        info->n_blocks = br.n_blocks;
+        info->max_depth = br.levels;
+        info->n_levels = br.levels;
       }
       return OCTL_OK;
     }

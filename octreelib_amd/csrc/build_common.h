@@ -28,8 +28,8 @@ static inline NodePtrs node_ptrs(NodeTable& t) {
 }
 
 // bucket_build.hip: complete build of a fresh forest (K-driven scheme or K < 0, no previous scheme) by
-// one MSD partition into buckets of consecutive voxels + one workgroup per bucket.  *done = 0 when
-// the path does not apply and the caller must run the general path.
+// one MSD partition into buckets of consecutive voxels + one workgroup per bucket (BucketBuildResult::done
+// = 0 when the path does not apply and the caller must run the general path).
 struct BucketBuildArgs {
   int64_t K;
   const uint8_t* scheme_dev;  // per pose slot: 1 = the pose drives the scheme; nullptr = all poses
@@ -47,10 +47,16 @@ struct BucketBuildGeom {  // decoding of the linear voxel keys: lin = ((qx-min0)
   uint64_t ny, nz;
   bool order_done = false;  // f->fast_order holds the blocks in the reference's listing order
 };
-// *pending = number of voxels left as single leaves for the level loop of build.hip (flagged roots).
-int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, int* done,
-                        std::vector<octl_forest::LevelSeg>* segs, int64_t* n_internal, int* levels,
-                        int64_t* n_voxels, int64_t* n_blocks, int64_t* pending, BucketBuildGeom* geom);
+struct BucketBuildResult {
+  int done = 0;  // 1: the build is complete; 0: the path does not apply, the caller runs the general one
+  std::vector<octl_forest::LevelSeg> segs;
+  int64_t n_internal = 0;
+  int levels = 0;
+  int64_t n_voxels = 0, n_blocks = 0;
+  int64_t pending = 0;  // voxels left as single leaves for the level loop of build.hip (flagged roots)
+  BucketBuildGeom geom;
+};
+int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, BucketBuildResult* r);
 
 // bucket_build.hip: one stable partition of a single cube's store by the child digits of its first pm levels
 // (records of 32 bytes: x, y, z f64 | six digits << 1 | bad | store index + scheme bit)

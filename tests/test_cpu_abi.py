@@ -254,3 +254,12 @@ def test_key_geometry_pads_the_box_and_divides_exactly():
     lib.octl_debug_key_geometry(C.cast(tb_a, C.c_void_p), 4096, 10_000_000, 2560, 1, C.cast(bb, C.c_void_p),
                                 C.byref(width), C.byref(nb), C.byref(valid), C.byref(bad))
     assert (width.value, nb.value, valid.value, bad.value) == (10, 3931, 1, 0)
+    # the largest single pass: the padded box has 256 x 256 x 255 keys (just under 2^24) in 4096 buckets of 4080 keys,
+    # a width that is no power of two
+    tb_a = (C.c_int32 * 6)(0, 0, 0, 253, 253, 252)
+    width, nb, valid, bad = C.c_uint32(0), C.c_uint32(0), C.c_int32(0), C.c_int64(-1)
+    rc = lib.octl_debug_key_geometry(C.cast(tb_a, C.c_void_p), 4096, 10_400_000, 2560, 1, C.cast(bb, C.c_void_p),
+                                     C.byref(width), C.byref(nb), C.byref(valid), C.byref(bad))
+    assert rc == 0
+    assert list(bb) == [-1, -1, -1, 254, 254, 253]
+    assert (width.value, nb.value, valid.value, bad.value) == (4080, 4096, 1, 0)
