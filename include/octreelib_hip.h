@@ -290,6 +290,35 @@ int octl_forest_point_to_plane(octl_forest* f, const double* xyz, int64_t n, int
 int octl_forest_point_to_plane_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t min_points,
                                       double max_variance, int32_t* node_dev, int32_t* row_dev,
                                       double* distance_dev);
+/* The point-to-plane normal equations of a scan against the pooled leaf planes, for ONE rigid transform: what a
+ * Gauss-Newton step of scan-to-map registration needs from the device (the 6x6 solve and the iteration are the
+ * caller's; octreelib_amd/registration.py has them and the NumPy definition of every number below).  T = row-major
+ * 3x4 (R | t), origin = c.  Per query q: p_i = ((R_i0 q_x + R_i1 q_y) + R_i2 q_z) + t_i with every product and sum
+ * rounded to f64 (no fma); node, row and r = residual of p exactly as octl_forest_point_to_plane answers them (same
+ * state rules and OCTL_E_STATE messages); the point is USED iff row >= 0, r is finite and (max_distance < 0 or |r| <=
+ * max_distance).  With d = p - c, J = [d x n, n] (the derivative of r under p <- Rot(w)(p - c) + c + v, xi = (w, v))
+ * and the weight w = 1, or for huber_delta > 0: 1 if |r| <= delta else delta / |r|:
+ *   sys[0..21)  = upper triangle of H = sum w J J^T, row-major (00, 01, ..., 05, 11, ...),
+ *   sys[21..27) = g = sum w J r,  sys[27] = cost = sum rho(r), rho = r^2 / 2 or delta (|r| - delta / 2) beyond delta,
+ *   counts[0] = used points, counts[1] = located points (node >= 0).
+ * Unused points are skipped (a NaN or inf query never reaches a sum).  node / row / residual: all three NULL, or all
+ * three given and then written for every query.  The sums are reduced in a fixed tree that depends on n alone (chunks
+ * of 4096 queries; no floating-point atomics): the same call gives the same bits on any device and in either form.
+ * With eps = 2^-53 and D = 34 + ceil(ceil(n / 4096) / 256) every entry is within (D + 8) eps sum |term| of the exact
+ * sum of the terms formed from p, r and the table's plane bits.  n = 0: no launch, sys = +0.0, counts = 0.
+ * OCTL_E_INVALID: n >= 2^31, a NULL pointer, a non-finite T or origin (checked before anything runs).  Two kernels;
+ * the host form adds one upload, the downloads and one wait.  Read-only.  No reference counterpart.                 */
+int octl_forest_registration_system(octl_forest* f, const double* xyz, int64_t n, const double T[12],
+                                    const double origin[3], int32_t min_points, double max_variance,
+                                    double max_distance, double huber_delta, double sys[28], int64_t counts[2],
+                                    int32_t* node, int32_t* row, double* residual);
+/* The same with pointers from octl_dev_alloc (T and origin stay host arrays); no host wait.  n = 0: sys_dev and
+ * counts_dev are zeroed by two fills.  No reference counterpart.                                                    */
+int octl_forest_registration_system_device(octl_forest* f, const double* xyz_dev, int64_t n, const double T[12],
+                                           const double origin[3], int32_t min_points, double max_variance,
+                                           double max_distance, double huber_delta, double* sys_dev,
+                                           int64_t* counts_dev, int32_t* node_dev, int32_t* row_dev,
+                                           double* residual_dev);
 /* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
 int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 

@@ -650,6 +650,91 @@ class Forest:
         self.ctx.check(self.lib.octl_forest_point_to_plane_device(self.handle, xyz_dptr, int(n), int(min_points), mv,
                                                                   node_dptr, row_dptr, dist_dptr))
 
+    # -- registration (octreelib_amd/registration.py is the host definition) ------------------------------------------
+    @staticmethod
+    def _reg_args(transform, origin, max_variance, max_distance, huber_delta):
+        from octreelib_amd.registration import _as_origin, as_transform
+
+        R, t = as_transform(transform)
+        T12 = np.ascontiguousarray(np.concatenate([R, t[:, None]], axis=1))
+        c = np.ascontiguousarray(_as_origin(origin))
+        mv = -1.0 if max_variance is None else float(max_variance)
+        md = -1.0 if max_distance is None else float(max_distance)
+        hd = 0.0 if huber_delta is None else float(huber_delta)
+        return T12, c, mv, md, hd
+
+    def registration_system(self, points, transform=None, origin=None, slots=None, min_points: int = 8,
+                            max_variance=None, max_distance=None, huber_delta=None, per_point: bool = False):
+        """The point-to-plane normal equations of a scan under `transform` (octl_forest_registration_system: two
+        kernels, one host wait); origin None: the centroid of the transformed scan.  per_point: the answers
+        point_to_plane gives for the transformed scan come back with the system."""
+        from octreelib_amd.query import _as_queries
+        from octreelib_amd.registration import default_origin, system_from_sums
+
+        pts = _as_queries(points)
+        planes = self.leaf_planes(slots)
+        if origin is None:
+            origin = default_origin(transform, pts)
+        T12, c, mv, md, hd = self._reg_args(transform, origin, max_variance, max_distance, huber_delta)
+        n = len(pts)
+        sums = np.empty(28, dtype=np.float64)
+        counts = np.empty(2, dtype=np.int64)
+        node = np.empty(n, dtype=np.int32) if per_point else None
+        row = np.empty(n, dtype=np.int32) if per_point else None
+        res = np.empty(n, dtype=np.float64) if per_point else None
+        self.ctx.check(self.lib.octl_forest_registration_system(
+            self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), int(min_points), mv, md, hd, nat.ptr(sums),
+            nat.ptr(counts), nat.ptr(node), nat.ptr(row), nat.ptr(res)))
+        out = system_from_sums(sums, counts, c)
+        if per_point:
+            out.node, out.row, out.residual, out.planes = node, row, res, planes
+        return out
+
+    def registration_system_device(self, xyz_dptr, n: int, transform, origin, sys_dptr, counts_dptr, node_dptr=None,
+                                   row_dptr=None, residual_dptr=None, min_points: int = 8, max_variance=None,
+                                   max_distance=None, huber_delta=None):
+        """registration_system against the pooled table the device holds (leaf_planes first), device pointers in and
+        out (28 f64 and 2 i64); the host does not wait."""
+        T12, c, mv, md, hd = self._reg_args(transform, origin, max_variance, max_distance, huber_delta)
+        self.ctx.check(self.lib.octl_forest_registration_system_device(
+            self.handle, xyz_dptr, int(n), nat.ptr(T12), nat.ptr(c), int(min_points), mv, md, hd, sys_dptr,
+            counts_dptr, node_dptr, row_dptr, residual_dptr))
+
+    def align(self, points, initial=None, slots=None, min_points: int = 8, max_variance=None, max_distance=None,
+              huber_delta=None, max_iterations: int = 20, tolerance: float = 1e-9, damping: float = 0.0):
+        """Gauss-Newton scan-to-map alignment (registration.align_np): the pooled planes are made once, the scan is
+        uploaded once, and every iteration is the device form on the resident scan plus one download of the 28 + 2
+        numbers (two launches, one host wait, whatever the size of the scan); the 6x6 solve runs on the host."""
+        from octreelib_amd.query import _as_queries
+        from octreelib_amd.registration import align_np, default_origin, system_from_sums
+
+        pts = _as_queries(points)
+        self.leaf_planes(slots)
+        n = len(pts)
+        lib, h = self.lib, self.ctx.handle
+        scan, out = C.c_void_p(), C.c_void_p()
+        self.ctx.check(lib.octl_dev_alloc(h, max(pts.nbytes, 8), C.byref(scan)))
+        try:
+            self.ctx.check(lib.octl_dev_alloc(h, 256, C.byref(out)))
+            if n:
+                self.ctx.check(lib.octl_dev_upload(h, scan, nat.ptr(pts), pts.nbytes))
+            counts_dptr = C.c_void_p(out.value + 28 * 8)
+            buf = np.empty(30, dtype=np.float64)
+
+            def system(T, origin):
+                if origin is None:
+                    origin = default_origin(T, pts)
+                self.registration_system_device(scan, n, T, origin, out, counts_dptr, None, None, None, min_points,
+                                                max_variance, max_distance, huber_delta)
+                self.ctx.check(lib.octl_dev_download(h, nat.ptr(buf), out, buf.nbytes))
+                return system_from_sums(buf[:28].copy(), buf[28:].view(np.int64), origin)
+
+            return align_np(system, initial, max_iterations, tolerance, damping)
+        finally:
+            lib.octl_dev_free(h, scan)    # (back to the context's pool: no hipFree on the scan path)
+            if out.value:
+                lib.octl_dev_free(h, out)
+
     @property
     def perm(self) -> np.ndarray:
         """perm[i] = index (in the concatenation of all pose clouds, slot order) of the point at

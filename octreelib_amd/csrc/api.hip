@@ -142,7 +142,7 @@ void octl_forest_destroy(octl_forest* f) {
         &f->entries, &f->split[0], &f->split[1], &f->split_tiles[0], &f->split_tiles[1],
         &f->child_sc, &f->pose_off_dev, &f->scheme_dev, &f->root_up, &f->vlin_dev, &f->vcode_dev[0],
         &f->vcode_dev[1], &f->split_lambda, &f->split_n, &f->pl_rows, &f->pl_plane, &f->pl_node_row, &f->pl_sort,
-        &f->pl_hist, &f->q_stage})
+        &f->pl_hist, &f->q_stage, &f->rg_rows})
     devbuf_release(f->ctx, *b);
   delete f;
 }

@@ -120,6 +120,7 @@ struct octl_forest {
   int64_t pl_n = 0, pl_cap = 0;
   std::vector<uint8_t> pl_sel;  // the pose selection of that call (empty: every pose)
   DevBuf q_stage;               // staging of the host forms of the queries (points in, answers out)
+  DevBuf rg_rows;               // octl_forest_registration_system (register.hip): per-chunk partial sums, the result
 
   // leaf-ordered arrays of the last build
   DevBuf ord_idx;    // u32 [n_ord] store index of the point at storage position i

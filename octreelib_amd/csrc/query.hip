@@ -17,43 +17,9 @@
 
 #include "common.h"
 #include "forest.h"
-#include "scheme_walk.h"
+#include "query_walk.h"
 
 namespace {
-
-struct QueryTables {
-  int mode;
-  double L;
-  VoxOrg org;
-  const uint64_t* vcode;
-  int64_t V;
-  const int32_t* first_child;
-  const double* corner;
-  const double* edge;
-};
-
-struct PlaneTable {
-  const int32_t* node_row;  // [n_nodes] row of the pooled table, -1: the leaf holds no pooled point
-  const double2* rows;      // [n_rows][4]: {nx, ny}, {nz, mx}, {my, mz}, {lambda0, count}
-  int32_t min_points;
-  double max_variance;      // < 0: no variance test
-};
-
-__device__ __forceinline__ int32_t locate_one(const QueryTables& t, double px, double py, double pz) {
-  if (t.V <= 0) return -1;  // (a forest without points has no root)
-  if (t.mode == 1) {
-    // a single cube has no voxel to miss: a point outside it (or not finite) has no leaf, whether or not the root
-    // is split (the walk itself only looks at the cubes of split nodes, as the insertion does)
-    const double e = t.edge[0];
-    const double ax = px - t.corner[0], ay = py - t.corner[1], az = pz - t.corner[2];
-    if (!((ax >= 0.0) && (ax < e) && (ay >= 0.0) && (ay < e) && (az >= 0.0) && (az < e))) return -1;
-  }
-  int32_t node = -1;
-  uint64_t code = 0;
-  const int status = scheme_walk(px, py, pz, t.mode, t.L, t.org, t.vcode, t.V, t.first_child, t.corner, t.edge, &node,
-                                 &code);
-  return status == WALK_LEAF ? node : -1;
-}
 
 template <bool PLANE>
 __global__ __launch_bounds__(256) void k_query(const double* __restrict__ xyz, int64_t n, QueryTables t, PlaneTable pt,
@@ -65,60 +31,13 @@ __global__ __launch_bounds__(256) void k_query(const double* __restrict__ xyz, i
     const int32_t node = locate_one(t, px, py, pz);
     node_out[i] = node;
     if (PLANE) {
-      int32_t row = node >= 0 ? pt.node_row[node] : -1;
-      double d = __longlong_as_double(0x7ff8000000000000ll);
-      if (row >= 0) {
-        const double2* r = pt.rows + 4 * (int64_t)row;
-        const double2 a = r[0], b = r[1], c = r[2], w = r[3];
-        const bool keep = w.y >= (double)pt.min_points && !(pt.max_variance >= 0.0 && w.x > pt.max_variance);
-        if (keep) {
-          const double dx = px - b.y, dy = py - c.x, dz = pz - c.y;
-          d = fma(a.x, dx, fma(a.y, dy, b.x * dz));
-        } else {
-          row = -1;
-        }
-      }
+      int32_t row;
+      double nrm[3];
+      const double d = plane_residual(pt, node, px, py, pz, &row, nrm);
       row_out[i] = row;
       dist_out[i] = d;
     }
   }
-}
-
-// what every query starts with: the forest is settled, built, and its voxel codes are on the device
-int query_begin(octl_forest* f, const char* what, QueryTables* t) {
-  OCTL_TRY(forest_settle(f));
-  octl_ctx* ctx = f->ctx;
-  if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "%s before build", what);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  OCTL_TRY(forest_sync_vcodes(f));
-  const NodeTable& nt = f->nodes[f->cur];
-  t->mode = f->mode;
-  t->L = f->edge;
-  t->org = f->vorg;
-  t->vcode = f->vcode_dev[0].as<uint64_t>();
-  t->V = f->n_voxels;
-  t->first_child = nt.first_child.as<int32_t>();
-  t->corner = nt.corner.as<double>();
-  t->edge = nt.edge.as<double>();
-  return OCTL_OK;
-}
-
-int plane_table(octl_forest* f, int32_t min_points, double max_variance, PlaneTable* pt) {
-  octl_ctx* ctx = f->ctx;
-  if (!f->pooled_valid) {
-    if (!f->pl_node_row.p)
-      return octl_set_error(ctx, OCTL_E_STATE,
-                            "point_to_plane: the forest has no pooled leaf planes (call octl_forest_pooled_leaf_stats "
-                            "first)");
-    return octl_set_error(ctx, OCTL_E_STATE,
-                          "point_to_plane: the pooled leaf planes are stale - the forest's contents or scheme changed "
-                          "after octl_forest_pooled_leaf_stats made them");
-  }
-  pt->node_row = f->pl_node_row.as<int32_t>();
-  pt->rows = f->pl_plane.as<double2>();
-  pt->min_points = min_points;
-  pt->max_variance = max_variance >= 0.0 ? max_variance : -1.0;
-  return OCTL_OK;
 }
 
 template <bool PLANE>
@@ -155,9 +74,45 @@ int query_host(octl_forest* f, const char* name, const double* xyz, int64_t n, c
   return OCTL_OK;
 }
 
-bool bad_count(int64_t n) { return n < 0 || n >= ((int64_t)1 << 31); }
-
 }  // namespace
+
+// (query_walk.h: shared with register.hip)
+int query_begin(octl_forest* f, const char* what, QueryTables* t) {
+  OCTL_TRY(forest_settle(f));
+  octl_ctx* ctx = f->ctx;
+  if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "%s before build", what);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  OCTL_TRY(forest_sync_vcodes(f));
+  const NodeTable& nt = f->nodes[f->cur];
+  t->mode = f->mode;
+  t->L = f->edge;
+  t->org = f->vorg;
+  t->vcode = f->vcode_dev[0].as<uint64_t>();
+  t->V = f->n_voxels;
+  t->first_child = nt.first_child.as<int32_t>();
+  t->corner = nt.corner.as<double>();
+  t->edge = nt.edge.as<double>();
+  return OCTL_OK;
+}
+
+int query_plane_table(octl_forest* f, const char* what, int32_t min_points, double max_variance, PlaneTable* pt) {
+  octl_ctx* ctx = f->ctx;
+  if (!f->pooled_valid) {
+    if (!f->pl_node_row.p)
+      return octl_set_error(ctx, OCTL_E_STATE,
+                            "%s: the forest has no pooled leaf planes (call octl_forest_pooled_leaf_stats first)",
+                            what);
+    return octl_set_error(ctx, OCTL_E_STATE,
+                          "%s: the pooled leaf planes are stale - the forest's contents or scheme changed after "
+                          "octl_forest_pooled_leaf_stats made them",
+                          what);
+  }
+  pt->node_row = f->pl_node_row.as<int32_t>();
+  pt->rows = f->pl_plane.as<double2>();
+  pt->min_points = min_points;
+  pt->max_variance = max_variance >= 0.0 ? max_variance : -1.0;
+  return OCTL_OK;
+}
 
 extern "C" {
 
@@ -165,7 +120,8 @@ int octl_forest_locate(octl_forest* f, const double* xyz, int64_t n, int32_t* no
   if (!f) return OCTL_E_INVALID;
   QueryTables t;
   OCTL_TRY(query_begin(f, "locate", &t));
-  if (bad_count(n) || (n > 0 && (!xyz || !node))) return octl_set_error(f->ctx, OCTL_E_INVALID, "bad locate arguments");
+  if (query_bad_count(n) || (n > 0 && (!xyz || !node)))
+    return octl_set_error(f->ctx, OCTL_E_INVALID, "bad locate arguments");
   if (n == 0) return OCTL_OK;
   return query_host<false>(f, "locate", xyz, n, t, PlaneTable{}, node, nullptr, nullptr);
 }
@@ -175,7 +131,7 @@ int octl_forest_locate_device(octl_forest* f, const double* xyz_dev, int64_t n, 
   QueryTables t;
   OCTL_TRY(query_begin(f, "locate", &t));
   octl_ctx* ctx = f->ctx;
-  if (bad_count(n) || (n > 0 && (!xyz_dev || !node_dev)))
+  if (query_bad_count(n) || (n > 0 && (!xyz_dev || !node_dev)))
     return octl_set_error(ctx, OCTL_E_INVALID, "bad locate arguments");
   if (n == 0) return OCTL_OK;
   // (the points may be the target of an octl_dev_upload_async that is still in flight: ordered on the device)
@@ -189,8 +145,8 @@ int octl_forest_point_to_plane(octl_forest* f, const double* xyz, int64_t n, int
   QueryTables t;
   OCTL_TRY(query_begin(f, "point_to_plane", &t));
   PlaneTable pt;
-  OCTL_TRY(plane_table(f, min_points, max_variance, &pt));
-  if (bad_count(n) || (n > 0 && (!xyz || !node || !row || !distance)))
+  OCTL_TRY(query_plane_table(f, "point_to_plane", min_points, max_variance, &pt));
+  if (query_bad_count(n) || (n > 0 && (!xyz || !node || !row || !distance)))
     return octl_set_error(f->ctx, OCTL_E_INVALID, "bad point_to_plane arguments");
   if (n == 0) return OCTL_OK;
   return query_host<true>(f, "point_to_plane", xyz, n, t, pt, node, row, distance);
@@ -204,8 +160,8 @@ int octl_forest_point_to_plane_device(octl_forest* f, const double* xyz_dev, int
   OCTL_TRY(query_begin(f, "point_to_plane", &t));
   octl_ctx* ctx = f->ctx;
   PlaneTable pt;
-  OCTL_TRY(plane_table(f, min_points, max_variance, &pt));
-  if (bad_count(n) || (n > 0 && (!xyz_dev || !node_dev || !row_dev || !distance_dev)))
+  OCTL_TRY(query_plane_table(f, "point_to_plane", min_points, max_variance, &pt));
+  if (query_bad_count(n) || (n > 0 && (!xyz_dev || !node_dev || !row_dev || !distance_dev)))
     return octl_set_error(ctx, OCTL_E_INVALID, "bad point_to_plane arguments");
   if (n == 0) return OCTL_OK;
   OCTL_TRY(ctx_wait_uploads(ctx, xyz_dev, (size_t)n * 24));

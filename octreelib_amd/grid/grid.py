@@ -19,6 +19,7 @@ from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, Visualization
 from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.query import HostMap, LeafPlanes, PointToPlane
+from octreelib_amd.registration import Alignment, RegistrationSystem
 
 __all__ = ["Grid", "GridConfig"]
 
@@ -144,6 +145,38 @@ class Grid(GridBase):
         if self._plug is not None:
             return self._host_map().point_to_plane(points, sel, min_points, max_variance)
         return self._forest.point_to_plane(points, sel, min_points, max_variance)
+
+    def registration_system(self, points, transform=None, pose_numbers: Optional[List[int]] = None,
+                            min_points: int = 8, max_variance: Optional[float] = None,
+                            max_distance: Optional[float] = None, huber_delta: Optional[float] = None, origin=None,
+                            per_point: bool = False) -> RegistrationSystem:
+        """The point-to-plane normal equations of a scan under `transform` (4x4 or 3x4, None: identity) against the
+        pooled leaf planes: a RegistrationSystem (H 6x6, g, cost, n_used, n_located, origin) for the left update
+        p <- Rot(w)(p - origin) + origin + v; .solve() is the Gauss-Newton step.  Gates as point_to_plane, plus
+        max_distance (points with a larger |residual| are not used) and huber_delta (Huber weights); origin None: the
+        centroid of the transformed scan; per_point: node / row / residual of every point come back too.  Two kernels
+        and one host wait (octreelib_amd/registration.py has the definition)."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().registration_system(points, transform, sel, min_points, max_variance,
+                                                        max_distance, huber_delta, origin, per_point)
+        return self._forest.registration_system(points, transform, origin, sel, min_points, max_variance,
+                                                max_distance, huber_delta, per_point)
+
+    def align(self, points, initial=None, pose_numbers: Optional[List[int]] = None, min_points: int = 8,
+              max_variance: Optional[float] = None, max_distance: Optional[float] = None,
+              huber_delta: Optional[float] = None, max_iterations: int = 20, tolerance: float = 1e-9,
+              damping: float = 0.0) -> Alignment:
+        """Gauss-Newton alignment of a scan to the map, from `initial` (None: identity): an Alignment (transform 4x4,
+        iterations, converged, costs, n_used, reason).  The planes are made once and the scan is uploaded once; an
+        iteration is two kernels, a 240-byte download and a 6x6 solve on the host.  Ends when |xi| < tolerance, at
+        max_iterations, or - not converged, last good transform - when fewer than six points are used."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().align(points, initial, sel, min_points, max_variance, max_distance, huber_delta,
+                                          max_iterations, tolerance, damping)
+        return self._forest.align(points, initial, sel, min_points, max_variance, max_distance, huber_delta,
+                                  max_iterations, tolerance, damping)
 
     def node_cubes(self):
         """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""

@@ -112,6 +112,21 @@ class Octree(OctreeBase, Generic[T]):
         self._query_ready()
         return self._forest.point_to_plane(points, None, min_points, max_variance)
 
+    def registration_system(self, points, transform=None, min_points: int = 8, max_variance=None, max_distance=None,
+                            huber_delta=None, origin=None, per_point: bool = False):
+        """The point-to-plane normal equations of a scan under `transform` against the leaf planes (a
+        RegistrationSystem; Grid.registration_system describes it)."""
+        self._query_ready()
+        return self._forest.registration_system(points, transform, origin, None, min_points, max_variance,
+                                                max_distance, huber_delta, per_point)
+
+    def align(self, points, initial=None, min_points: int = 8, max_variance=None, max_distance=None, huber_delta=None,
+              max_iterations: int = 20, tolerance: float = 1e-9, damping: float = 0.0):
+        """Gauss-Newton alignment of a scan to the leaf planes (an Alignment; Grid.align describes it)."""
+        self._query_ready()
+        return self._forest.align(points, initial, None, min_points, max_variance, max_distance, huber_delta,
+                                  max_iterations, tolerance, damping)
+
     def node_cubes(self):
         """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""
         self._query_ready()

@@ -198,7 +198,7 @@ def node_table_from_leaves(roots, leaves):
 
 
 class HostMap:
-    """The three queries over trees that are only known through their leaves (the classes on the caller's own plug
+    """The queries over trees that are only known through their leaves (the classes on the caller's own plug
     types): a node table rebuilt from the leaves (node_table_from_leaves) and the host definitions above.  mode /
     edge as locate_np; roots: [(corner, edge)] in voxel order; leaves_by_pose: {pose: leaves, empty ones included}
     in the order the poses were inserted, a leaf being anything with corner_min, edge_length and get_points()."""
@@ -230,3 +230,20 @@ class HostMap:
         node = self.locate(points)
         row, dist = point_to_plane_np(node, planes, points, min_points, max_variance)
         return PointToPlane(node, row, dist, planes)
+
+    def registration_system(self, points, transform=None, pose_numbers=None, min_points=8, max_variance=None,
+                            max_distance=None, huber_delta=None, origin=None, per_point=False):
+        from octreelib_amd.registration import registration_system_np
+
+        return registration_system_np(self.locate, self.leaf_planes(pose_numbers), points, transform, origin,
+                                      min_points, max_variance, max_distance, huber_delta, per_point=per_point)
+
+    def align(self, points, initial=None, pose_numbers=None, min_points=8, max_variance=None, max_distance=None,
+              huber_delta=None, max_iterations=20, tolerance=1e-9, damping=0.0):
+        from octreelib_amd.registration import align_np, registration_system_np
+
+        planes = self.leaf_planes(pose_numbers)     # (once: the map does not change while a scan is aligned)
+        pts = _as_queries(points)
+        system = lambda T, c: registration_system_np(self.locate, planes, pts, T, c, min_points, max_variance,
+                                                     max_distance, huber_delta)
+        return align_np(system, initial, max_iterations, tolerance, damping)

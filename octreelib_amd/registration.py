@@ -1,0 +1,215 @@
+"""
+Scan-to-map registration against the pooled leaf planes: the point-to-plane normal equations of a scan under a rigid
+transform (registration_system), and the Gauss-Newton loop over them (align).
+
+The device reduces a scan to the 6x6 system - 28 sums and two counts (octl_forest_registration_system, csrc/
+register.hip); the solve, the pose update and the loop are NumPy on the host (one download of 240 bytes per iteration).
+registration_system_np is the same on the host: the specification, the higher-precision reference of the tests, and
+what the classes built on the caller's own plug types run through query.HostMap.
+
+Per query q, with the transform T = (R, t) and an origin c:
+  p_i  = ((R_i0 q_x + R_i1 q_y) + R_i2 q_z) + t_i        every product and sum rounded to f64 (transform_np)
+  node = locate(p); row, r = point_to_plane(p)            the existing queries, same gates
+  used = row >= 0 and r finite and (max_distance is None or |r| <= max_distance)
+  d = p - c,  J = [d x n, n]                              dr/dxi under p <- Rot(w)(p - c) + c + v, xi = (w, v)
+  w = 1, or with Huber: 1 if |r| <= delta else delta / |r|
+  H = sum w J J^T,  g = sum w J r,  cost = sum rho(r)     rho = r^2 / 2, or delta (|r| - delta / 2) beyond delta
+over the used points only (they are selected, not weighted by zero: a NaN query never reaches a sum).
+"""
+
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional
+
+import numpy as np
+
+from octreelib_amd.query import LeafPlanes, _as_queries, point_to_plane_np
+
+__all__ = ["RegistrationSystem", "Alignment", "as_transform", "transform_np", "default_origin", "se3_exp",
+           "system_from_sums", "registration_system_np", "align_np"]
+
+_TRIU = np.triu_indices(6)
+
+
+@dataclass
+class RegistrationSystem:
+    """The normal equations of one transform.  node / row / residual / planes: the per-point answers (those of
+    point_to_plane for the transformed scan) when they were asked for, None otherwise."""
+
+    H: np.ndarray            # (6, 6) symmetric
+    g: np.ndarray            # (6,)
+    cost: float
+    n_used: int
+    n_located: int
+    origin: np.ndarray       # (3,)
+    node: Optional[np.ndarray] = None
+    row: Optional[np.ndarray] = None
+    residual: Optional[np.ndarray] = None
+    planes: Optional[LeafPlanes] = None
+
+    def solve(self, damping: float = 0.0) -> np.ndarray:
+        """xi = -(H + damping diag(H))^-1 g; ValueError when fewer than six points were used."""
+        if self.n_used < 6:
+            raise ValueError(f"registration system of {self.n_used} points: at least 6 are needed")
+        H = np.asarray(self.H, dtype=np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):     # (sums that overflowed give a non-finite step)
+            A = H + float(damping) * np.diag(np.diag(H))
+            return -np.linalg.solve(A, np.asarray(self.g, dtype=np.float64))
+
+
+@dataclass
+class Alignment:
+    transform: np.ndarray    # (4, 4)
+    iterations: int
+    converged: bool
+    costs: List[float] = field(default_factory=list)   # cost of every system that was solved
+    n_used: int = 0          # points used by the last system
+    reason: str = ""
+
+
+def as_transform(transform):
+    """(R (3, 3), t (3,)) f64 of a 4x4 or 3x4 rigid transform (None: the identity); ValueError otherwise."""
+    if transform is None:
+        return np.eye(3), np.zeros(3)
+    a = np.asarray(transform, dtype=np.float64)
+    if a.shape == (4, 4):
+        if not np.array_equal(a[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("the last row of a 4x4 transform must be (0, 0, 0, 1)")
+        a = a[:3]
+    if a.shape != (3, 4):
+        raise ValueError(f"expected a 4x4 or 3x4 transform, got shape {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError("the transform is not finite")
+    return np.ascontiguousarray(a[:, :3]), np.ascontiguousarray(a[:, 3])
+
+
+def _as_origin(origin) -> np.ndarray:
+    c = np.asarray(origin, dtype=np.float64).reshape(-1)
+    if c.shape != (3,) or not np.all(np.isfinite(c)):
+        raise ValueError("the origin must be three finite numbers")
+    return c
+
+
+def _matrix(R, t) -> np.ndarray:
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    return T
+
+
+def transform_np(transform, points) -> np.ndarray:
+    """p_i = ((R_i0 q_x + R_i1 q_y) + R_i2 q_z) + t_i in f64, one rounding per product and per sum, in this order:
+    the bits the device forms (no fused multiply-add on either side)."""
+    R, t = as_transform(transform)
+    q = _as_queries(points)
+    with np.errstate(invalid="ignore", over="ignore"):
+        cols = [((R[i, 0] * q[:, 0] + R[i, 1] * q[:, 1]) + R[i, 2] * q[:, 2]) + t[i] for i in range(3)]
+    return np.ascontiguousarray(np.stack(cols, axis=1)) if len(q) else np.empty((0, 3))
+
+
+def default_origin(transform, points) -> np.ndarray:
+    """Centroid of the transformed scan over its finite points (zeros when there is none): what align fixes as the
+    origin at its first iteration.  At UTM magnitudes d = p would let the rotational block of H swamp the rest.  A
+    finite but absurd coordinate (1e300) moves the centroid with it: such a scan wants cleaning, or an origin."""
+    p = transform_np(transform, points)
+    ok = np.all(np.isfinite(p), axis=1)
+    return p[ok].mean(axis=0) if ok.any() else np.zeros(3)
+
+
+def se3_exp(xi, origin=None) -> np.ndarray:
+    """4x4 of the update p <- Rot(w)(p - c) + c + v for xi = (w, v): Rodrigues' formula about the origin c."""
+    xi = np.asarray(xi, dtype=np.float64).reshape(6)
+    c = np.zeros(3) if origin is None else _as_origin(origin)
+    w, v = xi[:3], xi[3:]
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:     # (sin th / th and (1 - cos th) / th^2 by their series: exact to f64 below this angle)
+        a, b = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0
+    else:
+        a, b = np.sin(th) / th, (1.0 - np.cos(th)) / (th * th)
+    R = np.eye(3) + a * K + b * (K @ K)
+    return _matrix(R, c - R @ c + v)
+
+
+def system_from_sums(sums, counts, origin) -> RegistrationSystem:
+    """RegistrationSystem of the 28 sums (21 of H's upper triangle row-major, 6 of g, the cost) and the two counts."""
+    s = np.asarray(sums).reshape(28)
+    H = np.zeros((6, 6), dtype=s.dtype)
+    H[_TRIU] = s[:21]
+    H = H + np.triu(H, 1).T
+    return RegistrationSystem(H, s[21:27].copy(), s[27], int(counts[0]), int(counts[1]),
+                              np.array(origin, dtype=np.float64))
+
+
+def registration_system_np(locate: Callable, planes: LeafPlanes, points, transform=None, origin=None,
+                           min_points: int = 8, max_variance: Optional[float] = None,
+                           max_distance: Optional[float] = None, huber_delta: Optional[float] = None,
+                           dtype=np.float64, answers=None, per_point: bool = False) -> RegistrationSystem:
+    """The definition (module docstring), on the host.  locate: points (n, 3) -> node ids (HostMap.locate, or
+    locate_np over downloaded tables); planes: the pooled table.  origin None: default_origin.  The sums are formed in
+    `dtype` (np.longdouble for a reference of higher precision) from p, r and the table's own bits.  answers = (node,
+    row, residual): take these per-point answers as given instead of forming them here - the reference of a sum over
+    exactly the terms another implementation selected."""
+    R, t = as_transform(transform)
+    T = _matrix(R, t)
+    q = _as_queries(points)
+    p = transform_np(T, q)
+    c = default_origin(T, q) if origin is None else _as_origin(origin)
+    if answers is None:
+        node = np.asarray(locate(p), dtype=np.int32) if len(p) else np.empty(0, dtype=np.int32)
+        row, r = point_to_plane_np(node, planes, p, min_points, max_variance)
+    else:
+        node, row, r = (np.asarray(a) for a in answers)
+    with np.errstate(invalid="ignore"):
+        used = (row >= 0) & np.isfinite(r)
+        if max_distance is not None and max_distance >= 0:
+            used &= ~(np.abs(r) > max_distance)
+    with np.errstate(invalid="ignore", over="ignore"):      # (a wild origin overflows; the sums say so)
+        rr = np.asarray(r, dtype=np.float64)[used].astype(dtype)
+        nrm = (np.asarray(planes.normal, dtype=np.float64)[row[used]].astype(dtype) if used.any()
+               else np.zeros((0, 3), dtype))
+        d = p[used].astype(dtype) - c.astype(dtype)
+        J = np.concatenate([np.cross(d, nrm).reshape(-1, 3), nrm], axis=1)
+        ar = np.abs(rr)
+        w = np.ones(len(rr), dtype=dtype)
+        rho = rr * rr / 2
+        if huber_delta is not None and huber_delta > 0:
+            dl = dtype(huber_delta)
+            tail = ar > dl
+            w[tail] = dl / ar[tail]
+            rho[tail] = dl * (ar[tail] - dl / 2)
+        wJ = J * w[:, None]
+        H = wJ.T @ J
+        g = (wJ * rr[:, None]).sum(axis=0)
+    out = RegistrationSystem(np.asarray(H, dtype=dtype).reshape(6, 6), g, rho.sum(dtype=dtype), int(used.sum()),
+                             int((node >= 0).sum()), c)
+    if per_point:
+        out.node, out.row, out.residual, out.planes = node, row, r, planes
+    return out
+
+
+def align_np(system: Callable, initial=None, max_iterations: int = 20, tolerance: float = 1e-9,
+             damping: float = 0.0) -> Alignment:
+    """Gauss-Newton over system(T (4, 4), origin or None) -> RegistrationSystem.  The first call passes origin None
+    and the origin that system chose (RegistrationSystem.origin) is kept for the rest of the run.  Per iteration:
+    xi = system.solve(damping), T <- se3_exp(xi, origin) T.  Ends converged when |xi| < tolerance; otherwise at
+    max_iterations, or - with the last good transform - when fewer than six points are used ("no correspondences")
+    or the system cannot be solved ("singular system")."""
+    R, t = as_transform(initial)
+    T = _matrix(R, t)
+    costs, origin, n_used = [], None, 0
+    for it in range(int(max_iterations)):
+        s = system(T, origin)
+        origin, n_used = s.origin, s.n_used
+        if s.n_used < 6:
+            return Alignment(T, it, False, costs, n_used, "no correspondences")
+        try:
+            xi = s.solve(damping)
+        except np.linalg.LinAlgError:
+            xi = None
+        if xi is None or not np.all(np.isfinite(xi)):   # (also sums that overflowed: an origin at 1e300, say)
+            return Alignment(T, it, False, costs, n_used, "singular system")
+        costs.append(float(s.cost))
+        T = se3_exp(xi, origin) @ T
+        T[3] = [0.0, 0.0, 0.0, 1.0]
+        if float(np.linalg.norm(xi)) < tolerance:
+            return Alignment(T, it + 1, True, costs, n_used, "converged")
+    return Alignment(T, int(max_iterations), False, costs, n_used, "max_iterations")
