@@ -309,6 +309,11 @@ struct __attribute__((aligned(32))) PartRec {
 // The child digits are computed by the partition kernel, whose waves otherwise wait for their
 // scattered stores: the arithmetic is free there, in the bucket kernel it was a third of the VALU work.
 constexpr int PATH_EAGER = 6;          // child digits carried by the record; deeper ones on demand
+// (build.hip reads the records of forest_prefix_partition by the constants of build_common.h)
+static_assert(sizeof(PartRec) == PART_REC_BYTES && offsetof(PartRec, vp) == 4 * PART_REC_VP_WORD &&
+                  offsetof(PartRec, idx) == 4 * PART_REC_IDX_WORD,
+              "PartRec and the record layout of build_common.h");
+static_assert(PATH_EAGER == PART_VP_DIGITS && 3 * PATH_EAGER == 18 && PART_VP_DIGIT_BITS == 18, "eager digits of a record");
 
 __device__ __forceinline__ double floor_div_fast(double a, double L) {
   return L == 1.0 ? floor(a) : floor_div_exact(a, L);  // (floor_div_exact(a, 1) == floor(a))

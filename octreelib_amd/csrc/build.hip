@@ -10,7 +10,7 @@
 // This is the GENERAL path: schemes with history, keep_scheme re-placement, voxels with more points than
 // the bucket build of bucket_build.hip sorts in LDS (a bare Octree / OctreeManager with millions of
 // points in one cube), trees deeper than 7 levels, points outside their cube.  A fresh forest is
-// built by bucket_build.hip (step 0 of forest_build).
+// built by bucket_build.hip (build_bucket_route, which forest_build tries before build_general_route).
 // Pipeline (all kernels HBM-bound integer/compare work; nothing here is a contraction):
 //   k_keygen      xyz -> packed voxel key + 21-level child-digit path (reference arithmetic
 //                 restated as exact f64 comparisons), voxel bounding box
@@ -443,6 +443,9 @@ __global__ __launch_bounds__(256) void k_top_tree(const uint32_t* __restrict__ b
   if (d < pm && !((int64_t)(e - s) > K)) atomicExch(flag, 1u);
 }
 
+// the record of a prefix partition (build_common.h) is read as two uint4: vp is .z, the store index .w of the second
+static_assert(PART_REC_BYTES == 2 * sizeof(uint4) && PART_REC_VP_WORD == 4 + 2 && PART_REC_IDX_WORD == 4 + 3, "record words");
+
 // level-pm buffers from the partition records: position = record, "index" = the record's own position (the level
 // loop and the final gather then read coordinates out of the records, i.e. out of the 15 000-point neighbourhood
 // of their depth-pm node instead of the whole store), path word = the digits of levels pm..5 the record carries
@@ -451,11 +454,12 @@ __global__ __launch_bounds__(256) void k_pre_level0(const uint4* __restrict__ re
                                                     uint32_t* __restrict__ path0) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t vp = recs[2 * i + 1].z;
-  const uint32_t d18 = (vp >> 1) & 0x3FFFFu;
+  const uint32_t vp = recs[PART_REC_QUADS * i + 1].z;
+  const uint32_t d18 = (vp >> PART_VP_DIGIT_SHIFT) & PART_VP_DIGIT_MASK;
   idx0[i] = (uint32_t)i | 0x80000000u;
-  path0[i] = ((d18 & ((1u << (3 * (6 - pm))) - 1u)) << 14) | (vp & 1u);
-  pos_node[i] = (int32_t)(top_base(pm) + (d18 >> (18 - 3 * pm)));
+  // (the path word holds its digits from bit 31 down, compute_path: the record's 18 bits go to bits [14, 31])
+  path0[i] = ((d18 & ((1u << (3 * (PART_VP_DIGITS - pm))) - 1u)) << (32 - PART_VP_DIGIT_BITS)) | (vp & PART_VP_BAD);
+  pos_node[i] = (int32_t)(top_base(pm) + (d18 >> (PART_VP_DIGIT_BITS - 3 * pm)));
 }
 
 // k_finalize over the records: the leaf-ordered permutation holds the records' ORIGINAL store indices
@@ -470,7 +474,7 @@ __global__ __launch_bounds__(256) void k_finalize_rec(const int32_t* __restrict_
   if (i >= n_alive) return;
   const int d = depth[pos_node[i]];
   const uint32_t v = ((d & 1) ? idx_b[i] : idx_a[i]) & IDX_MASK;
-  const uint4 a = recs[2 * (size_t)v], b = recs[2 * (size_t)v + 1];
+  const uint4 a = recs[PART_REC_QUADS * (size_t)v], b = recs[PART_REC_QUADS * (size_t)v + 1];
   ord_idx[i] = b.w & IDX_MASK;
   uint2* o = reinterpret_cast<uint2*>(xyz_ord + 3 * i);
   o[0] = uint2{a.x, a.y};
@@ -1372,37 +1376,67 @@ static int forest_ensure_origin(octl_forest* f) {
   return forest_fix_origin(f, bb);
 }
 
-int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
-                 int32_t keep_scheme, int32_t max_depth, octl_build_info* info, const PlanarRule* planar) {
+// forest_build (at the end): build_validate -> build_begin -> build_try_incremental -> build_bucket_route ->
+// build_general_route -> build_block_table -> build_commit.  A route fills a BuildOutcome; build_commit is the only
+// place that writes a finished build into the forest.
+namespace {
+
+// what the caller asked for, and what follows from it once
+struct BuildRequest {
+  int64_t K;
+  int keep_scheme;
+  int max_depth;
+  const PlanarRule* planar;
+  bool all_scheme;             // every pose drives the scheme
+  const uint8_t* scheme_dev;   // the scheme mask on the device (build_begin); nullptr = all poses
+  int n_poses;
+  int64_t N;                   // stored points ...
+  int64_t n_alive;             // ... of which alive (read behind the incremental insertion)
+  int cur_epoch;               // epoch of the nodes this build splits (likewise)
+};
+
+// everything build_commit writes: filled by the route that built
+struct BuildOutcome {
+  NodeTable* nt = nullptr;
+  int64_t n_voxels = 0, n_internal = 0, n_blocks = 0;
+  int levels = 0;
+  std::vector<octl_forest::LevelSeg> segs;
+  bool blocks_made = false;  // the route has left the block table behind (else: build_block_table)
+  // the voxel keys: the key geometry of a fresh voxel list (decoded on the host only when someone asks) or the
+  // list merged with the previous scheme's voxels
+  bool fresh_keys = false;
+  int vl_min[3] = {0, 0, 0};
+  uint64_t vl_ny = 1, vl_nz = 1;
+  std::vector<uint64_t> new_vkeys;
+  bool uniform_epoch = true;
+  bool fast_order_valid = false;
+  int64_t max_block_hint = INT64_MAX;
+  bool publish_split_stats = false;  // a planar build: what its decisions saw, for octl_forest_get_split_stats
+};
+
+int build_validate(octl_forest* f, const BuildRequest& rq, const uint8_t* scheme_mask, int32_t n_mask) {
   octl_ctx* ctx = f->ctx;
-  hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int64_t N = f->n_store;
-  const int n_poses = (int)f->pose_off.size() - 1;
-  if (N >= ((int64_t)1 << 31))
+  if (rq.N >= ((int64_t)1 << 31))
     return octl_set_error(ctx, OCTL_E_INVALID, "more than 2^31-1 points in one forest");
-  if (keep_scheme && !f->built)
+  if (rq.keep_scheme && !f->built)
     return octl_set_error(ctx, OCTL_E_STATE, "keep_scheme build without a previous scheme");
-  if (keep_scheme && planar) return octl_set_error(ctx, OCTL_E_INVALID, "a planar build makes its own scheme");
-  if (scheme_mask && n_mask != n_poses)
+  if (rq.keep_scheme && rq.planar) return octl_set_error(ctx, OCTL_E_INVALID, "a planar build makes its own scheme");
+  if (scheme_mask && n_mask != rq.n_poses)
     return octl_set_error(ctx, OCTL_E_INVALID, "scheme mask has %d entries for %d poses", n_mask,
-                          n_poses);
-  if (f->displaced_rows && !keep_scheme)
+                          rq.n_poses);
+  if (f->displaced_rows && !rq.keep_scheme)
     return octl_set_error(ctx, OCTL_E_DOMAIN,
                           "map_leaf_points left points outside the cube of their leaf: the reference keeps them "
                           "there and raises IndexError when such a leaf is subdivided (octree.py:94-98)");
-  if (max_depth <= 0) max_depth = 63;
-  f->fast_order_valid = false;  // (the block table is about to change)
-  f->pooled_valid = false;
-  f->max_block_hint = INT64_MAX;
-  BuildTrace trace;
-  trace.on = ctx->opt.trace_build != 0;
-  uint32_t* small = ctx->small.as<uint32_t>();
+  return OCTL_OK;
+}
 
-  bool all_scheme = true;
-  if (scheme_mask && !keep_scheme)
-    for (int p = 0; p < n_poses; ++p) all_scheme = all_scheme && scheme_mask[p];
-
+// the first launch (k_build_begin: scalar block, staged hint, voxel box reset) and the small uploads: pose offsets
+// and, when a pose subset drives the scheme, its mask (rq.scheme_dev)
+int build_begin(octl_forest* f, BuildRequest& rq, const uint8_t* scheme_mask) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  const int n_poses = rq.n_poses;
   // ---- reset the scalar block -------------------------------------------------------------
   {
     uint32_t init[32];
@@ -1415,7 +1449,8 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
     // box is still to be found: bucket_build.hip decides and, if it does, finds the record in place)
     int hint_words = 0;
     ctx->geom_hint_staged = false;
-    if (f->bbox_pending && !keep_scheme && ctx->geom_hint_valid && !ctx->geom_hint_two_pass && !ctx->opt.no_geom_hint) {
+    if (f->bbox_pending && !rq.keep_scheme && ctx->geom_hint_valid && !ctx->geom_hint_two_pass &&
+        !ctx->opt.no_geom_hint) {
       static_assert(sizeof(ctx->geom_hint) == 192, "hint words");
       std::memcpy(static_cast<char*>(ctx->small_host) + SM_GEOM * 4, ctx->geom_hint, sizeof(ctx->geom_hint));
       hint_words = (int)(sizeof(ctx->geom_hint) / 4);
@@ -1427,8 +1462,8 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
       f->bbox_stale = false;
     }
     // (a kernel copy out of page-locked memory, not a DMA: see octl_copy_from_pinned)
-    OCTL_LAUNCH(k_build_begin, dim3(1), dim3(128), 0, st, static_cast<const uint32_t*>(ctx->small_host), small,
-                       hint_words, box);
+    OCTL_LAUNCH(k_build_begin, dim3(1), dim3(128), 0, st, static_cast<const uint32_t*>(ctx->small_host),
+                       ctx->small.as<uint32_t>(), hint_words, box);
     HIP_TRY(ctx, hipGetLastError());
   }
 
@@ -1438,187 +1473,278 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
     OCTL_TRY(devbuf_reserve(ctx, f->pose_off_dev, (size_t)(n_poses + 1) * 8));
     if (f->pose_off_dev.p != before) f->pose_off_uploaded.clear();  // a new buffer holds nothing yet
   }
-  const uint8_t* scheme_dev = nullptr;
-  {
-    // small uploads go through pinned staging so that no synchronisation is needed; the region
-    // [0, 128 KiB) of ctx->pinned belongs to the build, [128 KiB, 256 KiB) to the RANSAC table
-    const size_t off_bytes = (size_t)(n_poses + 1) * 8;
-    const bool fits = off_bytes + (size_t)n_poses <= OCTL_PINNED_BYTES / 2;
-    char* pin = static_cast<char*>(ctx->pinned);
-    const void* src_off = f->pose_off.data();
+  rq.scheme_dev = nullptr;
+  // small uploads go through pinned staging so that no synchronisation is needed; the region
+  // [0, 128 KiB) of ctx->pinned belongs to the build, [128 KiB, 256 KiB) to the RANSAC table
+  const size_t off_bytes = (size_t)(n_poses + 1) * 8;
+  const bool fits = off_bytes + (size_t)n_poses <= OCTL_PINNED_BYTES / 2;
+  char* pin = static_cast<char*>(ctx->pinned);
+  const void* src_off = f->pose_off.data();
+  if (fits) {
+    std::memcpy(pin, f->pose_off.data(), off_bytes);
+    src_off = pin;
+  }
+  if (f->pose_off_uploaded != f->pose_off) {  // (the same offsets step after step: nothing to upload)
+    if (fits)
+      OCTL_TRY(octl_copy_from_pinned(ctx, f->pose_off_dev.p, src_off, off_bytes));
+    else
+      HIP_TRY(ctx, hipMemcpyAsync(f->pose_off_dev.p, src_off, off_bytes, hipMemcpyHostToDevice, st));
+    f->pose_off_uploaded = f->pose_off;
+  }
+  if (!rq.all_scheme) {
+    OCTL_TRY(devbuf_reserve(ctx, f->scheme_dev, (size_t)n_poses));
+    const void* src_m = scheme_mask;
     if (fits) {
-      std::memcpy(pin, f->pose_off.data(), off_bytes);
-      src_off = pin;
+      std::memcpy(pin + off_bytes, scheme_mask, (size_t)n_poses);
+      src_m = pin + off_bytes;
     }
-    if (f->pose_off_uploaded != f->pose_off) {  // (the same offsets step after step: nothing to upload)
-      if (fits)
-        OCTL_TRY(octl_copy_from_pinned(ctx, f->pose_off_dev.p, src_off, off_bytes));
-      else
-        HIP_TRY(ctx, hipMemcpyAsync(f->pose_off_dev.p, src_off, off_bytes, hipMemcpyHostToDevice, st));
-      f->pose_off_uploaded = f->pose_off;
-    }
-    if (!all_scheme) {
-      OCTL_TRY(devbuf_reserve(ctx, f->scheme_dev, (size_t)n_poses));
-      const void* src_m = scheme_mask;
-      if (fits) {
-        std::memcpy(pin + off_bytes, scheme_mask, (size_t)n_poses);
-        src_m = pin + off_bytes;
-      }
-      HIP_TRY(ctx, hipMemcpyAsync(f->scheme_dev.p, src_m, (size_t)n_poses, hipMemcpyHostToDevice, st));
-      scheme_dev = f->scheme_dev.as<uint8_t>();
-    }
-    if (!fits) HIP_TRY(ctx, hipStreamSynchronize(st));  // pageable sources must not change in flight
+    HIP_TRY(ctx, hipMemcpyAsync(f->scheme_dev.p, src_m, (size_t)n_poses, hipMemcpyHostToDevice, st));
+    rq.scheme_dev = f->scheme_dev.as<uint8_t>();
   }
+  if (!fits) HIP_TRY(ctx, hipStreamSynchronize(st));  // pageable sources must not change in flight
+  return OCTL_OK;
+}
 
-  // ---- poses appended to a built forest inherit its scheme: only the new points are placed -----------
-  // (K < 0, "never split", over a scheme that has no internal nodes - the state between insert_points calls
-  //  before the first subdivide - is the same thing: new points into the existing roots, new voxels as
-  //  new roots; only the build counter advances)
-  const bool unsplit_again = !keep_scheme && !planar && K < 0 && f->built && f->n_internal == 0;
-  if (keep_scheme || unsplit_again) {
-    int done = 0;
-    OCTL_TRY(forest_insert_incremental(f, &done, info));
-    trace.mark("incremental insertion");
-    if (done) {
-      if (unsplit_again) f->epoch += 1;
-      return OCTL_OK;
-    }
-    // the re-placement below keys every stored point by its coordinates again: a row that map_leaf_points moved
-    // out of its leaf's cube would silently change leaf (or voxel).  The reference keeps such a row where it is
-    // until that leaf is subdivided (octree.py:94-98,114-123); only the incremental path above does the same.
-    if (f->displaced_rows)
-      return octl_set_error(ctx, OCTL_E_DOMAIN,
-                            "map_leaf_points left points outside the cube of their leaf and the stored poses have "
-                            "to be placed again (a pose was extended or the scheme replaced since): the points "
-                            "cannot be kept in their leaves, as the reference does (octree.py:114-123)");
+// Poses appended to a built forest inherit its scheme: only the new points are placed (incremental.hip).
+// (K < 0, "never split", over a scheme that has no internal nodes - the state between insert_points calls
+//  before the first subdivide - is the same thing: new points into the existing roots, new voxels as
+//  new roots; only the build counter advances.)  *done = 1: the build is complete, info filled.
+int build_try_incremental(octl_forest* f, const BuildRequest& rq, BuildTrace& trace, octl_build_info* info, int* done) {
+  *done = 0;
+  const bool unsplit_again = !rq.keep_scheme && !rq.planar && rq.K < 0 && f->built && f->n_internal == 0;
+  if (!rq.keep_scheme && !unsplit_again) return OCTL_OK;
+  OCTL_TRY(forest_insert_incremental(f, done, info));
+  trace.mark("incremental insertion");
+  if (*done) {
+    if (unsplit_again) f->epoch += 1;
+    return OCTL_OK;
   }
-  const int64_t n_alive = f->n_alive;
-  // ---- 0. the bucket build does insert + subdivide in one go (bucket_build.hip): a fresh forest, or a
-  //         count-driven subdivide over a previous scheme (its internal nodes keep their epochs, its voxels
-  //         must all be there again) ----------------------------------------------------------------------------
+  // the re-placement that follows keys every stored point by its coordinates again: a row that map_leaf_points moved
+  // out of its leaf's cube would silently change leaf (or voxel).  The reference keeps such a row where it is
+  // until that leaf is subdivided (octree.py:94-98,114-123); only the incremental path above does the same.
+  if (f->displaced_rows)
+    return octl_set_error(f->ctx, OCTL_E_DOMAIN,
+                          "map_leaf_points left points outside the cube of their leaf and the stored poses have "
+                          "to be placed again (a pose was extended or the scheme replaced since): the points "
+                          "cannot be kept in their leaves, as the reference does (octree.py:114-123)");
+  return OCTL_OK;
+}
+
+// The block table of the leaf-ordered arrays a route has left behind, and the build's final synchronisation.  A point
+// outside the cube of a node that was split shows here: the leaf-ordered arrays were overwritten, so the forest
+// is left with its points and no scheme.
+int build_block_table(octl_forest* f, int64_t n_alive, int64_t* n_blocks) {
+  const int64_t n_ord_before = f->n_ord;
+  f->n_ord = n_alive;
+  OCTL_TRY(forest_make_blocks(f));
+  uint32_t e = 0;
+  OCTL_TRY(forest_finish_blocks(f, &e));
+  *n_blocks = f->n_blocks;
+  if (e) {
+    f->n_ord = n_ord_before;
+    f->n_blocks = 0;
+    f->built = false;
+    return octl_set_error(f->ctx, OCTL_E_DOMAIN,
+                          "a point lies outside the cube of a node that is being subdivided "
+                          "(the reference raises IndexError or picks a wrong child here)");
+  }
+  return OCTL_OK;
+}
+
+// the finished build into the forest and into *info
+int build_commit(octl_forest* f, const BuildRequest& rq, BuildOutcome& o, octl_build_info* info) {
+  octl_ctx* ctx = f->ctx;
+  NodeTable& nt = *o.nt;
+  f->cur ^= 1;
+  f->n_voxels = o.n_voxels;
+  if (o.fresh_keys) {
+    f->vkeys.clear();
+    f->vkeys_stale = true;
+    f->vl_min[0] = o.vl_min[0]; f->vl_min[1] = o.vl_min[1]; f->vl_min[2] = o.vl_min[2];
+    f->vl_ny = o.vl_ny;
+    f->vl_nz = o.vl_nz;
+  } else {
+    f->vkeys.swap(o.new_vkeys);
+    f->vkeys_stale = false;
+  }
+  f->level_segs.swap(o.segs);
+  f->built = true;
+  f->epoch = rq.cur_epoch;
+  f->n_ord = rq.n_alive;
+  f->n_blocks = o.n_blocks;
+  f->n_internal = o.n_internal;
+  f->uniform_epoch = o.uniform_epoch;
+  f->max_depth_reached = o.levels;
+  f->mask_valid = false;
+  f->store_dirty = false;
+  f->vcode_valid = false;
+  f->fast_order_valid = o.fast_order_valid;
+  f->max_block_hint = o.max_block_hint;
+  f->built_store = f->n_store;
+  f->built_poses = rq.n_poses;
+  f->append_only = true;
+  if (o.publish_split_stats) {  // (the statistic is in place already)
+    OCTL_TRY(devbuf_reserve(ctx, f->split_n, (size_t)std::max<int64_t>(nt.n, 1) * 4));
+    if (nt.n > 0)
+      HIP_TRY(ctx, hipMemcpyAsync(f->split_n.p, nt.scount.p, (size_t)nt.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    f->split_stats_nodes = nt.n;
+    f->split_stats_valid = true;
+  }
+  if (info) {
+    info->n_points = rq.n_alive;
+    info->n_voxels = o.n_voxels;
+    info->n_nodes = nt.n;
+    info->n_internal = o.n_internal;
+    info->n_blocks = o.n_blocks;
+    info->max_depth = o.levels;
+    info->n_levels = o.levels;
+  }
+  return OCTL_OK;
+}
+
+// ---- the bucket route -----------------------------------------------------------------------------------------
+
+// Some voxels were left as single leaves (more than 4096 points, deeper than 6 levels, a point outside its cube):
+// the level loop subdivides exactly those roots, the rest of the build stands.  The block table is stale then.
+int bucket_finish_pending(octl_forest* f, const BuildRequest& rq, BuildTrace& trace, const BucketBuildArgs& ba,
+                          NodeTable& bt, BucketBuildResult& br) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t n_alive = rq.n_alive;
+  for (int b = 0; b < 2; ++b) {
+    OCTL_TRY(devbuf_reserve(ctx, f->idxbuf[b], (size_t)n_alive * 4));
+    OCTL_TRY(devbuf_reserve(ctx, f->pathbuf[b], (size_t)n_alive * 4));
+  }
+  LevelLoop L{f, &bt, rq.K, 0, rq.all_scheme, rq.scheme_dev, ba.old_fc, ba.old_epoch, rq.cur_epoch, rq.max_depth,
+              n_alive, true, 0, br.n_voxels, 0, 0, &br.segs};
+  OCTL_TRY(run_level_loop(L));
+  trace.mark("level loop (pending voxels)");
+  if (L.n_internal > 0) {
+    NodePtrs nd = node_ptrs(bt);
+    KTimer t(ctx, "finalize");
+    OCTL_LAUNCH(k_finalize_marked, dim3(grid_for(n_alive)), dim3(256), 0, st,
+                       (const int32_t*)f->pos_node.as<int32_t>(), (const int32_t*)nd.depth,
+                       (const int32_t*)nd.voxel, (const uint8_t*)f->root_up.as<uint8_t>(),
+                       (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
+                       (const uint32_t*)f->idxbuf[1].as<uint32_t>(), (const double*)f->xyz.as<double>(),
+                       n_alive, f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  br.n_internal += L.n_internal;
+  br.levels = std::max(br.levels, L.level);
+  return OCTL_OK;
+}
+
+// The bucket build does insert + subdivide in one go (bucket_build.hip): a fresh forest, or a count-driven
+// subdivide over a previous scheme (its internal nodes keep their epochs, its voxels must all be there again).
+// *done = false: the route does not apply, or the bucket build declined or abandoned the build - the general
+// route runs.
+int build_bucket_route(octl_forest* f, const BuildRequest& rq, BuildTrace& trace, BuildOutcome& o, bool* done) {
+  *done = false;
   const bool fresh0 = !f->built && f->vkeys.empty() && !f->vkeys_stale;
-  const bool over_old = f->built && !ctx->opt.no_bucket_history;
-  // (not a planar build: its statistic is evaluated level by level, by the level loop below)
-  if (!keep_scheme && !planar && (fresh0 || over_old) && n_alive > 0) {
-    NodeTable& bt = f->nodes[f->cur ^ 1];
-    const int cur_epoch = f->epoch + 1;
-    BucketBuildArgs ba{K, scheme_dev, cur_epoch, max_depth};
-    const int64_t old_internal0 = f->built ? f->n_internal : 0;
-    if (over_old) {
-      OCTL_TRY(forest_sync_vcodes(f));
-      NodeTable& old0 = f->nodes[f->cur];
-      ba.old_fc = old0.first_child.as<int32_t>();
-      ba.old_epoch = old0.epoch.as<int32_t>();
-      ba.old_vcode = f->vcode_dev[0].as<uint64_t>();
-      ba.old_voxels = f->n_voxels;
-    }
-    BucketBuildResult br;
-    OCTL_TRY(forest_bucket_build(f, ba, bt, &br));
-    trace.mark("bucket build");
-    if (br.done && br.pending > 0) {
-      // some voxels were left as single leaves (more than 4096 points, deeper than 6 levels, a point
-      // outside its cube): the level loop subdivides exactly those roots, the rest of the build stands
-      for (int b = 0; b < 2; ++b) {
-        OCTL_TRY(devbuf_reserve(ctx, f->idxbuf[b], (size_t)n_alive * 4));
-        OCTL_TRY(devbuf_reserve(ctx, f->pathbuf[b], (size_t)n_alive * 4));
-      }
-      LevelLoop L{f, &bt, K, 0, all_scheme, scheme_dev, ba.old_fc, ba.old_epoch, cur_epoch, max_depth, n_alive,
-                  true, 0, br.n_voxels, 0, 0, &br.segs};
-      OCTL_TRY(run_level_loop(L));
-      trace.mark("level loop (pending voxels)");
-      if (L.n_internal > 0) {
-        NodePtrs nd = node_ptrs(bt);
-        KTimer t(ctx, "finalize");
-        OCTL_LAUNCH(k_finalize_marked, dim3(grid_for(n_alive)), dim3(256), 0, st,
-                           (const int32_t*)f->pos_node.as<int32_t>(), (const int32_t*)nd.depth,
-                           (const int32_t*)nd.voxel, (const uint8_t*)f->root_up.as<uint8_t>(),
-                           (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
-                           (const uint32_t*)f->idxbuf[1].as<uint32_t>(), (const double*)f->xyz.as<double>(),
-                           n_alive, f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>());
-        HIP_TRY(ctx, hipGetLastError());
-      }
-      br.n_internal += L.n_internal;
-      br.levels = std::max(br.levels, L.level);
-      const int64_t n_ord_before = f->n_ord;
-      f->n_ord = n_alive;
-      OCTL_TRY(forest_make_blocks(f));
-      uint32_t e = 0;
-      OCTL_TRY(forest_finish_blocks(f, &e));
-      br.n_blocks = f->n_blocks;
-      if (e) {
-        f->n_ord = n_ord_before;
-        f->n_blocks = 0;
-        f->built = false;
-        return octl_set_error(ctx, OCTL_E_DOMAIN,
-                              "a point lies outside the cube of a node that is being subdivided "
-                              "(the reference raises IndexError or picks a wrong child here)");
-      }
-    }
-    if (br.done) {
-      f->cur ^= 1;
-      f->n_voxels = br.n_voxels;
-      f->vkeys.clear();
-      f->vkeys_stale = true;
-      f->vl_min[0] = br.geom.min[0]; f->vl_min[1] = br.geom.min[1]; f->vl_min[2] = br.geom.min[2];
-      f->vl_ny = br.geom.ny;
-      f->vl_nz = br.geom.nz;
-      f->level_segs.swap(br.segs);
-      f->built = true;
-      f->epoch = cur_epoch;
-      f->n_ord = n_alive;
-      f->n_blocks = br.n_blocks;
-      f->n_internal = br.n_internal;
-      // nodes inherit an older epoch only from a previous scheme that had internal nodes
-      f->uniform_epoch = !(over_old && old_internal0 > 0);
-      f->max_depth_reached = br.levels;
-      f->mask_valid = false;
-      f->store_dirty = false;
-      f->vcode_valid = false;
-      f->fast_order_valid = br.geom.order_done && br.pending == 0;
-      // (count-driven from ALL poses: a leaf holds at most K points; what the level loop finished for the voxels left
-      //  behind obeys the same rule)
-      if (all_scheme && K >= 0) f->max_block_hint = K;
-      f->built_store = f->n_store;
-      f->built_poses = n_poses;
-      f->append_only = true;
-      if (info) {
-        info->n_points = n_alive;
-        info->n_voxels = br.n_voxels;
-        info->n_nodes = bt.n;
-        info->n_internal = br.n_internal;
-        info->n_blocks = br.n_blocks;
-        info->max_depth = br.levels;
-        info->n_levels = br.levels;
-      }
-      return OCTL_OK;
-    }
+  const bool over_old = f->built && !f->ctx->opt.no_bucket_history;
+  // (not a planar build: its statistic is evaluated level by level, by the level loop of the general route)
+  if (rq.keep_scheme || rq.planar || !(fresh0 || over_old) || rq.n_alive <= 0) return OCTL_OK;
+  NodeTable& bt = f->nodes[f->cur ^ 1];
+  BucketBuildArgs ba{rq.K, rq.scheme_dev, rq.cur_epoch, rq.max_depth};
+  const int64_t old_internal0 = f->built ? f->n_internal : 0;
+  if (over_old) {
+    OCTL_TRY(forest_sync_vcodes(f));
+    NodeTable& old0 = f->nodes[f->cur];
+    ba.old_fc = old0.first_child.as<int32_t>();
+    ba.old_epoch = old0.epoch.as<int32_t>();
+    ba.old_vcode = f->vcode_dev[0].as<uint64_t>();
+    ba.old_voxels = f->n_voxels;
   }
-  OCTL_TRY(forest_sync_vkeys(f));  // the previous scheme's voxels persist (no-op when fresh)
-  trace.mark("sync_vkeys");
-  // ---- 1. keys -----------------------------------------------------------------------------------
+  BucketBuildResult br;
+  OCTL_TRY(forest_bucket_build(f, ba, bt, &br));
+  trace.mark("bucket build");
+  if (!br.done) return OCTL_OK;
+  if (br.pending > 0) OCTL_TRY(bucket_finish_pending(f, rq, trace, ba, bt, br));
+  *done = true;
+  o.nt = &bt;
+  o.n_voxels = br.n_voxels;
+  o.n_internal = br.n_internal;
+  o.levels = br.levels;
+  o.segs.swap(br.segs);
+  o.blocks_made = br.pending == 0;  // (k_bucket_finish made the table; the level loop's resume outdates it)
+  o.n_blocks = br.n_blocks;
+  // the bucket build always makes its voxel list anew (a previous scheme's voxels are all there again, or it hands
+  // the build back): key geometry, never merged keys
+  o.fresh_keys = true;
+  o.vl_min[0] = br.geom.min[0]; o.vl_min[1] = br.geom.min[1]; o.vl_min[2] = br.geom.min[2];
+  o.vl_ny = br.geom.ny;
+  o.vl_nz = br.geom.nz;
+  // nodes inherit an older epoch only from a previous scheme that had internal nodes (never keep_scheme here)
+  o.uniform_epoch = !(over_old && old_internal0 > 0);
+  // k_bucket_finish leaves the blocks' listing order behind; a resumed level loop renumbers blocks
+  o.fast_order_valid = br.geom.order_done && br.pending == 0;
+  // count-driven from ALL poses: a leaf holds at most K points; what the level loop finished for the voxels left
+  // behind obeys the same rule.  (The general route builds the same trees and promises nothing: see there.)
+  o.max_block_hint = (rq.all_scheme && rq.K >= 0) ? rq.K : INT64_MAX;
+  o.publish_split_stats = false;  // (never planar)
+  return OCTL_OK;
+}
+
+// ---- the general route: keys -> sort -> roots -> level-0 buffers -> level loop -> leaf-ordered arrays ---------------
+
+// what the phases of the general route hand to each other
+struct GeneralBuild {
+  bool cube_fast = false;  // a fresh single cube with every point alive: one root, store order = level-0 order
+  int pm = 0;              // ... partitioned once by the digits of its first pm levels (forest_prefix_partition); 0: not
+  const void* pre_recs = nullptr;
+  const uint32_t *pre_bstart = nullptr, *pre_bad = nullptr;
+  uint32_t pre_stride = 0;
+  int bb[6] = {0, 0, 0, 0, 0, 0};  // the voxel box, the previous scheme's voxels included (a single cube is voxel 0)
+  uint64_t ny = 1, nz = 1, dead_lin = 1;
+  int key_bits = 0;
+  int sorted = 0;  // which of f->lin / f->val holds the sorted keys
+  int64_t n_rtiles = 0;
+  bool have_old = false, fresh = false;  // fresh: roots made on the device (no previous voxels to merge with)
+  int64_t v_pts = 0;  // voxels that hold points; their table (lin, first position): device, and host when merged
+  uint64_t* vlin_d = nullptr;
+  uint32_t* vstart_d = nullptr;
+  std::vector<uint64_t> vlin_h;
+  std::vector<uint32_t> vstart_h;
+  NodeTable* nt = nullptr;
+  int64_t V = 0;                     // roots
+  std::vector<uint64_t> new_vkeys;   // merged voxel keys (!fresh)
+  std::vector<int32_t> local2root;   // voxel with points -> root (!fresh)
+  int32_t* pos_node = nullptr;
+};
+
+uint64_t lin_of(const octl_forest* f, const GeneralBuild& g, uint64_t k) {
+  int64_t q[3];
+  vkey_decode(k, f->vorg, q);
+  return ((uint64_t)(q[0] - g.bb[0]) * g.ny + (uint64_t)(q[1] - g.bb[1])) * g.nz + (uint64_t)(q[2] - g.bb[2]);
+}
+uint64_t vkey_of_lin(const octl_forest* f, const GeneralBuild& g, uint64_t l) {
+  const uint64_t qz = l % g.nz, qy = (l / g.nz) % g.ny, qx = l / (g.nz * g.ny);
+  return vkey_pack((int64_t)qx + g.bb[0], (int64_t)qy + g.bb[1], (int64_t)qz + g.bb[2], f->vorg);
+}
+
+// 1. keys: the route's variant (cube_fast, pm), packed voxel keys + paths, the voxel box
+int general_keys(octl_forest* f, const BuildRequest& rq, GeneralBuild& g) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  uint32_t* small = ctx->small.as<uint32_t>();
+  const int64_t N = rq.N, n_alive = rq.n_alive;
   OCTL_TRY(forest_ensure_origin(f));
-  // a fresh single cube with every point alive: one root, the store order is the level-0 order (k_cube_level0)
-  const bool cube_fast = f->mode == 1 && N > 0 && n_alive == N && !f->built && f->vkeys.empty() &&
-                         !ctx->opt.no_cube_fast;
-  // ... and when it is BIG the store is first partitioned once by the digits of its first pm levels
+  g.cube_fast = f->mode == 1 && N > 0 && n_alive == N && !f->built && f->vkeys.empty() && !ctx->opt.no_cube_fast;
+  // when the cube is BIG the store is first partitioned once by the digits of its first pm levels
   // (bucket_build.hip: forest_prefix_partition): the top pm levels of the tree follow from the partition's
   // histogram, the level loop starts at level pm and every later gather of coordinates stays inside the ~15 000
   // records of one depth-pm node.  BASELINE config 4 (64 M points, K = 4096, 5 levels): 4 of the 5 level passes
   // and the store-wide random gather of k_finalize (169 bytes fetched per 24-byte point) go.
-  int pm = 0;
-  const void* pre_recs = nullptr;
-  const uint32_t* pre_bstart = nullptr;
-  const uint32_t* pre_bad = nullptr;
-  uint32_t pre_stride = 0;
   // (OCTL_CUBE_PREFIX_MIN: tests run this path on small clouds; OCTL_NO_CUBE_PREFIX: never)
   const int64_t prefix_min = ctx->opt.cube_prefix_min > 0 ? ctx->opt.cube_prefix_min : ((int64_t)4 << 20);
-  if (cube_fast && all_scheme && !keep_scheme && !planar && K >= 0 && n_alive >= prefix_min &&
+  if (g.cube_fast && rq.all_scheme && !rq.keep_scheme && !rq.planar && rq.K >= 0 && n_alive >= prefix_min &&
       !ctx->opt.no_cube_prefix) {
-    for (int c = 4; c >= 2 && !pm; --c)   // every node above depth pm has to split: expect >= 2 K points per depth-pm node
-      if (n_alive >= 2 * std::max<int64_t>(K, 1) * ((int64_t)1 << (3 * c)) && c <= max_depth) pm = c;
-    if (pm) OCTL_TRY(forest_prefix_partition(f, pm, &pre_recs, &pre_bstart, &pre_stride, &pre_bad));
+    for (int c = 4; c >= 2 && !g.pm; --c)   // every node above depth pm has to split: expect >= 2 K points per depth-pm node
+      if (n_alive >= 2 * std::max<int64_t>(rq.K, 1) * ((int64_t)1 << (3 * c)) && c <= rq.max_depth) g.pm = c;
+    if (g.pm) OCTL_TRY(forest_prefix_partition(f, g.pm, &g.pre_recs, &g.pre_bstart, &g.pre_stride, &g.pre_bad));
   }
-  if (N > 0 && !cube_fast) {
+  if (N > 0 && !g.cube_fast) {
     OCTL_TRY(alive_ensure(f));
     OCTL_TRY(devbuf_reserve(ctx, f->vkey, (size_t)N * 8));
     OCTL_TRY(devbuf_reserve(ctx, f->path, (size_t)N * 4));
@@ -1630,15 +1756,15 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
     HIP_TRY(ctx, hipGetLastError());
   }
   uint32_t sm[32];
-  int bb[6] = {0, 0, 0, 0, 0, 0};  // (a single cube is voxel 0)
-  if (!cube_fast) {
+  int* bb = g.bb;
+  if (!g.cube_fast) {
     OCTL_TRY(octl_readback(ctx, small, 32, sm));
     if (sm[SM_ERR])
       return octl_set_error(ctx, OCTL_E_DOMAIN,
                             "a point has a non-finite coordinate, a top-level voxel index outside +-%d, or "
                             "lies more than %d voxels from where the scene started", OCTL_VOX_ABS_LIMIT,
                             OCTL_VOX_BIAS);
-    std::memcpy(bb, sm + SM_BBOX, sizeof(bb));
+    std::memcpy(bb, sm + SM_BBOX, sizeof(g.bb));
   }
   // the voxels of the previous scheme persist even when they have lost all their points
   for (uint64_t k : f->vkeys) {
@@ -1651,25 +1777,19 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   }
   const bool any_voxel = bb[0] <= bb[3];
   const uint64_t nx = any_voxel ? (uint64_t)(bb[3] - bb[0] + 1) : 1;
-  const uint64_t ny = any_voxel ? (uint64_t)(bb[4] - bb[1] + 1) : 1;
-  const uint64_t nz = any_voxel ? (uint64_t)(bb[5] - bb[2] + 1) : 1;
+  g.ny = any_voxel ? (uint64_t)(bb[4] - bb[1] + 1) : 1;
+  g.nz = any_voxel ? (uint64_t)(bb[5] - bb[2] + 1) : 1;
   if (!any_voxel) bb[0] = bb[1] = bb[2] = 0;
-  const uint64_t dead_lin = nx * ny * nz;  // < 2^63
-  const int key_bits = bits_for(dead_lin);
-  auto lin_of = [&](uint64_t k) {
-    int64_t q[3];
-    vkey_decode(k, f->vorg, q);
-    return ((uint64_t)(q[0] - bb[0]) * ny + (uint64_t)(q[1] - bb[1])) * nz + (uint64_t)(q[2] - bb[2]);
-  };
-  auto vkey_of_lin = [&](uint64_t l) {
-    const uint64_t qz = l % nz, qy = (l / nz) % ny, qx = l / (nz * ny);
-    return vkey_pack((int64_t)qx + bb[0], (int64_t)qy + bb[1], (int64_t)qz + bb[2], f->vorg);
-  };
+  g.dead_lin = nx * g.ny * g.nz;  // < 2^63
+  g.key_bits = bits_for(g.dead_lin);
+  return OCTL_OK;
+}
 
-  trace.mark("keys + bbox readback");
-  // ---- 2. sort by top-level voxel ---------------------------------------------------------------
-  int sorted = 0;
-  if (cube_fast) {  // (the voxel table of one entry is staged where the sort's second buffers would be)
+// 2. sort by top-level voxel
+int general_sort(octl_forest* f, const BuildRequest& rq, GeneralBuild& g) {
+  octl_ctx* ctx = f->ctx;
+  const int64_t N = rq.N;
+  if (g.cube_fast) {  // (the voxel table of one entry is staged where the sort's second buffers would be)
     OCTL_TRY(devbuf_reserve(ctx, f->lin[1], 64));
     OCTL_TRY(devbuf_reserve(ctx, f->val[1], 64));
   } else if (N > 0) {
@@ -1679,336 +1799,368 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
     }
     {
       KTimer t(ctx, "linkey");
-      OCTL_LAUNCH(k_linkey, dim3(grid_for(N)), dim3(256), 0, st, f->vkey.as<uint64_t>(), N,
-                         bb[0], bb[1], bb[2], ny, nz, dead_lin, f->vorg, f->pose_off_dev.as<int64_t>(),
-                         n_poses, scheme_dev, f->lin[0].as<uint64_t>(), f->val[0].as<uint32_t>());
+      OCTL_LAUNCH(k_linkey, dim3(grid_for(N)), dim3(256), 0, ctx->stream, f->vkey.as<uint64_t>(), N,
+                         g.bb[0], g.bb[1], g.bb[2], g.ny, g.nz, g.dead_lin, f->vorg, f->pose_off_dev.as<int64_t>(),
+                         rq.n_poses, rq.scheme_dev, f->lin[0].as<uint64_t>(), f->val[0].as<uint32_t>());
       HIP_TRY(ctx, hipGetLastError());
     }
     uint64_t* keys[2] = {f->lin[0].as<uint64_t>(), f->lin[1].as<uint64_t>()};
     uint32_t* vals[2] = {f->val[0].as<uint32_t>(), f->val[1].as<uint32_t>()};
     // a single voxel and no dead points: already "sorted"
-    if (!(dead_lin == 1 && n_alive == N))
-      OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys, vals, N, key_bits, f->hist, &sorted));
+    if (!(g.dead_lin == 1 && rq.n_alive == N))
+      OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys, vals, N, g.key_bits, f->hist, &g.sorted));
   }
-  const uint64_t* lin_sorted = f->lin[sorted].as<uint64_t>();
-  const uint32_t* val_sorted = f->val[sorted].as<uint32_t>();
+  return OCTL_OK;
+}
 
-  trace.mark("sort (enqueue)");
-  // ---- 3. roots ------------------------------------------------------------------------------------
+// 3b. roots by union with the voxels of the previous scheme, on the host (both lists are sorted by lin: the packed
+//     key order and the lin order are both the lexicographic (x,y,z) order)
+int general_union_roots(octl_forest* f, const BuildRequest& rq, GeneralBuild& g) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  NodeTable& nt = *g.nt;
+  const int64_t n_alive = rq.n_alive, v_pts = g.v_pts;
+  std::vector<uint64_t>& new_vkeys = g.new_vkeys;
+  std::vector<uint32_t> r_start, r_count;
+  std::vector<int32_t> r_old;
+  g.local2root.resize(std::max<int64_t>(v_pts, 1));
+  size_t a = 0, b = 0;
+  const size_t na = (size_t)v_pts, nb_old = f->vkeys.size();
+  while (a < na || b < nb_old) {
+    const uint64_t la = (a < na) ? g.vlin_h[a] : ~0ull;
+    const uint64_t lb = (b < nb_old) ? lin_of(f, g, f->vkeys[b]) : ~0ull;
+    const uint64_t l = std::min(la, lb);
+    const int32_t root = (int32_t)new_vkeys.size();
+    new_vkeys.push_back(vkey_of_lin(f, g, l));
+    if (la == l) {
+      const uint32_t s0 = g.vstart_h[a];
+      const uint32_t e0 = (a + 1 < na) ? g.vstart_h[a + 1] : (uint32_t)n_alive;
+      r_start.push_back(s0);
+      r_count.push_back(e0 - s0);
+      g.local2root[a] = root;
+      ++a;
+    } else {
+      r_start.push_back(0);
+      r_count.push_back(0);
+    }
+    if (lb == l) {
+      r_old.push_back((int32_t)b);  // old roots are nodes [0, V_old) in voxel order
+      ++b;
+    } else {
+      r_old.push_back(-1);
+    }
+  }
+  if (f->mode == 1 && new_vkeys.empty()) {  // a cube without points still has its root
+    new_vkeys.push_back(vkey_pack(0, 0, 0, f->vorg));
+    r_start.push_back(0);
+    r_count.push_back(0);
+    r_old.push_back(f->built ? 0 : -1);
+  }
+  const int64_t V = g.V = (int64_t)new_vkeys.size();
+  OCTL_TRY(nodes_reserve(ctx, nt, std::max<int64_t>(V, 1)));
+  nt.n = V;
+  NodePtrs nd = node_ptrs(nt);
+  if (V > 0) {
+    std::vector<int32_t> i32((size_t)V);
+    std::vector<double> cor((size_t)V * 3), edg((size_t)V, f->edge);
+    auto up = [&](void* dst, const void* src, size_t bytes) {
+      return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    for (int64_t v = 0; v < V; ++v) {
+      i32[v] = (int32_t)v;
+      if (f->mode == 0) {
+        int64_t q[3];
+        vkey_decode(new_vkeys[v], f->vorg, q);
+        // np.array(voxel_coordinates): int64(q * L), L integer valued (grid.py:72-76,104)
+        for (int ax = 0; ax < 3; ++ax) cor[3 * v + ax] = (double)(int64_t)((double)q[ax] * f->edge);
+      } else {
+        for (int ax = 0; ax < 3; ++ax) cor[3 * v + ax] = f->corner[ax];
+      }
+    }
+    HIP_TRY(ctx, up(nd.start, r_start.data(), (size_t)V * 4));
+    HIP_TRY(ctx, up(nd.count, r_count.data(), (size_t)V * 4));
+    HIP_TRY(ctx, up(nd.old_id, r_old.data(), (size_t)V * 4));
+    HIP_TRY(ctx, up(nd.voxel, i32.data(), (size_t)V * 4));
+    HIP_TRY(ctx, hipMemsetAsync(nd.depth, 0, (size_t)V * 4, st));
+    HIP_TRY(ctx, hipMemsetAsync(nd.epoch, 0, (size_t)V * 4, st));
+    HIP_TRY(ctx, hipMemsetAsync(nd.parent, 0xFF, (size_t)V * 4, st));
+    HIP_TRY(ctx, hipMemsetAsync(nd.first_child, 0xFF, (size_t)V * 4, st));
+    HIP_TRY(ctx, up(nd.corner, cor.data(), (size_t)V * 24));
+    HIP_TRY(ctx, up(nd.edge, edg.data(), (size_t)V * 8));
+    if (rq.all_scheme || rq.keep_scheme) {
+      HIP_TRY(ctx, up(nd.scount, r_count.data(), (size_t)V * 4));
+    } else {
+      HIP_TRY(ctx, hipMemsetAsync(nd.scount, 0, (size_t)V * 4, st));
+    }
+    // the sources above are pageable host vectors that die with this scope
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  return OCTL_OK;
+}
+
+// 3. roots: the table of the voxels that hold points, then one root per voxel - the complete top tree of a prefix
+//    partition (which may send the build back to pm = 0), made on the device (fresh), or merged on the host
+int general_roots(octl_forest* f, const BuildRequest& rq, GeneralBuild& g, BuildTrace& trace) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  uint32_t* small = ctx->small.as<uint32_t>();
+  const int64_t n_alive = rq.n_alive;
   // (first voxel ordinal of every tile of RT_TILE positions: k_root_tiles, k_init_level0)
-  const int64_t n_rtiles = ceil_div(std::max<int64_t>(n_alive, 1), (int64_t)RT_TILE);
-  OCTL_TRY(devbuf_reserve(ctx, f->flags, (size_t)(n_rtiles + 8) * 4));
+  g.n_rtiles = ceil_div(std::max<int64_t>(n_alive, 1), (int64_t)RT_TILE);
+  OCTL_TRY(devbuf_reserve(ctx, f->flags, (size_t)(g.n_rtiles + 8) * 4));
   uint32_t* flags = f->flags.as<uint32_t>();
-  const bool have_old = f->built;
-  const bool fresh = !have_old && f->vkeys.empty() && n_alive > 0;  // roots made on the device
-  int64_t v_pts = 0;
-  std::vector<uint64_t> vlin_h;
-  std::vector<uint32_t> vstart_h;
-  uint64_t* vlin_d = f->lin[sorted ^ 1].as<uint64_t>();   // free now: staging for the voxel table
-  uint32_t* vstart_d = f->val[sorted ^ 1].as<uint32_t>();
-  if (cube_fast) {
-    HIP_TRY(ctx, hipMemsetAsync(vlin_d, 0, 8, st));    // voxel 0 ...
-    HIP_TRY(ctx, hipMemsetAsync(vstart_d, 0, 4, st));  // ... starts at position 0
-    v_pts = 1;
+  g.have_old = f->built;
+  g.fresh = !g.have_old && f->vkeys.empty() && n_alive > 0;
+  g.vlin_d = f->lin[g.sorted ^ 1].as<uint64_t>();   // free now: staging for the voxel table
+  g.vstart_d = f->val[g.sorted ^ 1].as<uint32_t>();
+  if (g.cube_fast) {
+    HIP_TRY(ctx, hipMemsetAsync(g.vlin_d, 0, 8, st));    // voxel 0 ...
+    HIP_TRY(ctx, hipMemsetAsync(g.vstart_d, 0, 4, st));  // ... starts at position 0
+    g.v_pts = 1;
   } else if (n_alive > 0) {
+    const uint64_t* lin_sorted = f->lin[g.sorted].as<uint64_t>();
     KTimer t(ctx, "roots");
-    OCTL_LAUNCH(k_root_tiles<false>, dim3((unsigned)n_rtiles), dim3(256), 0, st, lin_sorted, n_alive, flags,
+    OCTL_LAUNCH(k_root_tiles<false>, dim3((unsigned)g.n_rtiles), dim3(256), 0, st, lin_sorted, n_alive, flags,
                        (uint64_t*)nullptr, (uint32_t*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
-    OCTL_TRY(octl_exclusive_scan_u32(ctx, flags, flags, n_rtiles, small + SM_NVOX));
-    OCTL_LAUNCH(k_root_tiles<true>, dim3((unsigned)n_rtiles), dim3(256), 0, st, lin_sorted, n_alive, flags,
-                       vlin_d, vstart_d);
+    OCTL_TRY(octl_exclusive_scan_u32(ctx, flags, flags, g.n_rtiles, small + SM_NVOX));
+    OCTL_LAUNCH(k_root_tiles<true>, dim3((unsigned)g.n_rtiles), dim3(256), 0, st, lin_sorted, n_alive, flags,
+                       g.vlin_d, g.vstart_d);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t nv;
     OCTL_TRY(octl_readback(ctx, small + SM_NVOX, 1, &nv));
-    v_pts = nv;
-    if (!fresh) {
-      vlin_h.resize(v_pts);
-      vstart_h.resize(v_pts);
-      HIP_TRY(ctx, hipMemcpyAsync(vlin_h.data(), vlin_d, (size_t)v_pts * 8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx, hipMemcpyAsync(vstart_h.data(), vstart_d, (size_t)v_pts * 4, hipMemcpyDeviceToHost, st));
+    g.v_pts = nv;
+    if (!g.fresh) {
+      g.vlin_h.resize(g.v_pts);
+      g.vstart_h.resize(g.v_pts);
+      HIP_TRY(ctx, hipMemcpyAsync(g.vlin_h.data(), g.vlin_d, (size_t)g.v_pts * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(g.vstart_h.data(), g.vstart_d, (size_t)g.v_pts * 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(ctx, hipStreamSynchronize(st));
     }
   }
-  NodeTable& nt = f->nodes[f->cur ^ 1];
-  NodeTable& old = f->nodes[f->cur];
-  const int32_t* old_fc = have_old ? old.first_child.as<int32_t>() : nullptr;
-  const int32_t* old_epoch = have_old ? old.epoch.as<int32_t>() : nullptr;
-  std::vector<uint64_t> new_vkeys;
-  std::vector<int32_t> local2root;
-  int64_t V = 0;
-  NodePtrs nd;
-  const int cur_epoch_new = f->epoch + (keep_scheme ? 0 : 1);
-  if (pm) {
+  g.nt = &f->nodes[f->cur ^ 1];
+  NodeTable& nt = *g.nt;
+  if (g.pm) {
     // the complete top of the tree from the partition's bucket starts; a point outside the cube or a node above
     // depth pm that does not split (few points, very uneven cloud) sends the build down the plain path
-    OCTL_TRY(nodes_reserve(ctx, nt, top_base(pm + 1)));
-    nd = node_ptrs(nt);
-    OCTL_LAUNCH(k_top_tree, dim3(grid_for(top_base(pm + 1))), dim3(256), 0, st, pre_bstart, pre_stride, pm,
-                       n_alive, K, f->edge, f->corner[0], f->corner[1], f->corner[2], cur_epoch_new, nd,
+    OCTL_TRY(nodes_reserve(ctx, nt, top_base(g.pm + 1)));
+    OCTL_LAUNCH(k_top_tree, dim3(grid_for(top_base(g.pm + 1))), dim3(256), 0, st, g.pre_bstart, g.pre_stride, g.pm,
+                       n_alive, rq.K, f->edge, f->corner[0], f->corner[1], f->corner[2], rq.cur_epoch, node_ptrs(nt),
                        small + SM_BK_MISSING);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t* fl = static_cast<uint32_t*>(ctx->small_host);
     HIP_TRY(ctx, hipMemcpyAsync(fl, small + SM_BK_MISSING, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(fl + 1, pre_bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(fl + 1, g.pre_bad, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (fl[0] || fl[1]) {
-      pm = 0;
+      g.pm = 0;
       HIP_TRY(ctx, hipMemsetAsync(small + SM_BK_MISSING, 0, 4, st));
     }
   }
-  if (pm) {
-    V = 1;
-    nt.n = top_base(pm + 1);
-  } else if (fresh) {
-    V = v_pts;
+  if (g.pm) {
+    g.V = 1;
+    nt.n = top_base(g.pm + 1);
+  } else if (g.fresh) {
+    const int64_t V = g.V = g.v_pts;
     OCTL_TRY(nodes_reserve(ctx, nt, std::max<int64_t>(V, 1)));
     nt.n = V;
-    nd = node_ptrs(nt);
-    OCTL_LAUNCH(k_make_roots, dim3(grid_for(V)), dim3(256), 0, st, (const uint64_t*)vlin_d,
-                       (const uint32_t*)vstart_d, V, n_alive, f->mode, f->edge, f->corner[0],
-                       f->corner[1], f->corner[2], bb[0], bb[1], bb[2], ny, nz,
-                       (int)(all_scheme || keep_scheme), nd);
+    OCTL_LAUNCH(k_make_roots, dim3(grid_for(V)), dim3(256), 0, st, (const uint64_t*)g.vlin_d,
+                       (const uint32_t*)g.vstart_d, V, n_alive, f->mode, f->edge, f->corner[0],
+                       f->corner[1], f->corner[2], g.bb[0], g.bb[1], g.bb[2], g.ny, g.nz,
+                       (int)(rq.all_scheme || rq.keep_scheme), node_ptrs(nt));
     HIP_TRY(ctx, hipGetLastError());
   } else {
-    // union with the voxels of the previous scheme (both lists are sorted by lin: the packed key
-    // order and the lin order are both the lexicographic (x,y,z) order)
-    std::vector<uint32_t> r_start, r_count;
-    std::vector<int32_t> r_old;
-    local2root.resize(std::max<int64_t>(v_pts, 1));
-    size_t a = 0, b = 0;
-    const size_t na = (size_t)v_pts, nb_old = f->vkeys.size();
-    while (a < na || b < nb_old) {
-      const uint64_t la = (a < na) ? vlin_h[a] : ~0ull;
-      const uint64_t lb = (b < nb_old) ? lin_of(f->vkeys[b]) : ~0ull;
-      const uint64_t l = std::min(la, lb);
-      const int32_t root = (int32_t)new_vkeys.size();
-      new_vkeys.push_back(vkey_of_lin(l));
-      if (la == l) {
-        const uint32_t s0 = vstart_h[a];
-        const uint32_t e0 = (a + 1 < na) ? vstart_h[a + 1] : (uint32_t)n_alive;
-        r_start.push_back(s0);
-        r_count.push_back(e0 - s0);
-        local2root[a] = root;
-        ++a;
-      } else {
-        r_start.push_back(0);
-        r_count.push_back(0);
-      }
-      if (lb == l) {
-        r_old.push_back((int32_t)b);  // old roots are nodes [0, V_old) in voxel order
-        ++b;
-      } else {
-        r_old.push_back(-1);
-      }
-    }
-    if (f->mode == 1 && new_vkeys.empty()) {  // a cube without points still has its root
-      new_vkeys.push_back(vkey_pack(0, 0, 0, f->vorg));
-      r_start.push_back(0);
-      r_count.push_back(0);
-      r_old.push_back(f->built ? 0 : -1);
-    }
-    V = (int64_t)new_vkeys.size();
-    OCTL_TRY(nodes_reserve(ctx, nt, std::max<int64_t>(V, 1)));
-    nt.n = V;
-    nd = node_ptrs(nt);
-    if (V > 0) {
-      std::vector<int32_t> i32((size_t)V);
-      std::vector<double> cor((size_t)V * 3), edg((size_t)V, f->edge);
-      auto up = [&](void* dst, const void* src, size_t bytes) {
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-      };
-      for (int64_t v = 0; v < V; ++v) {
-        i32[v] = (int32_t)v;
-        if (f->mode == 0) {
-          int64_t q[3];
-          vkey_decode(new_vkeys[v], f->vorg, q);
-          // np.array(voxel_coordinates): int64(q * L), L integer valued (grid.py:72-76,104)
-          for (int ax = 0; ax < 3; ++ax) cor[3 * v + ax] = (double)(int64_t)((double)q[ax] * f->edge);
-        } else {
-          for (int ax = 0; ax < 3; ++ax) cor[3 * v + ax] = f->corner[ax];
-        }
-      }
-      HIP_TRY(ctx, up(nd.start, r_start.data(), (size_t)V * 4));
-      HIP_TRY(ctx, up(nd.count, r_count.data(), (size_t)V * 4));
-      HIP_TRY(ctx, up(nd.old_id, r_old.data(), (size_t)V * 4));
-      HIP_TRY(ctx, up(nd.voxel, i32.data(), (size_t)V * 4));
-      HIP_TRY(ctx, hipMemsetAsync(nd.depth, 0, (size_t)V * 4, st));
-      HIP_TRY(ctx, hipMemsetAsync(nd.epoch, 0, (size_t)V * 4, st));
-      HIP_TRY(ctx, hipMemsetAsync(nd.parent, 0xFF, (size_t)V * 4, st));
-      HIP_TRY(ctx, hipMemsetAsync(nd.first_child, 0xFF, (size_t)V * 4, st));
-      HIP_TRY(ctx, up(nd.corner, cor.data(), (size_t)V * 24));
-      HIP_TRY(ctx, up(nd.edge, edg.data(), (size_t)V * 8));
-      if (all_scheme || keep_scheme) {
-        HIP_TRY(ctx, up(nd.scount, r_count.data(), (size_t)V * 4));
-      } else {
-        HIP_TRY(ctx, hipMemsetAsync(nd.scount, 0, (size_t)V * 4, st));
-      }
-      // the sources above are pageable host vectors that die with this scope
-      HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
+    OCTL_TRY(general_union_roots(f, rq, g));
   }
 
   trace.mark("roots (+ union with old voxels)");
   // voxel keys of this build: kept on the device, decoded on the host only when someone asks
-  OCTL_TRY(devbuf_reserve(ctx, f->vlin_dev, (size_t)std::max<int64_t>(V, 1) * 8));
-  if (fresh && V > 0)
-    HIP_TRY(ctx, hipMemcpyAsync(f->vlin_dev.p, vlin_d, (size_t)V * 8, hipMemcpyDeviceToDevice, st));
+  OCTL_TRY(devbuf_reserve(ctx, f->vlin_dev, (size_t)std::max<int64_t>(g.V, 1) * 8));
+  if (g.fresh && g.V > 0)
+    HIP_TRY(ctx, hipMemcpyAsync(f->vlin_dev.p, g.vlin_d, (size_t)g.V * 8, hipMemcpyDeviceToDevice, st));
+  return OCTL_OK;
+}
 
-  const int cur_epoch = f->epoch + (keep_scheme ? 0 : 1);
-  const int64_t old_internal = have_old ? f->n_internal : 0;
-  int64_t first_new = 0, n_new = V, n_internal = 0;
-  int level = 0;
-
-  int32_t* pos_node = nullptr;
-  // ---- 4. level-0 buffers ---------------------------------------------------------------------------
+// 4. level-0 buffers: node, point index and path word of every position
+int general_level0(octl_forest* f, const BuildRequest& rq, GeneralBuild& g) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t N = rq.N, n_alive = rq.n_alive;
   for (int b = 0; b < 2; ++b) {
     OCTL_TRY(devbuf_reserve(ctx, f->idxbuf[b], (size_t)std::max<int64_t>(n_alive, 1) * 4));
     OCTL_TRY(devbuf_reserve(ctx, f->pathbuf[b], (size_t)std::max<int64_t>(n_alive, 1) * 4));
   }
   OCTL_TRY(devbuf_reserve(ctx, f->pos_node, (size_t)std::max<int64_t>(n_alive, 1) * 4));
-  pos_node = f->pos_node.as<int32_t>();
+  int32_t* pos_node = g.pos_node = f->pos_node.as<int32_t>();
   if (n_alive > 0) {
     const int32_t* l2r = nullptr;
-    if (!fresh) {
-      OCTL_TRY(devbuf_reserve(ctx, f->root_up, (size_t)v_pts * 4));
-      HIP_TRY(ctx, hipMemcpyAsync(f->root_up.p, local2root.data(), (size_t)v_pts * 4,
+    if (!g.fresh) {
+      OCTL_TRY(devbuf_reserve(ctx, f->root_up, (size_t)g.v_pts * 4));
+      HIP_TRY(ctx, hipMemcpyAsync(f->root_up.p, g.local2root.data(), (size_t)g.v_pts * 4,
                                   hipMemcpyHostToDevice, st));
       HIP_TRY(ctx, hipStreamSynchronize(st));
       l2r = f->root_up.as<int32_t>();
     }
     KTimer t(ctx, "init_level0");
-    if (pm)
-      OCTL_LAUNCH(k_pre_level0, dim3(grid_for(N)), dim3(256), 0, st, static_cast<const uint4*>(pre_recs), N, pm,
-                         pos_node, f->idxbuf[pm & 1].as<uint32_t>(), f->pathbuf[pm & 1].as<uint32_t>());
-    else if (cube_fast)
+    if (g.pm)
+      OCTL_LAUNCH(k_pre_level0, dim3(grid_for(N)), dim3(256), 0, st, static_cast<const uint4*>(g.pre_recs), N, g.pm,
+                         pos_node, f->idxbuf[g.pm & 1].as<uint32_t>(), f->pathbuf[g.pm & 1].as<uint32_t>());
+    else if (g.cube_fast)
       OCTL_LAUNCH(k_cube_level0, dim3(grid_for(N)), dim3(256), 0, st, (const double*)f->xyz.as<double>(), N,
                          f->edge, f->corner[0], f->corner[1], f->corner[2],
-                         (const int64_t*)f->pose_off_dev.as<int64_t>(), n_poses, scheme_dev,
+                         (const int64_t*)f->pose_off_dev.as<int64_t>(), rq.n_poses, rq.scheme_dev,
                          ctx->opt.no_exact_digits ? 0 : 1, pos_node,
                          f->idxbuf[0].as<uint32_t>(), f->pathbuf[0].as<uint32_t>());
     else
-      OCTL_LAUNCH(k_init_level0, dim3((unsigned)n_rtiles), dim3(256), 0, st, lin_sorted,
-                         (const uint32_t*)flags, val_sorted, (const uint32_t*)f->path.as<uint32_t>(),
+      OCTL_LAUNCH(k_init_level0, dim3((unsigned)g.n_rtiles), dim3(256), 0, st,
+                         (const uint64_t*)f->lin[g.sorted].as<uint64_t>(), (const uint32_t*)f->flags.as<uint32_t>(),
+                         (const uint32_t*)f->val[g.sorted].as<uint32_t>(), (const uint32_t*)f->path.as<uint32_t>(),
                          n_alive, l2r, pos_node,
                          f->idxbuf[0].as<uint32_t>(), f->pathbuf[0].as<uint32_t>());
     HIP_TRY(ctx, hipGetLastError());
-    if (!all_scheme && !keep_scheme) {
+    if (!rq.all_scheme && !rq.keep_scheme) {
       OCTL_LAUNCH(k_count_scheme, dim3((unsigned)ceil_div(n_alive, 2048)), dim3(256), 0, st,
                          (const int32_t*)pos_node, (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
-                         n_alive, nd.scount);
+                         n_alive, node_ptrs(*g.nt).scount);
       HIP_TRY(ctx, hipGetLastError());
     }
-  }
-
-  trace.mark("level-0 buffers");
-  // ---- 5. level loop ----------------------------------------------------------------------------------
-  std::vector<octl_forest::LevelSeg> segs{{0, V, 0}};
-  LevelLoop L{f, &nt, K, (int)keep_scheme, all_scheme, scheme_dev, old_fc, old_epoch, cur_epoch, max_depth,
-              n_alive, false, first_new, n_new, 0, 0, &segs};
-  L.planar = planar;
-  if (pm) {  // levels 0 .. pm-1 are done: all of their nodes are internal
-    for (int d = 1; d <= pm; ++d) segs.push_back({top_base(d), top_base(d + 1), d});
-    L.first_new = top_base(pm);
-    L.n_new = (int64_t)1 << (3 * pm);
-    L.n_internal = top_base(pm);
-    L.level = pm;
-    L.gx = static_cast<const double*>(pre_recs);
-    L.xs = 4;
-  }
-  OCTL_TRY(run_level_loop(L));
-  nd = node_ptrs(nt);
-  n_internal = L.n_internal;
-  level = L.level;
-  trace.mark("level loop");
-  // ---- 6. leaf-ordered arrays and the block table ------------------------------------------------------
-  if (n_alive > 0) {
-    OCTL_TRY(devbuf_reserve(ctx, f->ord_idx, (size_t)n_alive * 4));
-    OCTL_TRY(devbuf_reserve(ctx, f->xyz_ord, (size_t)n_alive * 24));
-    {
-      // (a fused gather + block-head count, eight positions per thread, was measured SLOWER on BASELINE config 4:
-      //  2.39 + 0.24 ms against 1.95 + 0.39 ms - eight dependent random gathers per thread hide less latency
-      //  than one per thread at full occupancy)
-      KTimer t(ctx, "finalize");
-      if (pm)
-        OCTL_LAUNCH(k_finalize_rec, dim3(grid_for(n_alive)), dim3(256), 0, st,
-                           (const int32_t*)pos_node, (const int32_t*)nd.depth,
-                           (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
-                           (const uint32_t*)f->idxbuf[1].as<uint32_t>(), static_cast<const uint4*>(pre_recs),
-                           n_alive, f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>());
-      else
-        OCTL_LAUNCH(k_finalize, dim3(grid_for(n_alive)), dim3(256), 0, st,
-                           (const int32_t*)pos_node, (const int32_t*)nd.depth,
-                           (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
-                           (const uint32_t*)f->idxbuf[1].as<uint32_t>(),
-                           (const double*)f->xyz.as<double>(), n_alive, f->ord_idx.as<uint32_t>(),
-                           f->xyz_ord.as<double>());
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }
-  trace.mark("finalize (enqueue)");
-  int64_t n_blocks = 0;
-  const int64_t n_ord_before = f->n_ord;
-  f->n_ord = n_alive;
-  OCTL_TRY(forest_make_blocks(f));
-  {
-    uint32_t e = 0;
-    OCTL_TRY(forest_finish_blocks(f, &e));  // the build's final synchronisation
-    n_blocks = f->n_blocks;
-    if (e) {
-      f->n_ord = n_ord_before;
-      f->n_blocks = 0;
-      f->built = false;  // the leaf-ordered arrays were overwritten
-      return octl_set_error(ctx, OCTL_E_DOMAIN,
-                            "a point lies outside the cube of a node that is being subdivided "
-                            "(the reference raises IndexError or picks a wrong child here)");
-    }
-  }
-
-  trace.mark("blocks + final sync");
-  // ---- commit --------------------------------------------------------------------------------------------
-  f->cur ^= 1;
-  f->n_voxels = V;
-  if (fresh) {
-    f->vkeys.clear();
-    f->vkeys_stale = true;
-    f->vl_min[0] = bb[0]; f->vl_min[1] = bb[1]; f->vl_min[2] = bb[2];
-    f->vl_ny = ny;
-    f->vl_nz = nz;
-  } else {
-    f->vkeys.swap(new_vkeys);
-    f->vkeys_stale = false;
-  }
-  f->level_segs.swap(segs);
-  f->built = true;
-  f->epoch = cur_epoch;
-  f->n_ord = n_alive;
-  f->n_blocks = n_blocks;
-  f->n_internal = n_internal;
-  // nodes inherit an older epoch only from a previous scheme that had internal nodes
-  f->uniform_epoch = keep_scheme ? f->uniform_epoch : !(have_old && old_internal > 0);
-  f->max_depth_reached = level;
-  f->mask_valid = false;
-  f->store_dirty = false;
-  f->vcode_valid = false;
-  f->built_store = f->n_store;
-  f->built_poses = n_poses;
-  f->append_only = true;
-  if (planar) {  // what the decisions saw, for octl_forest_get_split_stats (the statistic is in place already)
-    OCTL_TRY(devbuf_reserve(ctx, f->split_n, (size_t)std::max<int64_t>(nt.n, 1) * 4));
-    if (nt.n > 0)
-      HIP_TRY(ctx, hipMemcpyAsync(f->split_n.p, nt.scount.p, (size_t)nt.n * 4, hipMemcpyDeviceToDevice, st));
-    f->split_stats_nodes = nt.n;
-    f->split_stats_valid = true;
-  }
-  if (info) {
-    info->n_points = n_alive;
-    info->n_voxels = V;
-    info->n_nodes = nt.n;
-    info->n_internal = n_internal;
-    info->n_blocks = n_blocks;
-    info->max_depth = level;
-    info->n_levels = level;
   }
   return OCTL_OK;
+}
+
+// 5. level loop, from the roots or - behind a prefix partition - from level pm
+int general_level_loop(octl_forest* f, const BuildRequest& rq, GeneralBuild& g, BuildOutcome& o) {
+  NodeTable& old = f->nodes[f->cur];
+  const int32_t* old_fc = g.have_old ? old.first_child.as<int32_t>() : nullptr;
+  const int32_t* old_epoch = g.have_old ? old.epoch.as<int32_t>() : nullptr;
+  o.segs = {{0, g.V, 0}};
+  LevelLoop L{f, g.nt, rq.K, (int)rq.keep_scheme, rq.all_scheme, rq.scheme_dev, old_fc, old_epoch, rq.cur_epoch,
+              rq.max_depth, rq.n_alive, false, 0, g.V, 0, 0, &o.segs};
+  L.planar = rq.planar;
+  if (g.pm) {  // levels 0 .. pm-1 are done: all of their nodes are internal
+    for (int d = 1; d <= g.pm; ++d) o.segs.push_back({top_base(d), top_base(d + 1), d});
+    L.first_new = top_base(g.pm);
+    L.n_new = (int64_t)1 << (3 * g.pm);
+    L.n_internal = top_base(g.pm);
+    L.level = g.pm;
+    L.gx = static_cast<const double*>(g.pre_recs);
+    L.xs = PART_REC_DOUBLES;
+  }
+  OCTL_TRY(run_level_loop(L));
+  o.n_internal = L.n_internal;
+  o.levels = L.level;
+  return OCTL_OK;
+}
+
+// 6. leaf-ordered arrays
+int general_finalize(octl_forest* f, const BuildRequest& rq, GeneralBuild& g) {
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t n_alive = rq.n_alive;
+  if (n_alive <= 0) return OCTL_OK;
+  NodePtrs nd = node_ptrs(*g.nt);
+  OCTL_TRY(devbuf_reserve(ctx, f->ord_idx, (size_t)n_alive * 4));
+  OCTL_TRY(devbuf_reserve(ctx, f->xyz_ord, (size_t)n_alive * 24));
+  // (a fused gather + block-head count, eight positions per thread, was measured SLOWER on BASELINE config 4:
+  //  2.39 + 0.24 ms against 1.95 + 0.39 ms - eight dependent random gathers per thread hide less latency
+  //  than one per thread at full occupancy)
+  KTimer t(ctx, "finalize");
+  if (g.pm)
+    OCTL_LAUNCH(k_finalize_rec, dim3(grid_for(n_alive)), dim3(256), 0, st,
+                       (const int32_t*)g.pos_node, (const int32_t*)nd.depth,
+                       (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
+                       (const uint32_t*)f->idxbuf[1].as<uint32_t>(), static_cast<const uint4*>(g.pre_recs),
+                       n_alive, f->ord_idx.as<uint32_t>(), f->xyz_ord.as<double>());
+  else
+    OCTL_LAUNCH(k_finalize, dim3(grid_for(n_alive)), dim3(256), 0, st,
+                       (const int32_t*)g.pos_node, (const int32_t*)nd.depth,
+                       (const uint32_t*)f->idxbuf[0].as<uint32_t>(),
+                       (const uint32_t*)f->idxbuf[1].as<uint32_t>(),
+                       (const double*)f->xyz.as<double>(), n_alive, f->ord_idx.as<uint32_t>(),
+                       f->xyz_ord.as<double>());
+  HIP_TRY(ctx, hipGetLastError());
+  return OCTL_OK;
+}
+
+// The general route: schemes with history the bucket build does not take, keep_scheme re-placements, planar builds,
+// big single cubes, and whatever the bucket build declined or handed back.
+int build_general_route(octl_forest* f, const BuildRequest& rq, BuildTrace& trace, BuildOutcome& o) {
+  OCTL_TRY(forest_sync_vkeys(f));  // the previous scheme's voxels persist (no-op when fresh)
+  trace.mark("sync_vkeys");
+  GeneralBuild g;
+  OCTL_TRY(general_keys(f, rq, g));
+  trace.mark("keys + bbox readback");
+  OCTL_TRY(general_sort(f, rq, g));
+  trace.mark("sort (enqueue)");
+  OCTL_TRY(general_roots(f, rq, g, trace));
+  const int64_t old_internal = g.have_old ? f->n_internal : 0;
+  OCTL_TRY(general_level0(f, rq, g));
+  trace.mark("level-0 buffers");
+  OCTL_TRY(general_level_loop(f, rq, g, o));
+  trace.mark("level loop");
+  OCTL_TRY(general_finalize(f, rq, g));
+  trace.mark("finalize (enqueue)");
+  o.nt = g.nt;
+  o.n_voxels = g.V;
+  o.blocks_made = false;
+  // roots made on the device: their keys stay there as linear keys (f->vlin_dev) with this geometry; merged with the
+  // previous scheme's voxels on the host: the merged list is the forest's
+  o.fresh_keys = g.fresh;
+  if (g.fresh) {
+    o.vl_min[0] = g.bb[0]; o.vl_min[1] = g.bb[1]; o.vl_min[2] = g.bb[2];
+    o.vl_ny = g.ny;
+    o.vl_nz = g.nz;
+  } else {
+    o.new_vkeys.swap(g.new_vkeys);
+  }
+  // nodes inherit an older epoch only from a previous scheme that had internal nodes; a keep_scheme re-placement
+  // changes no epoch
+  o.uniform_epoch = rq.keep_scheme ? f->uniform_epoch : !(g.have_old && old_internal > 0);
+  // the level loop leaves no listing order behind: order.hip computes it
+  o.fast_order_valid = false;
+  // NO REASON FOUND: a fresh count-driven build from all poses bounds its leaves by K here exactly as on the bucket
+  // route, which promises K; this route has always left "no bound" 
+  o.max_block_hint = INT64_MAX;
+  // only this route builds planar schemes
+  o.publish_split_stats = rq.planar != nullptr;
+  return OCTL_OK;
+}
+
+}  // namespace
+
+int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
+                 int32_t keep_scheme, int32_t max_depth, octl_build_info* info, const PlanarRule* planar) {
+  octl_ctx* ctx = f->ctx;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  BuildRequest rq{};
+  rq.K = K;
+  rq.keep_scheme = keep_scheme;
+  rq.max_depth = max_depth <= 0 ? 63 : max_depth;
+  rq.planar = planar;
+  rq.N = f->n_store;
+  rq.n_poses = (int)f->pose_off.size() - 1;
+  OCTL_TRY(build_validate(f, rq, scheme_mask, n_mask));
+  rq.all_scheme = true;
+  if (scheme_mask && !keep_scheme)
+    for (int p = 0; p < rq.n_poses; ++p) rq.all_scheme = rq.all_scheme && scheme_mask[p];
+  f->fast_order_valid = false;  // (the block table is about to change)
+  f->pooled_valid = false;
+  f->max_block_hint = INT64_MAX;
+  BuildTrace trace;
+  trace.on = ctx->opt.trace_build != 0;
+
+  OCTL_TRY(build_begin(f, rq, scheme_mask));
+  int placed = 0;
+  OCTL_TRY(build_try_incremental(f, rq, trace, info, &placed));
+  if (placed) return OCTL_OK;
+  rq.n_alive = f->n_alive;
+  rq.cur_epoch = f->epoch + (keep_scheme ? 0 : 1);
+
+  BuildOutcome out;
+  bool bucket_built = false;
+  OCTL_TRY(build_bucket_route(f, rq, trace, out, &bucket_built));
+  if (!bucket_built) OCTL_TRY(build_general_route(f, rq, trace, out));
+  if (!out.blocks_made) OCTL_TRY(build_block_table(f, rq.n_alive, &out.n_blocks));
+  if (!bucket_built) trace.mark("blocks + final sync");  // (the bucket route's marks end with its level loop)
+  return build_commit(f, rq, out, info);
 }

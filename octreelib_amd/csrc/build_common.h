@@ -59,6 +59,18 @@ struct BucketBuildResult {
 int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, BucketBuildResult* r);
 
 // bucket_build.hip: one stable partition of a single cube's store by the child digits of its first pm levels
-// (records of 32 bytes: x, y, z f64 | six digits << 1 | bad | store index + scheme bit)
+// (records of 32 bytes: x, y, z f64 | six digits << 1 | bad | store index + scheme bit).  The layout as the readers
+// of the records in build.hip use it (general_level0: k_pre_level0, general_level_loop, general_finalize:
+// k_finalize_rec); bucket_build.hip ties it to PartRec and PATH_EAGER.
+constexpr int PART_REC_BYTES = 32;
+constexpr int PART_REC_QUADS = PART_REC_BYTES / 16;      // 16-byte accesses per record
+constexpr int PART_REC_DOUBLES = PART_REC_BYTES / 8;     // stride of the coordinates, in doubles (LevelLoop::xs)
+constexpr int PART_REC_VP_WORD = 6;                      // 32-bit word that holds vp ...
+constexpr int PART_REC_IDX_WORD = 7;                     // ... and the one that holds the store index
+constexpr int PART_VP_DIGITS = 6;                        // child digits vp carries, first level highest
+constexpr int PART_VP_DIGIT_BITS = 3 * PART_VP_DIGITS;
+constexpr int PART_VP_DIGIT_SHIFT = 1;
+constexpr uint32_t PART_VP_DIGIT_MASK = (1u << PART_VP_DIGIT_BITS) - 1u;
+constexpr uint32_t PART_VP_BAD = 1u;                     // the point is outside the cube at some level
 int forest_prefix_partition(octl_forest* f, int pm, const void** recs_out, const uint32_t** bstart, uint32_t* bstride,
                             const uint32_t** bad_flag);
