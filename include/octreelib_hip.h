@@ -372,11 +372,17 @@ int octl_forest_settle(octl_forest* f, int64_t* n_alive);
 /* OctreeNode.filter (octree/octree.py:102-112) for point-count predicates, on the device: every leaf of
  * the poses with slot_sel[slot] != 0 whose point count is outside [lo, hi] is emptied (its points
  * leave the tree), followed by the same compaction as apply_mask.  A criterion `len(points) >= c` is
- * [c, INT64_MAX], `len(points) < c` is [0, c-1], several criteria intersect.                    */
+ * [c, INT64_MAX], `len(points) < c` is [0, c-1], several criteria intersect; lo > hi empties every
+ * leaf of the selected poses.  A forest that still holds an unapplied RANSAC mask (octl_forest_ransac
+ * without octl_forest_apply_mask*) keeps it: the filter clears the bytes of the leaves it empties in
+ * that mask and ONE compaction applies both - the points the RANSAC mask dropped leave as well, also
+ * from poses the filter did not select.  The sizes the filter compares are those of the block table
+ * before the call (points the pending mask is about to drop still count).                       */
 int octl_forest_filter_count(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int64_t lo,
                              int64_t hi, int64_t* n_alive);
 /* Drop points by an explicit host mask over storage positions (filter / map_leaf_points
- * paths of the Python layer for arbitrary callables).                                       */
+ * paths of the Python layer for arbitrary callables): n = the forest's point count, one byte per
+ * position; a byte of 0 drops the point, ANY other value keeps it (as octl_forest_apply_mask).  */
 int octl_forest_apply_host_mask(octl_forest* f, const uint8_t* mask, int64_t n,
                                 int64_t* n_alive);
 
