@@ -319,6 +319,46 @@ int octl_forest_registration_system_device(octl_forest* f, const double* xyz_dev
                                            double max_distance, double huber_delta, double* sys_dev,
                                            int64_t* counts_dev, int32_t* node_dev, int32_t* row_dev,
                                            double* residual_dev);
+/* Multi-pose plane adjustment: for ONE rigid transform PER selected pose, the point-to-plane normal equations of every
+ * pose against the leaf planes pooled at those transforms - what one block-Jacobi iteration of a sliding-window plane
+ * adjustment needs from the device (the 6x6 solves and the iteration are the caller's; octreelib_amd/adjustment.py has
+ * them and the NumPy definition of every number below).  slot_sel / n_sel select the poses as
+ * octl_forest_pooled_leaf_stats takes them (NULL: all); S = number of selected poses, in ascending slot order;
+ * transforms = S row-major 3x4 (R | t), increments applied to the points as they were inserted (leaf membership stays
+ * what the last build made it); origin = c.  Per selected (leaf, pose) block, anchor a = the leaf's centre: n, s = sum d,
+ * M = sum d d^T, d = x - a, by the chunked wave reduction of octl_forest_pooled_leaf_stats (80 bytes per block, made
+ * once per map and selection and kept until a call changes the forest's contents or scheme - the list of
+ * octl_forest_pooled_leaf_stats - or the selection is another one).  Per call no point is read: the moments move in
+ * closed form, a' = ((R_i0 a_x + R_i1 a_y) + R_i2 a_z) + t_i (rounded f64, no fma), delta = a' - a, s'' = R s + n delta,
+ * M'' = R M R^T + delta (R s)^T + (R s) delta^T + n delta delta^T; a leaf pools its blocks in ascending slot order,
+ * mean = a + S / N, covariance, eigen-decomposition and sign rule of octl_forest_pooled_leaf_stats (at identity
+ * transforms: its bits), plane normal = the smallest eigenvalue's vector.  A leaf is USED iff N >= min_points, at least
+ * min_poses of its selected blocks are non-empty, lambda0 is finite and (max_variance < 0 or lambda0 <= max_variance).
+ * With r = normal . (x - mean) and J = [(x - c) x normal, normal] over the points x of pose p in used leaves:
+ *   sums[p][0..21)  = upper triangle of H_p = sum J J^T, row-major,  sums[p][21..27) = g_p = sum J r,
+ *   sums[p][27] = cost_p = sum r^2 / 2,  counts[p][0] = those points,  counts[p][1] = the pose's blocks in used leaves,
+ *   n_leaves[0] = leaves pooled, n_leaves[1] = leaves used.
+ * Blocks of unused leaves are skipped, never multiplied by zero.  The sums of a pose are reduced in a fixed tree that
+ * depends on that pose's selected-block count nb alone (chunks of 1024 blocks; no floating-point atomics): with eps =
+ * 2^-53 and D = 22 + ceil(ceil(nb / 1024) / 256) every entry is within (D + 32) eps sum |term| of the exact sum of the
+ * block terms formed from the block moments and the leaf table's plane bits, |term| taken product by product
+ * (DESIGN.md 4.10).  Three kernels and one host wait on a prepared forest; nothing to reduce (no selected block): no
+ * launch, sums = +0.0, counts = 0.  OCTL_E_STATE before the first build; OCTL_E_INVALID: n_sel is not the number of
+ * poses, a NULL pointer, a non-finite transform or origin (checked before anything runs).  Read-only apart from its
+ * own tables.  No reference counterpart: the reference has no adjustment.                                           */
+int octl_forest_adjustment_system(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, const double* transforms,
+                                  const double origin[3], int32_t min_points, int32_t min_poses, double max_variance,
+                                  double* sums, int64_t* counts, int64_t n_leaves[2]);
+/* The tables behind the last octl_forest_adjustment_system call (OCTL_E_STATE if there is none on the forest as it is
+ * now).  Leaves, in ascending node id: node, count (pooled points), mean (3), normal (3), lambda0, used (u8);
+ * *n_leaves = their number, rows are written only when cap_leaves >= *n_leaves (size query: cap_leaves = 0).  Blocks,
+ * in (node, slot) order: blk_node, blk_slot, blk_moments (10 f64 per block: n, sum d (3), sum d d^T xx xy xz yy yz zz
+ * about the leaf's centre, at the inserted positions - they do not depend on any transform); *n_blocks, cap_blocks
+ * likewise.  Any output may be NULL.  One host wait.  No reference counterpart.                                     */
+int octl_forest_adjustment_tables(octl_forest* f, int64_t cap_leaves, int32_t* node, int64_t* count, double* mean,
+                                  double* normal, double* lambda0, uint8_t* used, int64_t* n_leaves,
+                                  int64_t cap_blocks, int32_t* blk_node, int32_t* blk_slot, double* blk_moments,
+                                  int64_t* n_blocks);
 /* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
 int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 

@@ -12,6 +12,8 @@ for gfx950.  There is no CPU fallback: without liboctree_hip.so and a GPU every 
 raises.
 """
 
+from octreelib_amd.adjustment import (Adjustment, AdjustmentLeaves, AdjustmentSystem, BlockMoments, adjust_np,
+                                      adjustment_system_np, block_moments_np)
 from octreelib_amd.criteria import MaxPoints, NotPlanar
 from octreelib_amd.feed import DeviceCloud, ScanPipeline, pinned_empty, upload_async
 from octreelib_amd.query import (LeafPlanes, PointToPlane, locate_np, point_to_plane_np,
@@ -22,4 +24,5 @@ from octreelib_amd.registration import (Alignment, RegistrationSystem, align_np,
 __version__ = "0.1.0"
 __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "LeafPlanes",
            "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np", "RegistrationSystem",
-           "Alignment", "registration_system_np", "align_np", "se3_exp", "transform_np", "__version__"]
+           "Alignment", "registration_system_np", "align_np", "se3_exp", "transform_np", "AdjustmentSystem", "Adjustment",
+           "AdjustmentLeaves", "BlockMoments", "adjustment_system_np", "adjust_np", "block_moments_np", "__version__"]

@@ -735,6 +735,88 @@ class Forest:
             if out.value:
                 lib.octl_dev_free(h, out)
 
+    # -- plane adjustment (octreelib_amd/adjustment.py is the host definition) ---------------------------------------------
+    def _adjust_selection(self, slots):
+        """(selection mask or None, its length, the selected slots in ascending order)"""
+        if slots is None:
+            return None, 0, list(range(self.n_slots))
+        chosen = sorted(set(int(s) for s in slots))
+        sel = np.zeros(max(self.n_slots, 1), dtype=np.uint8)[:self.n_slots]
+        sel[chosen] = 1
+        return np.ascontiguousarray(sel), self.n_slots, chosen
+
+    def adjustment_origin(self) -> np.ndarray:
+        """Centre of the box spanned by the scheme's root cubes (the single cube's centre): the default origin."""
+        from octreelib_amd.adjustment import root_box_centre
+
+        nd = self.nodes
+        roots = np.nonzero(nd["depth"] == 0)[0] if len(nd["depth"]) else np.zeros(0, dtype=np.int64)
+        return root_box_centre(nd["corner"][roots], nd["edge"][roots])
+
+    def adjustment_system(self, transforms=None, slots=None, origin=None, min_points: int = 8, min_poses: int = 2,
+                          max_variance=None, leaves: bool = False, pose_numbers=None):
+        """The per-pose plane-adjustment systems at `transforms` (octl_forest_adjustment_system: the block moments
+        are made once per map and selection, a call is three kernels and one host wait).  pose_numbers: the names the
+        result carries for the selected slots (ascending slot order; None: the slots themselves)."""
+        from octreelib_amd.adjustment import _as_origin, as_transforms, system_from_device
+
+        self.ensure_built()
+        sel, n_sel, chosen = self._adjust_selection(slots)
+        S = len(chosen)
+        T = np.ascontiguousarray(as_transforms(transforms, S).reshape(S, 12))
+        c = np.ascontiguousarray(_as_origin(self.adjustment_origin() if origin is None else origin))
+        mv = -1.0 if max_variance is None else float(max_variance)
+        sums = np.zeros((S, 28), dtype=np.float64)
+        counts = np.zeros((S, 2), dtype=np.int64)
+        n_leaves = np.zeros(2, dtype=np.int64)
+        self.ctx.check(self.lib.octl_forest_adjustment_system(
+            self.handle, nat.ptr(sel), n_sel, nat.ptr(T), nat.ptr(c), int(min_points), int(min_poses), mv,
+            nat.ptr(sums), nat.ptr(counts), nat.ptr(n_leaves)))
+        out = system_from_device(sums, counts, n_leaves, c, chosen if pose_numbers is None else pose_numbers)
+        if leaves:
+            out.leaves, out.blocks = self.adjustment_tables(slots, out.pose_numbers, c)
+        return out
+
+    def adjustment_tables(self, slots=None, pose_numbers=None, origin=None):
+        """(AdjustmentLeaves, BlockMoments) behind the last adjustment_system call (octl_forest_adjustment_tables)."""
+        from octreelib_amd.adjustment import AdjustmentLeaves, BlockMoments
+
+        nl, nb = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_adjustment_tables(self.handle, 0, None, None, None, None, None, None,
+                                                              C.byref(nl), 0, None, None, None, C.byref(nb)))
+        L, B = nl.value, nb.value
+        node, count = np.empty(L, dtype=np.int32), np.empty(L, dtype=np.int64)
+        mean, normal, lam = np.empty((L, 3)), np.empty((L, 3)), np.empty(L)
+        used = np.empty(L, dtype=np.uint8)
+        bnode, bslot, mom = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32), np.empty((B, 10))
+        if L:
+            self.ctx.check(self.lib.octl_forest_adjustment_tables(
+                self.handle, L, nat.ptr(node), nat.ptr(count), nat.ptr(mean), nat.ptr(normal), nat.ptr(lam),
+                nat.ptr(used), C.byref(nl), B, nat.ptr(bnode), nat.ptr(bslot), nat.ptr(mom), C.byref(nb)))
+        nd = self.nodes
+        anchor = nd["corner"][bnode] + (nd["edge"][bnode] / 2.0)[:, None] if B else np.empty((0, 3))
+        chosen = list(range(self.n_slots)) if slots is None else sorted(set(int(x) for x in slots))
+        names = chosen if pose_numbers is None else list(pose_numbers)
+        pose = np.searchsorted(np.asarray(chosen, dtype=np.int64), bslot).astype(np.int32)   # (index into the selection)
+        blocks = BlockMoments(bnode, pose, mom[:, 0].astype(np.int64), mom[:, 1:4].copy(), mom[:, 4:].copy(),
+                              np.ascontiguousarray(anchor, dtype=np.float64), names,
+                              None if origin is None else np.asarray(origin, dtype=np.float64))
+        return AdjustmentLeaves(node, count, mean, normal, lam, used.astype(bool)), blocks
+
+    def adjust(self, initial=None, slots=None, origin=None, min_points: int = 8, min_poses: int = 2,
+               max_variance=None, fixed=None, max_iterations: int = 200, tolerance: float = 1e-9,
+               damping: float = 0.0, pose_numbers=None):
+        """Block-Jacobi plane adjustment (adjustment.adjust_np) over the device's systems: the block moments are made
+        once, an iteration is three kernels, one download of S x 240 bytes and S 6x6 solves on the host."""
+        from octreelib_amd.adjustment import adjust_np
+
+        self.ensure_built()
+        _, _, chosen = self._adjust_selection(slots)
+        c = self.adjustment_origin() if origin is None else origin
+        system = lambda T: self.adjustment_system(T, slots, c, min_points, min_poses, max_variance, False,
+                                                  pose_numbers)
+        return adjust_np(system, len(chosen), initial, fixed, max_iterations, tolerance, damping)
+
     @property
     def perm(self) -> np.ndarray:
         """perm[i] = index (in the concatenation of all pose clouds, slot order) of the point at

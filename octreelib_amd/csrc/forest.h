@@ -122,6 +122,21 @@ struct octl_forest {
   DevBuf q_stage;               // staging of the host forms of the queries (points in, answers out)
   DevBuf rg_rows;               // octl_forest_registration_system (register.hip): per-chunk partial sums, the result
 
+  // octl_forest_adjustment_system (adjust.hip).  Prepared once per map and pose selection, stamped as the pooled table
+  // is (every entry point that clears pooled_valid clears adj_valid; another selection recomputes):
+  //  adj_tab   the selected (leaf, pose) blocks in (node, slot) order - 80-byte moments {n, sum d, sum d d^T} about the
+  //            leaf's centre, leaf row and selection index of every block - the leaves (first block, node, anchor), the
+  //            second order of the same blocks by (slot, node) and its chunks of at most 1024 blocks of one pose;
+  //  adj_sort  scratch of the two sorts (their histograms go through pl_hist, which nobody keeps anything in);
+  //  adj_call  what one call writes: transforms, the plane row of every leaf, the per-chunk partial sums, the result.
+  DevBuf adj_tab, adj_sort, adj_call;
+  bool adj_valid = false;
+  bool adj_called = false;           // adj_call holds the leaf table of a call on this preparation
+  std::vector<uint8_t> adj_sel;      // the pose selection it was made for (empty: every pose)
+  std::vector<int32_t> adj_slots;    // slot of every selected pose, ascending
+  std::vector<int64_t> adj_chunk_off;  // [S + 1] first chunk of every selected pose
+  int64_t adj_blocks = 0, adj_rows = 0;  // selected blocks, leaves that hold one
+
   // leaf-ordered arrays of the last build
   DevBuf ord_idx;    // u32 [n_ord] store index of the point at storage position i
   DevBuf xyz_ord;    // f64 [n_ord][3]

@@ -15,6 +15,7 @@ from octreelib_amd.internal.voxel import Voxel, VoxelBase
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase
 from octreelib_amd.query import HostMap, LeafPlanes, PointToPlane
+from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
 __all__ = ["OctreeManager"]
@@ -176,6 +177,44 @@ class OctreeManager(VoxelBase):
                                           max_iterations, tolerance, damping)
         return self._forest.align(points, initial, sel, min_points, max_variance, max_distance, huber_delta,
                                   max_iterations, tolerance, damping)
+
+    def adjustment_system(self, transforms=None, pose_numbers: Optional[List[int]] = None, origin=None,
+                          min_points: int = 8, min_poses: int = 2, max_variance: Optional[float] = None,
+                          leaves: bool = False) -> AdjustmentSystem:
+        """The plane-adjustment systems of the given poses (None: all) at one rigid transform per pose (4x4 or 3x4,
+        increments applied to the points as they were inserted; None: identities, in the order the poses were
+        inserted): an AdjustmentSystem (H (S, 6, 6), g, cost per pose, total_cost, n_points, n_blocks, n_leaves,
+        origin) against the leaf planes pooled AT those transforms; .solve() is one block-Jacobi step.  A leaf is used
+        with at least min_points pooled points, min_poses poses that see it and a smallest eigenvalue of at most
+        max_variance; origin None: the centre of the cube; leaves: the leaf table and the
+        block moments come back too.  The map is reduced to 80 bytes per (leaf, pose) block once; a call reads no
+        point: three kernels and one host wait (octreelib_amd/adjustment.py has the definition)."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().adjustment_system(transforms, sel, origin, min_points, min_poses, max_variance,
+                                                      leaves)
+        return self._forest.adjustment_system(transforms, sel, origin, min_points, min_poses, max_variance, leaves,
+                                              self._adjust_names(pose_numbers))
+
+    def adjust(self, initial=None, pose_numbers: Optional[List[int]] = None, origin=None, min_points: int = 8,
+               min_poses: int = 2, max_variance: Optional[float] = None, fixed=None, max_iterations: int = 200,
+               tolerance: float = 1e-9, damping: float = 0.0) -> Adjustment:
+        """Block-Jacobi plane adjustment of the given poses from `initial` (None: identities): an Adjustment
+        (transforms (S, 4, 4), iterations, converged, costs, reason).  `fixed` (pose numbers; None: the first selected
+        pose) stay where they are.  Per iteration T_p <- se3_exp(xi_p, origin) T_p; ends when max |xi_p| < tolerance,
+        at max_iterations, or - not converged, last good transforms - when a free pose has fewer than six used
+        points.  The transforms are returned, not written back into the map."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().adjust(initial, sel, origin, min_points, min_poses, max_variance, fixed,
+                                           max_iterations, tolerance, damping)
+        return self._forest.adjust(initial, sel, origin, min_points, min_poses, max_variance, fixed, max_iterations,
+                                   tolerance, damping, self._adjust_names(pose_numbers))
+
+    def _adjust_names(self, pose_numbers):
+        """The selected pose numbers in ascending slot order: the order of the transforms and of every result row."""
+        chosen = self._slots if pose_numbers is None else set(pose_numbers)
+        return [p for p, _ in sorted(self._slots.items(), key=lambda kv: kv[1]) if p in chosen]
 
     def node_cubes(self):
         """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""

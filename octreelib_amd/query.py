@@ -209,6 +209,7 @@ class HostMap:
         cubes = [(v.corner_min, v.edge_length) for leaves in leaves_by_pose.values() for v in leaves]
         self.nodes, self._ids = node_table_from_leaves(roots, cubes)
         self.voxels = np.array([np.asarray(c, dtype=np.float64) for c, _ in roots]).reshape(-1, 3).astype(np.int64)
+        self._roots = roots
 
     def _id(self, leaf) -> int:
         return self._ids[(tuple(float(x) for x in np.asarray(leaf.corner_min, dtype=np.float64)),
@@ -247,3 +248,30 @@ class HostMap:
         system = lambda T, c: registration_system_np(self.locate, planes, pts, T, c, min_points, max_variance,
                                                      max_distance, huber_delta)
         return align_np(system, initial, max_iterations, tolerance, damping)
+
+    def block_moments(self, pose_numbers=None):
+        """adjustment.BlockMoments of the chosen poses (insertion order), moments in np.longdouble returned as f64."""
+        from octreelib_amd.adjustment import block_moments_np, root_box_centre
+
+        chosen = list(self._leaves) if pose_numbers is None else [p for p in self._leaves if p in set(pose_numbers)]
+        rows = [(self._id(v), k, np.asarray(v.corner_min, dtype=np.float64) + np.float64(v.edge_length) / 2.0,
+                 v.get_points()) for k, p in enumerate(chosen) for v in self._leaves[p]]
+        origin = root_box_centre([c for c, _ in self._roots], [e for _, e in self._roots]) if self._roots else None
+        bm = block_moments_np(rows, chosen, origin, dtype=np.longdouble)
+        bm.s, bm.M = bm.s.astype(np.float64), bm.M.astype(np.float64)
+        return bm
+
+    def adjustment_system(self, transforms=None, pose_numbers=None, origin=None, min_points=8, min_poses=2,
+                          max_variance=None, leaves=False):
+        from octreelib_amd.adjustment import adjustment_system_np
+
+        return adjustment_system_np(self.block_moments(pose_numbers), transforms, origin, min_points, min_poses,
+                                    max_variance, leaves=leaves)
+
+    def adjust(self, initial=None, pose_numbers=None, origin=None, min_points=8, min_poses=2, max_variance=None,
+               fixed=None, max_iterations=200, tolerance=1e-9, damping=0.0):
+        from octreelib_amd.adjustment import adjust_np, adjustment_system_np
+
+        bm = self.block_moments(pose_numbers)      # (once: the map does not change while it is adjusted)
+        system = lambda T: adjustment_system_np(bm, T, origin, min_points, min_poses, max_variance)
+        return adjust_np(system, len(bm.pose_numbers), initial, fixed, max_iterations, tolerance, damping)
