@@ -290,6 +290,31 @@ int octl_forest_point_to_plane(octl_forest* f, const double* xyz, int64_t n, int
 int octl_forest_point_to_plane_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t min_points,
                                       double max_variance, int32_t* node_dev, int32_t* row_dev,
                                       double* distance_dev);
+/* The stored points nearest to every query point, within max_distance: exact k-nearest neighbours across leaf walls.
+ * For query q and stored point p: dx = q_x - p_x (dy, dz likewise), d2 = (dx dx + dy dy) + dz dz in f64 with every
+ * product and sum rounded (no fma).  Candidates are the points of the selected poses (slot_sel: n_sel = number of
+ * poses flags, NULL = every pose) that are alive and in the leaf-ordered arrays - what a mask or filter removed is
+ * never returned - with d2 <= max_distance * max_distance (inclusive).  Row i of the (n, k) outputs holds the k best
+ * in ascending (d2, slot, index): slot_out = the pose slot, index_out = the point's row in that pose's cloud as it
+ * was inserted (the value of octl_forest_get_perm minus the pose's offset; masks and filters do not renumber it),
+ * d2_out = d2; places beyond count_out[i] <= k hold -1, -1, +inf.  A query with a coordinate that is not finite has
+ * count 0.  The order is total, so the answer is a function of the input: octreelib_amd/query.py: nearest_np is the
+ * same by brute force, bit for bit.
+ * OCTL_E_INVALID: k outside 1 .. OCTL_NN_MAX_K; max_distance not finite or <= 0; a grid with max_distance above twice
+ * the voxel edge (a query would touch more than 5 voxels per axis: the cap bounds a call's cost).  OCTL_E_STATE:
+ * before the first build; a forest whose rows map_leaf_points moved outside their leaves (octl_forest_set_contents),
+ * where no cube bounds what it holds.  The index of the blocks by node is made by the call that finds it missing,
+ * stale or made for another selection (a few launches and one wait); with it in place a call is one kernel, plus
+ * one upload, the downloads and one wait.  No reference counterpart.                                              */
+#define OCTL_NN_MAX_K 8
+int octl_forest_nearest(octl_forest* f, const double* xyz, int64_t n, int32_t k, double max_distance,
+                        const uint8_t* slot_sel, int32_t n_sel, int32_t* slot_out, int64_t* index_out, double* d2_out,
+                        int32_t* count_out);
+/* The same with pointers from octl_dev_alloc (slot_sel stays a host array): one kernel, nothing is downloaded and
+ * the host does not wait.  No reference counterpart.                                                             */
+int octl_forest_nearest_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t k, double max_distance,
+                               const uint8_t* slot_sel, int32_t n_sel, int32_t* slot_dev, int64_t* index_dev,
+                               double* d2_dev, int32_t* count_dev);
 /* The point-to-plane normal equations of a scan against the pooled leaf planes, for ONE rigid transform: what a
  * Gauss-Newton step of scan-to-map registration needs from the device (the 6x6 solve and the iteration are the
  * caller's; octreelib_amd/registration.py has them and the NumPy definition of every number below).  T = row-major

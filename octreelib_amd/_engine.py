@@ -650,6 +650,50 @@ class Forest:
         self.ctx.check(self.lib.octl_forest_point_to_plane_device(self.handle, xyz_dptr, int(n), int(min_points), mv,
                                                                   node_dptr, row_dptr, dist_dptr))
 
+    def nearest(self, points, k: int = 1, max_distance=None, slots=None):
+        """The k stored points of the poses of `slots` (None: all) nearest to every query point within max_distance
+        (octl_forest_nearest: one kernel once the block index of the selection exists): (slot (n, k) int32, index
+        (n, k) int64, distance2 (n, k) float64, count (n,) int32) as query.nearest_np defines them, the pose given by
+        its slot."""
+        from octreelib_amd.query import _as_queries, check_nearest_args
+
+        k, r = check_nearest_args(k, max_distance)
+        pts = _as_queries(points)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        n = len(pts)
+        slot = np.full((n, k), -1, dtype=np.int32)
+        index = np.full((n, k), -1, dtype=np.int64)
+        d2 = np.full((n, k), np.inf, dtype=np.float64)
+        count = np.zeros(n, dtype=np.int32)
+        # (n = 0 still goes to the library: what it refuses whatever the queries is refused for an empty scan too)
+        self.ctx.check(self.lib.octl_forest_nearest(self.handle, nat.ptr(pts), n, k, r, nat.ptr(sel), n_sel,
+                                                    nat.ptr(slot), nat.ptr(index), nat.ptr(d2), nat.ptr(count)))
+        return slot, index, d2, count
+
+    def nearest_device(self, xyz_dptr, n: int, k: int, max_distance, slot_dptr, index_dptr, d2_dptr, count_dptr,
+                       slots=None):
+        """nearest for points that are in device memory already, the (n, k) / (n,) answers left there (pointers from
+        octl_dev_alloc); enqueued on the context's stream, the host does not wait."""
+        from octreelib_amd.query import check_nearest_args
+
+        k, r = check_nearest_args(k, max_distance)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        self.ctx.check(self.lib.octl_forest_nearest_device(self.handle, xyz_dptr, int(n), k, r, nat.ptr(sel), n_sel,
+                                                           slot_dptr, index_dptr, d2_dptr, count_dptr))
+
+    def neighbours(self, points, k, max_distance, slots, pose_of_slot):
+        """nearest as a query.Neighbours: pose_of_slot maps the slot column to pose numbers (None: slots are the
+        pose numbers)."""
+        from octreelib_amd.query import Neighbours
+
+        slot, index, d2, count = self.nearest(points, k, max_distance, slots)
+        if pose_of_slot is not None and slot.size:
+            names = np.asarray(list(pose_of_slot) + [-1], dtype=np.int32)   # (-1 pads index the last entry)
+            slot = names[slot]
+        return Neighbours(slot, index, d2, count)
+
     # -- registration (octreelib_amd/registration.py is the host definition) ------------------------------------------
     @staticmethod
     def _reg_args(transform, origin, max_variance, max_distance, huber_delta):

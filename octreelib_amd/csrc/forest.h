@@ -137,6 +137,16 @@ struct octl_forest {
   std::vector<int64_t> adj_chunk_off;  // [S + 1] first chunk of every selected pose
   int64_t adj_blocks = 0, adj_rows = 0;  // selected blocks, leaves that hold one
 
+  // octl_forest_nearest (nearest.hip): the index node -> run of selected (leaf, pose) blocks in slot order.  Made by
+  // the call that finds it missing, stale or made for another selection; stamped as the pooled table is (every entry
+  // point that clears pooled_valid clears nn_valid):
+  //  nn_tab   one 16-byte record {start, size, slot, store offset of the pose} per block in (node, slot) order, then
+  //           first record and number of records of every node of the scheme;
+  //  nn_sort  scratch of the sort (its histograms go through pl_hist).
+  DevBuf nn_tab, nn_sort;
+  bool nn_valid = false;
+  std::vector<uint8_t> nn_sel;  // the pose selection it was made for (empty: every pose)
+
   // leaf-ordered arrays of the last build
   DevBuf ord_idx;    // u32 [n_ord] store index of the point at storage position i
   DevBuf xyz_ord;    // f64 [n_ord][3]

@@ -18,7 +18,7 @@ from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, VisualizationConfig
 from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
-from octreelib_amd.query import HostMap, LeafPlanes, PointToPlane
+from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PointToPlane
 from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
@@ -127,6 +127,22 @@ class Grid(GridBase):
         if self._plug is not None:
             return self._host_map().locate(points)
         return self._forest.locate(points)
+
+    def nearest(self, points, k: int = 1, *, max_distance: float,
+                pose_numbers: Optional[List[int]] = None) -> Neighbours:
+        """The k <= 8 stored points of the given poses (None: all) nearest to every query point, within max_distance:
+        exact neighbours across leaf and voxel walls.  A Neighbours (pose, index, distance2 (n, k), count (n,)): rows
+        in ascending (distance2, insertion order of the pose, index), index = the point's row in the cloud that was
+        inserted as that pose (masks and filters do not renumber it; removed points are never returned), pads -1 /
+        -1 / +inf.  distance2 <= max_distance^2 inclusive; a query that is not finite finds nothing.  One kernel once
+        the block index of the selection exists (octreelib_amd/query.py: nearest_np is the definition, bit for bit).
+        ValueError for k outside 1 .. 8, a max_distance that is not finite and positive or above twice the voxel
+        edge; RuntimeError after map_leaf_points moved rows outside their leaves; KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().nearest(points, k, max_distance=max_distance, pose_numbers=sel)
+        names = [p for p, _ in sorted(self._slots.items(), key=lambda kv: kv[1])]
+        return self._forest.neighbours(points, k, max_distance, sel, names)
 
     def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
         """One least-squares plane per leaf over the given poses (None: all), all their points pooled: a LeafPlanes in

@@ -102,6 +102,12 @@ class Octree(OctreeBase, Generic[T]):
         self._query_ready()
         return self._forest.locate(points)
 
+    def nearest(self, points, k: int = 1, *, max_distance: float):
+        """The k <= 8 stored points nearest to every query point within max_distance (a Neighbours whose pose column
+        is 0; Grid.nearest describes it)."""
+        self._query_ready()
+        return self._forest.neighbours(points, k, max_distance, None, [0] * self._forest.n_slots)
+
     def leaf_planes(self):
         """One least-squares plane per non-empty leaf, in ascending node id (a LeafPlanes)."""
         self._query_ready()

@@ -17,9 +17,10 @@ import numpy as np
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_np
 
 __all__ = ["LeafPlanes", "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np",
-           "node_table_from_leaves", "HostMap"]
+           "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K"]
 
 VOX_ABS_LIMIT = 1 << 30   # absolute voxel indices travel as int32
+NN_MAX_K = 8              # OCTL_NN_MAX_K: the largest k of nearest()
 
 
 @dataclass
@@ -38,6 +39,17 @@ class PointToPlane:
     row: np.ndarray        # (n,) int32 row of `planes`, -1: no accepted plane
     distance: np.ndarray   # (n,) signed distance normal . (p - mean); NaN where row < 0
     planes: LeafPlanes
+
+
+@dataclass
+class Neighbours:
+    """Answer of nearest for n query points: row i holds the count[i] <= k stored points nearest to query i within
+    max_distance, in ascending (distance2, slot of the pose, index)."""
+
+    pose: np.ndarray        # (n, k) int32 pose number, -1 pads
+    index: np.ndarray       # (n, k) int64 row of the neighbour in that pose's points as they were inserted, -1 pads
+    distance2: np.ndarray   # (n, k) float64 squared distance, +inf pads
+    count: np.ndarray       # (n,) int32 neighbours found
 
 
 def _as_queries(points) -> np.ndarray:
@@ -157,6 +169,61 @@ def point_to_plane_np(node, planes: LeafPlanes, points, min_points: int = 8, max
     return row, dist
 
 
+def check_nearest_args(k, max_distance):
+    """(k, max_distance) as (int, float); ValueError for what nearest refuses whatever the map."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= NN_MAX_K:
+        raise ValueError(f"nearest: k = {k!r} is outside 1 .. {NN_MAX_K}")
+    r = float(max_distance)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"nearest: max_distance must be finite and positive, got {max_distance!r}")
+    return int(k), r
+
+
+def nearest_np(points, clouds, k: int = 1, *, max_distance: float, dtype=np.float64, chunk: int = 256) -> Neighbours:
+    """The k stored points nearest to every query point within max_distance, by brute force: the definition of
+    nearest.  clouds: [(pose number, (m, 3) points)] of the selected poses in ascending slot order; `index` is the row
+    in that array.  For query q and stored point p: dx = q_x - p_x (dy, dz likewise), d2 = (dx dx + dy dy) + dz dz in
+    `dtype` with separate products and sums in that order; candidates have d2 <= r2 = max_distance * max_distance
+    (inclusive, r2 formed once); the order is ascending (d2, position of the pose in `clouds`, index) - a total order,
+    so the answer is a function of the input.  A query with a coordinate that is not finite finds nothing."""
+    k, r = check_nearest_args(k, max_distance)
+    q = _as_queries(points)
+    n = len(q)
+    pose = np.full((n, k), -1, dtype=np.int32)
+    index = np.full((n, k), -1, dtype=np.int64)
+    dist2 = np.full((n, k), np.inf, dtype=np.float64)
+    count = np.zeros(n, dtype=np.int32)
+    parts = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for _, c in clouds]
+    names = np.asarray([int(p) for p, _ in clouds], dtype=np.int32)
+    m = sum(len(c) for c in parts)
+    if n == 0 or m == 0:
+        return Neighbours(pose, index, dist2, count)
+    P = np.concatenate(parts).astype(dtype)
+    # (concatenated in slot order, a pose's rows ascending: the row of P IS the rank of (slot, index))
+    slot = np.repeat(np.arange(len(parts)), [len(c) for c in parts])
+    local = np.concatenate([np.arange(len(c), dtype=np.int64) for c in parts])
+    r2 = dtype(r) * dtype(r)
+    ok = np.all(np.isfinite(q), axis=1)
+    rows = np.arange(m)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for a in range(0, n, chunk):
+            qa = q[a: a + chunk].astype(dtype)
+            dx = qa[:, None, 0] - P[None, :, 0]
+            dy = qa[:, None, 1] - P[None, :, 1]
+            dz = qa[:, None, 2] - P[None, :, 2]
+            d2 = (dx * dx + dy * dy) + dz * dz
+            hit = (d2 <= r2) & ok[a: a + chunk, None]
+            for i in np.nonzero(hit.any(axis=1))[0]:
+                cand = rows[hit[i]]
+                cand = cand[np.argsort(d2[i, cand], kind="stable")][:k]    # (stable: ties stay in (slot, index) order)
+                c = len(cand)
+                pose[a + i, :c] = names[slot[cand]]
+                index[a + i, :c] = local[cand]
+                dist2[a + i, :c] = d2[i, cand]
+                count[a + i] = c
+    return Neighbours(pose, index, dist2, count)
+
+
 def node_table_from_leaves(roots, leaves):
     """A node table (the dict locate_np takes, plus the id of every leaf) for trees given by their LEAVES - what the
     classes on the caller's own plug types can list: roots = [(corner (3,), edge)] in voxel order, leaves = iterable of
@@ -248,6 +315,23 @@ class HostMap:
         system = lambda T, c: registration_system_np(self.locate, planes, pts, T, c, min_points, max_variance,
                                                      max_distance, huber_delta)
         return align_np(system, initial, max_iterations, tolerance, damping)
+
+    def clouds(self, pose_numbers=None):
+        """[(pose number, (m, 3) points)] of the chosen poses in the order they were inserted: what nearest searches
+        and what its `index` refers to.  These classes only know a pose through its leaves, so a pose's points are
+        those of its leaves, concatenated in listing order."""
+        chosen = list(self._leaves) if pose_numbers is None else [p for p in self._leaves if p in set(pose_numbers)]
+        out = []
+        for p in chosen:
+            parts = [np.asarray(v.get_points(), dtype=np.float64).reshape(-1, 3) for v in self._leaves[p]]
+            out.append((p, np.concatenate(parts) if parts else np.empty((0, 3))))
+        return out
+
+    def nearest(self, points, k=1, *, max_distance, pose_numbers=None) -> Neighbours:
+        k, r = check_nearest_args(k, max_distance)
+        if self.mode == 0 and r > 2.0 * self.edge:
+            raise ValueError(f"nearest: max_distance {r} exceeds twice the voxel edge {self.edge}")
+        return nearest_np(points, self.clouds(pose_numbers), k, max_distance=r)
 
     def block_moments(self, pose_numbers=None):
         """adjustment.BlockMoments of the chosen poses (insertion order), moments in np.longdouble returned as f64."""
