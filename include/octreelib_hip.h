@@ -315,6 +315,33 @@ int octl_forest_nearest(octl_forest* f, const double* xyz, int64_t n, int32_t k,
 int octl_forest_nearest_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t k, double max_distance,
                                const uint8_t* slot_sel, int32_t n_sel, int32_t* slot_dev, int64_t* index_dev,
                                double* d2_dev, int32_t* count_dev);
+/* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
+ * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
+ * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in
+ * f64 with every product and sum rounded (no fma), so neighbour, label, root and n_leaves EQUAL it.
+ *   eligible   a row with count >= min_points, lambda0 finite and, with max_variance >= 0, lambda0 <= max_variance;
+ *   neighbour  (rows, 6) node ids behind the faces -x +x -y +y -z +z: the leaf that holds the centre of the row's cube
+ *              with one coordinate replaced by corner + edge (+) or by the double before corner (-), as
+ *              octl_forest_locate answers; -1 for no leaf or the leaf itself;
+ *   edge       rows i and j = the row of a neighbour of i, both eligible, |(ni.x nj.x + ni.y nj.y) + ni.z nj.z| >=
+ *              cos_min and |n . (mj - mi)| <= max_offset for n = ni and n = nj (n the eigenvector of lambda0, m the
+ *              mean; the difference rounded once per component, dot products summed as above);
+ *   label      (rows,) the segment of a row - the connected components over the eligible rows, numbered in ascending
+ *              smallest row - or -1 for a row that is not eligible;
+ *   segments   root = node id of the smallest row, n_leaves, and count, mean, cov6 (xx xy xz yy yz zz), eigval,
+ *              eigvec (as octl_forest_leaf_stats orders and orients them) merged from the rows' own count, mean and
+ *              covariance about the mean of the smallest row; a segment of one leaf copies its row's bits.
+ * cos_min = cos(max_angle) is formed by the caller, once.  Size query and fill as octl_forest_pooled_leaf_stats: the
+ * call computes what is missing, caches it on the forest with its arguments (dropped wherever the pooled table is),
+ * writes *n_rows and *n_segments, and downloads the tables whose pointer is not NULL only when cap_rows >= *n_rows and
+ * cap_segments >= *n_segments.  A call with the same arguments on an unchanged forest launches nothing.
+ * OCTL_E_INVALID: min_points < 1, cos_min outside [0, 1], max_offset negative or not finite, max_variance NaN, a
+ * selection of the wrong length.  OCTL_E_STATE: before the first build.  No reference counterpart.               */
+int octl_forest_plane_segments(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int32_t min_points,
+                               double max_variance, double cos_min, double max_offset, int64_t cap_rows,
+                               int64_t cap_segments, int32_t* neighbour, int32_t* label, int32_t* root,
+                               int32_t* n_leaves, int64_t* count, double* mean, double* cov6, double* eigval,
+                               double* eigvec, int64_t* n_rows, int64_t* n_segments);
 /* The point-to-plane normal equations of a scan against the pooled leaf planes, for ONE rigid transform: what a
  * Gauss-Newton step of scan-to-map registration needs from the device (the 6x6 solve and the iteration are the
  * caller's; octreelib_amd/registration.py has them and the NumPy definition of every number below).  T = row-major

@@ -694,6 +694,38 @@ class Forest:
             slot = names[slot]
         return Neighbours(slot, index, d2, count)
 
+    def plane_segments(self, slots=None, min_points: int = 8, max_variance=None, max_angle: float = 0.1,
+                       max_offset: float = 0.05):
+        """The rows of leaf_planes(slots) merged across leaf faces into connected coplanar segments
+        (octl_forest_plane_segments: a size query that computes and caches on the device, then the fill): a
+        query.PlaneSegments as query.plane_segments_np defines it."""
+        from octreelib_amd.leaf_stats import cov6_to_full
+        from octreelib_amd.query import PlaneSegments, SegmentTable, check_segment_args
+
+        min_points, mv, cos_min, max_offset = check_segment_args(min_points, max_variance, max_angle, max_offset)
+        planes = self.leaf_planes(slots)
+        sel, n_sel, _ = self._adjust_selection(slots)
+        mv = -1.0 if mv is None else mv
+        nr, ns = C.c_int64(0), C.c_int64(0)
+
+        def call(cap_r, cap_s, *out):
+            self.ctx.check(self.lib.octl_forest_plane_segments(
+                self.handle, nat.ptr(sel), n_sel, min_points, mv, cos_min, max_offset, cap_r, cap_s,
+                *[nat.ptr(a) for a in out], C.byref(nr), C.byref(ns)))
+
+        call(0, 0, *([None] * 9))
+        R, S = nr.value, ns.value
+        if R != len(planes):
+            raise RuntimeError(f"plane_segments: {R} rows on the device, {len(planes)} in the plane table")
+        neighbour = np.full((R, 6), -1, dtype=np.int32)
+        label = np.full(R, -1, dtype=np.int32)
+        root, n_leaves = np.empty(S, dtype=np.int32), np.empty(S, dtype=np.int32)
+        count, mean, cov = np.empty(S, dtype=np.int64), np.empty((S, 3)), np.empty((S, 6))
+        w, v = np.empty((S, 3)), np.empty((S, 3, 3))
+        if R:
+            call(R, S, neighbour, label, root, n_leaves, count, mean, cov, w, v)
+        return PlaneSegments(planes, neighbour, label, SegmentTable(count, mean, cov6_to_full(cov), w, v, root, n_leaves))
+
     # -- registration (octreelib_amd/registration.py is the host definition) ------------------------------------------
     @staticmethod
     def _reg_args(transform, origin, max_variance, max_distance, huber_delta):

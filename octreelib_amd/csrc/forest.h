@@ -147,6 +147,21 @@ struct octl_forest {
   bool nn_valid = false;
   std::vector<uint8_t> nn_sel;  // the pose selection it was made for (empty: every pose)
 
+  // octl_forest_plane_segments (segments.hip): the face adjacency of the rows of the pooled table, the connected
+  // components of the coplanar ones and one merged plane per component.  Cached with the arguments it was made for and
+  // stamped as the pooled table is (every entry point that clears pooled_valid clears seg_valid):
+  //  seg_tab   [neighbour i32 x6 per row | label i32 per row];
+  //  seg_out   for seg_cap segments [root i32 | leaves i32 | count i64 | mean 3 | cov 6 | eigval 3 | eigvec 9];
+  //  seg_sort  what one computation needs besides: parents, roots, head flags and their scan, the sort's keys and
+  //            values, the first sorted position of every segment (the histograms go through pl_hist).
+  // Every part of the three starts 256-byte aligned.
+  DevBuf seg_tab, seg_out, seg_sort;
+  bool seg_valid = false;
+  int64_t seg_rows = 0, seg_n = 0, seg_cap = 0;  // rows the tables were made for, segments, segments the layout holds
+  std::vector<uint8_t> seg_sel;                  // the pose selection (empty: every pose)
+  int32_t seg_min_points = 0;
+  double seg_max_variance = -1.0, seg_cos_min = 0.0, seg_max_offset = 0.0;
+
   // leaf-ordered arrays of the last build
   DevBuf ord_idx;    // u32 [n_ord] store index of the point at storage position i
   DevBuf xyz_ord;    // f64 [n_ord][3]
@@ -240,6 +255,23 @@ int forest_fix_origin(octl_forest* f, const int bb[6]);
 // its scheme in O(new points).  *done = 0: not applicable, nothing was changed
 int forest_sync_vcodes(octl_forest* f);
 int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info);
+
+// leaf_stats.hip: layout of f->pl_rows for `cap` rows, and the pooled table of the selection `sel` (empty: every pose)
+// of the forest as it stands - what octl_forest_pooled_leaf_stats and octl_forest_plane_segments make when they find
+// none that is valid
+struct PoolLayout {
+  size_t o_count, o_mean, o_cov, o_w, o_v, total;
+  explicit PoolLayout(int64_t cap) {
+    const size_t c = (size_t)(cap > 1 ? cap : 1);
+    o_count = align256(c * 4);
+    o_mean = o_count + align256(c * 8);
+    o_cov = o_mean + align256(c * 24);
+    o_w = o_cov + align256(c * 48);
+    o_v = o_w + align256(c * 24);
+    total = o_v + align256(c * 72);
+  }
+};
+int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel);
 
 // mask.hip: wait for the counts an asynchronous apply_mask left in flight (octl_forest_apply_mask_async) and book
 // them; a no-op otherwise.  Every entry point that looks at the forest calls it first.

@@ -339,20 +339,9 @@ __global__ __launch_bounds__(256) void k_pool_eigen(int64_t n_rows, const int32_
   node_row[node[r]] = (int32_t)r;
 }
 
-// layout of f->pl_rows for `cap` rows
-struct PoolLayout {
-  size_t o_count, o_mean, o_cov, o_w, o_v, total;
-  explicit PoolLayout(int64_t cap) {
-    const size_t c = (size_t)std::max<int64_t>(cap, 1);
-    o_count = align256(c * 4);
-    o_mean = o_count + align256(c * 8);
-    o_cov = o_mean + align256(c * 24);
-    o_w = o_cov + align256(c * 48);
-    o_v = o_w + align256(c * 24);
-    total = o_v + align256(c * 72);
-  }
-};
+}  // namespace
 
+// (PoolLayout: forest.h)
 int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel) {
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
@@ -429,8 +418,6 @@ int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel) {
   f->pooled_valid = true;
   return OCTL_OK;
 }
-
-}  // namespace
 
 extern "C" int octl_forest_pooled_leaf_stats(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int64_t cap,
                                              int32_t* node, int64_t* count, double* mean, double* cov6, double* eigval,

@@ -113,6 +113,13 @@ class Octree(OctreeBase, Generic[T]):
         self._query_ready()
         return self._forest.leaf_planes(None)
 
+    def plane_segments(self, min_points: int = 8, max_variance=None, max_angle: float = 0.1,
+                       max_offset: float = 0.05):
+        """The leaves of leaf_planes() merged across their faces into connected coplanar segments (a PlaneSegments;
+        Grid.plane_segments describes it)."""
+        self._query_ready()
+        return self._forest.plane_segments(None, min_points, max_variance, max_angle, max_offset)
+
     def point_to_plane(self, points, min_points: int = 8, max_variance=None):
         """Leaf, plane row and signed distance to the plane of its own leaf for every query point."""
         self._query_ready()

@@ -14,7 +14,7 @@ from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.internal.voxel import Voxel, VoxelBase
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase
-from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PointToPlane
+from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane
 from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
@@ -153,6 +153,23 @@ class OctreeManager(VoxelBase):
         if self._plug is not None:
             return self._host_map().leaf_planes(sel)
         return self._forest.leaf_planes(sel)
+
+    def plane_segments(self, pose_numbers: Optional[List[int]] = None, min_points: int = 8,
+                       max_variance: Optional[float] = None, max_angle: float = 0.1,
+                       max_offset: float = 0.05) -> PlaneSegments:
+        """The leaves of leaf_planes(pose_numbers) merged across their faces into connected coplanar segments - plane
+        landmarks (a floor, a wall) instead of hundreds of leaves: a PlaneSegments (planes, neighbour (rows, 6) node
+        ids behind the faces -x +x -y +y -z +z, label (rows,) segment of a row or -1, segments = one merged plane per
+        segment with root and n_leaves).  A row takes part with at least min_points points and a smallest eigenvalue
+        that is finite and at most max_variance; two face neighbours are joined when their normals are within
+        max_angle and each plane passes within max_offset of the other's mean.  Computed on the device and cached
+        until the map changes (octreelib_amd/query.py: plane_segments_np is the definition; neighbour, label, root
+        and n_leaves equal it exactly).  ValueError for max_angle outside [0, pi/2], a max_offset that is negative or
+        not finite, min_points < 1; KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().plane_segments(sel, min_points, max_variance, max_angle, max_offset)
+        return self._forest.plane_segments(sel, min_points, max_variance, max_angle, max_offset)
 
     def point_to_plane(self, points, pose_numbers: Optional[List[int]] = None, min_points: int = 8,
                        max_variance: Optional[float] = None) -> PointToPlane:

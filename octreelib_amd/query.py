@@ -12,12 +12,15 @@ use, so that the whole feature also runs, slowly, without a GPU.
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
+import math
+
 import numpy as np
 
-from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_np
+from octreelib_amd.leaf_stats import LeafStatistics, cov6_to_full, leaf_statistics_np, orient_eigenvectors
 
 __all__ = ["LeafPlanes", "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np",
-           "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K"]
+           "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K", "PlaneSegments",
+           "SegmentTable", "plane_segments_np", "segment_probes_np"]
 
 VOX_ABS_LIMIT = 1 << 30   # absolute voxel indices travel as int32
 NN_MAX_K = 8              # OCTL_NN_MAX_K: the largest k of nearest()
@@ -224,6 +227,162 @@ def nearest_np(points, clouds, k: int = 1, *, max_distance: float, dtype=np.floa
     return Neighbours(pose, index, dist2, count)
 
 
+@dataclass
+class SegmentTable(LeafStatistics):
+    """LeafStatistics of the plane segments, merged from the moments of their leaves; row s describes segment s."""
+
+    root: np.ndarray = None       # (S,) int32 node id of the segment's smallest row
+    n_leaves: np.ndarray = None   # (S,) int32 leaves of the segment
+
+
+@dataclass
+class PlaneSegments:
+    """Answer of plane_segments: the leaves of `planes` merged across their faces into connected coplanar regions."""
+
+    planes: LeafPlanes        # the rows: one per leaf that holds a point of the selection, ascending node id
+    neighbour: np.ndarray     # (rows, 6) int32 node id of the leaf behind the faces -x, +x, -y, +y, -z, +z; -1: none
+    label: np.ndarray         # (rows,) int32 segment of the row, -1: not eligible
+    segments: SegmentTable    # one merged plane per segment, in ascending smallest row
+
+
+def check_segment_args(min_points, max_variance, max_angle, max_offset):
+    """(min_points, max_variance or None, cos_min, max_offset); ValueError for what plane_segments refuses whatever
+    the map.  cos_min = math.cos(max_angle), formed here once and handed on as a double."""
+    if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 1:
+        raise ValueError(f"plane_segments: min_points = {min_points!r} is below 1")
+    a = float(max_angle)
+    if not 0.0 <= a <= math.pi / 2:
+        raise ValueError(f"plane_segments: max_angle = {max_angle!r} is outside [0, pi/2]")
+    o = float(max_offset)
+    if not (np.isfinite(o) and o >= 0.0):
+        raise ValueError(f"plane_segments: max_offset must be finite and not negative, got {max_offset!r}")
+    mv = None
+    if max_variance is not None:
+        mv = float(max_variance)
+        if np.isnan(mv):
+            raise ValueError("plane_segments: max_variance is NaN")
+        if mv < 0:
+            mv = None           # (as point_to_plane: a negative bound is no bound)
+    return int(min_points), mv, math.cos(a), o
+
+
+def segment_probes_np(corner, edge) -> np.ndarray:
+    """(n, 6, 3) probe points of the cubes (corner (n, 3), edge (n,)) in direction order -x, +x, -y, +y, -z, +z: the
+    cube's centre corner + edge / 2 with one coordinate replaced - by corner + edge in a + direction (the face itself:
+    cubes are half-open, it belongs to the far side), by nextafter(corner, -inf) in a - direction."""
+    c = np.asarray(corner, dtype=np.float64).reshape(-1, 3)
+    e = np.asarray(edge, dtype=np.float64).reshape(-1)
+    centre = c + (e / 2.0)[:, None]
+    probes = np.repeat(centre[:, None, :], 6, axis=1)
+    for a in range(3):
+        probes[:, 2 * a, a] = np.nextafter(c[:, a], -np.inf)
+        probes[:, 2 * a + 1, a] = c[:, a] + e
+    return probes
+
+
+def _components(n: int, ei: np.ndarray, ej: np.ndarray) -> np.ndarray:
+    """Smallest member of the connected component of every vertex 0 .. n-1 under the undirected edges (ei, ej)."""
+    lab = np.arange(n, dtype=np.int64)
+    while len(ei):
+        new = lab.copy()
+        np.minimum.at(new, ei, lab[ej])
+        np.minimum.at(new, ej, lab[ei])
+        new = new[new]            # (lab[x] <= x: a label is a vertex of the same component)
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    return lab
+
+
+def plane_segments_np(planes: LeafPlanes, nodes, voxels, mode: int, edge: float, min_points: int = 8,
+                      max_variance: Optional[float] = None, max_angle: float = 0.1,
+                      max_offset: float = 0.05) -> PlaneSegments:
+    """The definition of plane_segments, on the host.  planes: the pooled table (leaf_planes of the selection); nodes,
+    voxels, mode, edge: the node table as locate_np takes it.  Every decision is made in float64 on the table's own
+    bits with separate products and sums in the stated order, so that the device forms the same bits:
+
+    eligible   count >= min_points, lambda0 finite, lambda0 <= max_variance when one is given;
+    neighbour  locate_np of the six probes of the row's cube (segment_probes_np); -1 where locate answers -1 or the
+               leaf itself (a non-dyadic single cube, where corner + edge rounds);
+    edge       rows i, j = the row of a neighbour of i, both eligible, |(ni.x nj.x + ni.y nj.y) + ni.z nj.z| >=
+               cos_min = math.cos(max_angle), and |n . (mj - mi)| <= max_offset for n = ni and n = nj, the difference
+               rounded once per component and the dot products summed as above - symmetric in (i, j);
+    segments   the connected components of the eligible rows, numbered in ascending smallest row; label -1 for a row
+               that is not eligible;
+    table      per segment with anchor a = the mean of its smallest row, d_i = m_i - a: N = sum n_i, S_d = sum n_i d_i,
+               S_dd = sum n_i (C_i + d_i d_i^T), mean = a + S_d / N, cov = S_dd / N - (S_d / N)(S_d / N)^T, the
+               eigen-decomposition as leaf_statistics_np's; a segment of one leaf copies its row."""
+    min_points, mv, cos_min, max_offset = check_segment_args(min_points, max_variance, max_angle, max_offset)
+    ids = np.asarray(planes.node, dtype=np.int64)
+    R = len(ids)
+    neighbour = np.full((R, 6), -1, dtype=np.int32)
+    label = np.full(R, -1, dtype=np.int32)
+    empty = SegmentTable(np.zeros(0, dtype=np.int64), np.zeros((0, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3)),
+                         np.zeros((0, 3, 3)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
+    if R == 0:
+        return PlaneSegments(planes, neighbour, label, empty)
+    corner = np.asarray(nodes["corner"], dtype=np.float64).reshape(-1, 3)[ids]
+    e = np.asarray(nodes["edge"], dtype=np.float64)[ids]
+    nb = locate_np(nodes, voxels, mode, edge, segment_probes_np(corner, e).reshape(-1, 3)).reshape(R, 6)
+    nb = np.where(nb == ids[:, None], -1, nb).astype(np.int32)
+    neighbour[:] = nb
+    lam0 = np.asarray(planes.eigenvalues, dtype=np.float64)[:, 0]
+    with np.errstate(invalid="ignore"):
+        ok = (np.asarray(planes.count) >= min_points) & np.isfinite(lam0)
+        if mv is not None:
+            ok &= lam0 <= mv
+    # candidate edges: (row, row of the neighbour) where the neighbour has a row
+    pos = np.minimum(np.searchsorted(ids, nb), R - 1)
+    has = (nb >= 0) & (ids[pos] == nb)
+    ri, d = np.nonzero(has)
+    rj = pos[ri, d]
+    keep = ok[ri] & ok[rj] & (ri != rj)
+    ri, rj = ri[keep], rj[keep]
+    n = np.asarray(planes.normal, dtype=np.float64)
+    m = np.asarray(planes.mean, dtype=np.float64)
+    ni, nj = n[ri], n[rj]
+    dm = m[rj] - m[ri]
+    with np.errstate(invalid="ignore", over="ignore"):
+        dot = (ni[:, 0] * nj[:, 0] + ni[:, 1] * nj[:, 1]) + ni[:, 2] * nj[:, 2]
+        oi = (ni[:, 0] * dm[:, 0] + ni[:, 1] * dm[:, 1]) + ni[:, 2] * dm[:, 2]
+        oj = (nj[:, 0] * dm[:, 0] + nj[:, 1] * dm[:, 1]) + nj[:, 2] * dm[:, 2]
+        join = (np.abs(dot) >= cos_min) & (np.abs(oi) <= max_offset) & (np.abs(oj) <= max_offset)
+    comp = _components(R, ri[join], rj[join])
+    roots = np.nonzero(ok & (comp == np.arange(R)))[0]
+    number = np.full(R, -1, dtype=np.int64)
+    number[roots] = np.arange(len(roots))
+    label[ok] = number[comp[ok]]
+    S = len(roots)
+    if S == 0:
+        return PlaneSegments(planes, neighbour, label, empty)
+    # the table: rows of a segment in ascending row order
+    rows = np.nonzero(ok)[0]
+    rows = rows[np.argsort(label[rows], kind="stable")]
+    seg = label[rows]
+    starts = np.searchsorted(seg, np.arange(S))
+    n_leaves = np.diff(np.concatenate([starts, [len(rows)]])).astype(np.int32)
+    cnt = np.asarray(planes.count, dtype=np.int64)[rows]
+    nf = cnt.astype(np.float64)
+    a = m[roots]
+    dd = m[rows] - a[seg]
+    C = np.asarray(planes.covariance, dtype=np.float64)[rows]
+    N = np.add.reduceat(cnt, starts)
+    Nf = N.astype(np.float64)
+    Sd = np.add.reduceat(nf[:, None] * dd, starts, axis=0)
+    Sdd = np.add.reduceat(nf[:, None, None] * (C + dd[:, :, None] * dd[:, None, :]), starts, axis=0)
+    md = Sd / Nf[:, None]
+    mean = a + md
+    cov = Sdd / Nf[:, None, None] - md[:, :, None] * md[:, None, :]
+    w, v = np.linalg.eigh(cov)
+    v = orient_eigenvectors(np.ascontiguousarray(v))
+    one = n_leaves == 1
+    r1 = roots[one]
+    mean[one], cov[one] = m[r1], np.asarray(planes.covariance, dtype=np.float64)[r1]
+    w[one], v[one] = np.asarray(planes.eigenvalues)[r1], np.asarray(planes.eigenvectors)[r1]
+    table = SegmentTable(N, mean, cov, w, v, ids[roots].astype(np.int32), n_leaves)
+    return PlaneSegments(planes, neighbour, label, table)
+
+
 def node_table_from_leaves(roots, leaves):
     """A node table (the dict locate_np takes, plus the id of every leaf) for trees given by their LEAVES - what the
     classes on the caller's own plug types can list: roots = [(corner (3,), edge)] in voxel order, leaves = iterable of
@@ -332,6 +491,12 @@ class HostMap:
         if self.mode == 0 and r > 2.0 * self.edge:
             raise ValueError(f"nearest: max_distance {r} exceeds twice the voxel edge {self.edge}")
         return nearest_np(points, self.clouds(pose_numbers), k, max_distance=r)
+
+    def plane_segments(self, pose_numbers=None, min_points=8, max_variance=None, max_angle=0.1,
+                       max_offset=0.05) -> PlaneSegments:
+        check_segment_args(min_points, max_variance, max_angle, max_offset)
+        return plane_segments_np(self.leaf_planes(pose_numbers), self.nodes, self.voxels, self.mode, self.edge,
+                                 min_points, max_variance, max_angle, max_offset)
 
     def block_moments(self, pose_numbers=None):
         """adjustment.BlockMoments of the chosen poses (insertion order), moments in np.longdouble returned as f64."""
