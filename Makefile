@@ -12,6 +12,10 @@ STUB = tests/rccl_stub/librccl_stub.so
 
 all: $(LIB) $(STUB)
 
+# ransac.hip alone: no SLP vectoriser, which packs the f32 FMAs of neighbouring hypotheses into v_pk_fma_f32
+# (measured slower than the scalar pairs on gfx950: the comment above fma32 in ransac.hip)
+build/ransac.o: HIPFLAGS += -fno-slp-vectorize
+
 build/%.o: octreelib_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

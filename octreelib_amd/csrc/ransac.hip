@@ -447,19 +447,24 @@ __device__ __forceinline__ void ransac_block_global(const BlockDesc& d, int be,
                                            pts[3 * (int64_t)i + 2]) < thr) ? 1 : 0;
 }
 
-// Helpers of the screened scoring loop, as inline asm on purpose: the loop's instruction mix is
-// the whole point.  Plain v_fma_f32: left to itself hipcc SLP-packs neighbouring hypotheses into
-// v_pk_fma_f32, which measured SLOWER than two scalar FMAs on gfx950 (both as compiler output
-// and hand-packed with op_sel broadcasts: 5.56 vs 5.47 ms in round 2; again in round 5 on the
-// VALU-issue-bound kernel: 120 v_pk_fma_f32 for 240 v_fma_f32, same moves, 119 VGPRs - 3.60 vs
-// 3.52 ms, although tools/probes/pkfma_probe.hip has the packed form at 5.2 cycles against
-// 2 x 3.5 in isolation), and adds canonicalising v_max around fminf.
+// Helpers of the screened scoring loop: the loop's instruction mix is the whole point.
+// fma32 is the fused multiply-add as a builtin (fused whatever -ffp-contract says), so that the
+// compiler knows the instruction.  As inline asm - which it was, to keep hipcc from SLP-packing
+// neighbouring hypotheses into v_pk_fma_f32 - the compiler assumed the worst hazard behind every
+// FMA and padded its dependent use with an s_nop: 200 in the one-wave instance, 39 against 61 VALU
+// instructions in the 4-point body of the widened count; without them the kernel runs 6-7 % faster
+// (HISTORY.md 11).  The packing - measured SLOWER than two scalar FMAs on gfx950: 5.56 vs 5.47 ms
+// in round 2, 120 v_pk_fma_f32 for 240 v_fma_f32 in round 5: 3.60 vs 3.52 ms, HISTORY.md 8 - is
+// now the Makefile's business: this file alone is compiled with -fno-slp-vectorize.
+// The ORDER of the FMAs is the compiler's: the NH chains of a point one after the other in the
+// count loops, fit after fit in the prescreen.  Holding the independent chains next to each other
+// with scheduling barriers (12 chains per 4-point body, the three fits of a trio stage by stage,
+// their gathers ahead) was measured and lost or did not show: four waves per SIMD hide a chain's
+// latency already (HISTORY.md 11).
+// min3abs stays asm: written with fminf / fabsf the compiler puts a canonicalising v_max in front
+// of the v_min3 for every operand it cannot prove quiet.
 typedef float f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float fma32(float a, float b, float c) {
-  float r;
-  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
+__device__ __forceinline__ float fma32(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // min(m, |a|, |b|)
 __device__ __forceinline__ float min3abs(float m, float a, float b) {
   float r;
@@ -644,8 +649,7 @@ __device__ __forceinline__ void screen_ub(const f4* __restrict__ loc, int n, con
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
         const float sv = fma32(fa[h], L.x, fma32(fb[h], L.y, fma32(fc[h], L.z, sto[h])));
-        float e;
-        asm("v_fma_f32 %0, %1, %1, -%2" : "=v"(e) : "v"(sv), "v"(T2[h]));
+        const float e = fma32(sv, sv, -T2[h]);
         hist[h] = __builtin_amdgcn_alignbit(hist[h], __float_as_uint(e), 31);
       }
     };

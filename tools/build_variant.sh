@@ -7,7 +7,9 @@ OUT=build/variants
 mkdir -p $OUT/obj_$NAME
 for f in octreelib_amd/csrc/*.hip; do
   b=$(basename $f .hip)
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -Wno-unused-function -Iinclude -DOCTL_EXPERIMENTS $FLAGS -c $f -o $OUT/obj_$NAME/$b.o &
+  PERFILE=""
+  [ $b = ransac ] && PERFILE="-fno-slp-vectorize"   # as the Makefile
+  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -Wno-unused-function -Iinclude -DOCTL_EXPERIMENTS $PERFILE $FLAGS -c $f -o $OUT/obj_$NAME/$b.o &
   pids="$pids $!"
 done
 for p in $pids; do wait $p; done
