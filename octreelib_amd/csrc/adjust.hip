@@ -9,9 +9,9 @@
 //   s' = R s,  M' = (R M) R^T,  s'' = s' + n delta,  M'' = M' + delta s'^T + s' delta^T + n delta delta^T,
 // every dot product as fma(x2, y2, fma(x1, y1, x0 y0)); at R = I, t = 0 every step is exact.
 //
-// Prepared once per map and pose selection (adj_prepare; stamped like the pooled table, forest.h):
-//   k_pool_keys, sort, k_pool_heads, scan   the (node, slot) grouping of octl_forest_pooled_leaf_stats
+// Prepared once per map and pose selection (adj_prepare; stamped as every derived map table is, forest.h):
 //   k_adj_hist                              selected blocks per pose (integer atomics)
+//   k_pool_keys, sort, k_pool_heads, scan   the (node, slot) grouping of the selected blocks (leaf_moments.h: block_groups)
 //   k_adj_moments   one wave per selected block: its 80-byte moments by the chunked reduction of k_pool_moments
 //                   (chunk_sums over chunks of 4096, folded in chunk order), its leaf row, its pose
 //   k_adj_keys2, sort                       the same blocks by (slot, node); a pose's blocks are one run of it, cut
@@ -320,43 +320,41 @@ __global__ __launch_bounds__(256) void k_adj_fold(const double* __restrict__ row
   }
 }
 
-// f->adj_tab for n_sel blocks, n_rows leaves, n_chunks chunks, S selected poses of n_poses
+// f->adj_tab for n_sel blocks, n_rows leaves, n_chunks chunks, S selected poses
 struct AdjTab {
-  size_t o_row, o_pose, o_ord2, o_first, o_node, o_anchor, o_chunks, o_choff, o_sidx, total;
-  AdjTab(int64_t n_sel, int64_t n_rows, int64_t n_chunks, int S, int n_poses) {
-    o_row = align256((size_t)n_sel * AJ_MOM * 8);
-    o_pose = o_row + align256((size_t)n_sel * 4);
-    o_ord2 = o_pose + align256((size_t)n_sel * 4);
-    o_first = o_ord2 + align256((size_t)n_sel * 4);
-    o_node = o_first + align256((size_t)(n_rows + 1) * 4);
-    o_anchor = o_node + align256((size_t)n_rows * 4);
-    o_chunks = o_anchor + align256((size_t)n_rows * 24);
-    o_choff = o_chunks + align256((size_t)n_chunks * 16);
-    o_sidx = o_choff + align256((size_t)(S + 1) * 4);
-    total = o_sidx + align256((size_t)std::max(n_poses, 1) * 4);
-  }
+  size_t n_sel, n_rows, n_chunks, S;
+  Carve plan;
+  Carve::Part<double> mom = plan.add<double>(n_sel * AJ_MOM);
+  Carve::Part<int32_t> row = plan.add<int32_t>(n_sel), pose = plan.add<int32_t>(n_sel);
+  Carve::Part<uint32_t> ord2 = plan.add<uint32_t>(n_sel);
+  Carve::Part<int32_t> first = plan.add<int32_t>(n_rows + 1), node = plan.add<int32_t>(n_rows);
+  Carve::Part<double> anchor = plan.add<double>(n_rows * 3);
+  Carve::Part<int4> chunks = plan.add<int4>(n_chunks);
+  Carve::Part<int32_t> choff = plan.add<int32_t>(S + 1);
+  constexpr AdjTab(int64_t blocks, int64_t rows, int64_t n_ck, int s)
+      : n_sel((size_t)blocks), n_rows((size_t)rows), n_chunks((size_t)n_ck), S((size_t)s) {}
 };
+static_assert(AdjTab(100, 10, 3, 2).choff.off == 10752 && AdjTab(100, 10, 3, 2).plan.total == 11008, "AdjTab offsets");
 
 // f->adj_call: [T 12 f64 per pose | plane 8 f64 per leaf | used i32 per leaf | used leaves i32 per wave of k_adj_leaf |
 //               partial rows | result]
 struct AdjCall {
-  size_t o_plane, o_used, o_wused, o_rows, o_out, total;
-  AdjCall(int64_t n_rows, int64_t n_chunks, int S) {
-    o_plane = align256((size_t)S * 96);
-    o_used = o_plane + align256((size_t)n_rows * 64);
-    o_wused = o_used + align256((size_t)n_rows * 4);
-    o_rows = o_wused + align256((size_t)ceil_div(n_rows, 64) * 4);
-    o_out = o_rows + align256((size_t)n_chunks * RS_ROW * 8);
-    total = o_out + align256(((size_t)S * AJ_OUT + 1) * 8);
-  }
+  size_t n_rows, n_chunks, S;
+  Carve plan;
+  Carve::Part<double> T = plan.add<double>(S * 12), plane = plan.add<double>(n_rows * 8);
+  Carve::Part<int32_t> used = plan.add<int32_t>(n_rows), wused = plan.add<int32_t>((n_rows + 63) / 64);
+  Carve::Part<double> rows = plan.add<double>(n_chunks * RS_ROW), out = plan.add<double>(S * AJ_OUT + 1);
+  constexpr AdjCall(int64_t rows_, int64_t n_ck, int s) : n_rows((size_t)rows_), n_chunks((size_t)n_ck), S((size_t)s) {}
 };
+static_assert(AdjCall(100, 3, 2).out.off == 8192 && AdjCall(100, 3, 2).plan.total == 8704, "AdjCall offsets");
 
 int adj_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
-  const int64_t nb = f->n_blocks, n_nodes = f->nodes[f->cur].n;
+  const int64_t nb = f->n_blocks;
   const int n_poses = (int)f->pose_off.size() - 1;
-  f->adj_valid = f->adj_called = false;
+  f->adj_stamp = 0;
+  f->adj_called = false;
   std::vector<int32_t> slots, slot_idx((size_t)std::max(n_poses, 1), -1);
   for (int s = 0; s < n_poses; ++s)
     if (sel.empty() || sel[s]) {
@@ -367,41 +365,22 @@ int adj_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   std::vector<int64_t> chunk_off((size_t)S + 1, 0);
   int64_t n_sel = 0, n_rows = 0;
   if (nb > 0 && S > 0) {
-    const int sbits = std::max(1, bits_for((uint64_t)std::max(n_poses, 1)));
-    const int nbits = std::max(1, bits_for((uint64_t)n_nodes));
-    const int kbits = sbits + nbits;
-    // f->adj_sort: [key u64 x2 | val u32 x2 | heads u32 (+8: the scan's tail) | selection u8 | slot -> selection index
-    //               i32 | scan total u32, blocks per selected pose u32]
-    const size_t o_key1 = align256((size_t)nb * 8), o_val0 = 2 * o_key1, o_val1 = o_val0 + align256((size_t)nb * 4);
-    const size_t o_heads = o_val1 + align256((size_t)nb * 4), o_sel = o_heads + align256(((size_t)nb + 8) * 4);
-    const size_t o_sidx = o_sel + align256((size_t)n_poses), o_misc = o_sidx + align256((size_t)n_poses * 4);
+    // f->grp_scratch: the grouping, then [slot -> selection index i32 | scan total u32, blocks per selected pose u32]
+    BlockGroups g(f, true);
+    const auto sidx_part = g.plan.add<int32_t>((size_t)n_poses);
+    const auto misc_part = g.plan.add<uint32_t>((size_t)S + 1);
     const size_t misc_bytes = ((size_t)S + 1) * 4;
-    OCTL_TRY(devbuf_reserve(ctx, f->adj_sort, o_misc + align256(misc_bytes)));
-    char* base = static_cast<char*>(f->adj_sort.p);
-    uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base), reinterpret_cast<uint64_t*>(base + o_key1)};
-    uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(base + o_val0), reinterpret_cast<uint32_t*>(base + o_val1)};
-    uint32_t* heads = reinterpret_cast<uint32_t*>(base + o_heads);
-    uint8_t* sel_d = reinterpret_cast<uint8_t*>(base + o_sel);
-    int32_t* sidx_d = reinterpret_cast<int32_t*>(base + o_sidx);
-    uint32_t* misc_d = reinterpret_cast<uint32_t*>(base + o_misc);
-    if (!sel.empty()) HIP_TRY(ctx, hipMemcpyAsync(sel_d, sel.data(), sel.size(), hipMemcpyHostToDevice, st));
+    OCTL_TRY(g.prepare(f, sel));
+    int32_t* sidx_d = Carve::at(f->grp_scratch, sidx_part);
+    uint32_t* misc_d = Carve::at(f->grp_scratch, misc_part);
     HIP_TRY(ctx, hipMemcpyAsync(sidx_d, slot_idx.data(), (size_t)n_poses * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(misc_d, 0, misc_bytes, st));
-    int res = 0;
     {
       KTimer t(ctx, "adj_group");
-      OCTL_LAUNCH(k_pool_keys, dim3(grid_for(nb)), dim3(256), 0, st, (const int32_t*)f->blk_node.as<int32_t>(),
-                  (const int32_t*)f->blk_slot.as<int32_t>(), nb, sel.empty() ? (const uint8_t*)nullptr : sel_d,
-                  (int)sel.size(), sbits, kbits, keys[0], vals[0]);
-      HIP_TRY(ctx, hipGetLastError());
       OCTL_LAUNCH(k_adj_hist, dim3(grid_for(nb)), dim3(256), 0, st, (const int32_t*)f->blk_slot.as<int32_t>(), nb,
                   (const int32_t*)sidx_d, n_poses, misc_d + 1);
       HIP_TRY(ctx, hipGetLastError());
-      OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys, vals, nb, kbits + 1, f->pl_hist, &res));
-      OCTL_LAUNCH(k_pool_heads, dim3(grid_for(nb)), dim3(256), 0, st, (const uint64_t*)keys[res], nb, sbits, kbits,
-                  heads);
-      HIP_TRY(ctx, hipGetLastError());
-      OCTL_TRY(octl_exclusive_scan_u32(ctx, heads, heads, nb, misc_d));
+      OCTL_TRY(block_groups(f, (int)sel.size(), misc_d, g));
     }
     std::vector<uint32_t> misc((size_t)S + 1);
     HIP_TRY(ctx, hipMemcpyAsync(misc.data(), misc_d, misc_bytes, hipMemcpyDeviceToHost, st));
@@ -420,39 +399,41 @@ int adj_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
                             (long long)n_sel, (long long)nb, (long long)n_rows);
     if (n_sel > 0) {
       const int64_t n_chunks = (int64_t)chunks.size();
-      const AdjTab lay(n_sel, n_rows, n_chunks, S, n_poses);
-      OCTL_TRY(devbuf_reserve(ctx, f->adj_tab, lay.total));
-      char* tb = static_cast<char*>(f->adj_tab.p);
+      const AdjTab lay(n_sel, n_rows, n_chunks, S);
+      DevBuf& tb = f->adj_tab;
+      OCTL_TRY(devbuf_reserve(ctx, f->adj_tab, lay.plan.total));
       std::vector<int32_t> choff32(chunk_off.begin(), chunk_off.end());
       // (rows, poses, order and leaf ranges start as zeros: a table the kernels below left incomplete names no memory
       //  outside the tables)
-      HIP_TRY(ctx, hipMemsetAsync(tb + lay.o_row, 0, lay.o_node - lay.o_row, st));
-      HIP_TRY(ctx, hipMemcpyAsync(tb + lay.o_chunks, chunks.data(), (size_t)n_chunks * 16, hipMemcpyHostToDevice, st));
-      HIP_TRY(ctx, hipMemcpyAsync(tb + lay.o_choff, choff32.data(), ((size_t)S + 1) * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemsetAsync(Carve::at(tb, lay.row), 0, lay.node.off - lay.row.off, st));
+      HIP_TRY(ctx, hipMemcpyAsync(Carve::at(tb, lay.chunks), chunks.data(), (size_t)n_chunks * 16,
+                                  hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(Carve::at(tb, lay.choff), choff32.data(), ((size_t)S + 1) * 4, hipMemcpyHostToDevice,
+                                  st));
       {
         KTimer t(ctx, "adj_moments");
         const NodeTable& nt = f->nodes[f->cur];
-        OCTL_LAUNCH(k_adj_moments, dim3((unsigned)ceil_div(n_sel, 4)), dim3(256), 0, st, (const uint64_t*)keys[res],
-                    (const uint32_t*)vals[res], (const uint32_t*)heads, n_sel, sbits,
+        OCTL_LAUNCH(k_adj_moments, dim3((unsigned)ceil_div(n_sel, 4)), dim3(256), 0, st, (const uint64_t*)g.keys[0],
+                    (const uint32_t*)g.vals[0], (const uint32_t*)g.heads, n_sel, g.sbits,
                     (const uint32_t*)f->blk_start.as<uint32_t>(), (const int32_t*)f->blk_size.as<int32_t>(),
                     (const double*)f->xyz_ord.as<double>(), (const double*)nt.corner.as<double>(),
                     (const double*)nt.edge.as<double>(), (const int32_t*)sidx_d, n_poses, n_rows,
-                    reinterpret_cast<double*>(tb), reinterpret_cast<int32_t*>(tb + lay.o_row),
-                    reinterpret_cast<int32_t*>(tb + lay.o_pose), reinterpret_cast<int32_t*>(tb + lay.o_first),
-                    reinterpret_cast<int32_t*>(tb + lay.o_node), reinterpret_cast<double*>(tb + lay.o_anchor));
+                    Carve::at(tb, lay.mom), Carve::at(tb, lay.row), Carve::at(tb, lay.pose), Carve::at(tb, lay.first),
+                    Carve::at(tb, lay.node), Carve::at(tb, lay.anchor));
         HIP_TRY(ctx, hipGetLastError());
       }
       {
         // (the first order's keys are read for the last time here: the second sort takes their buffers over)
         KTimer t(ctx, "adj_order");
-        uint64_t* keys2[2] = {keys[1 - res], keys[res]};
-        uint32_t* vals2[2] = {vals[1 - res], vals[res]};
-        OCTL_LAUNCH(k_adj_keys2, dim3(grid_for(n_sel)), dim3(256), 0, st, (const uint64_t*)keys[res], n_sel, sbits,
-                    nbits, keys2[0], vals2[0]);
+        uint64_t* keys2[2] = {g.keys[1], g.keys[0]};
+        uint32_t* vals2[2] = {g.vals[1], g.vals[0]};
+        OCTL_LAUNCH(k_adj_keys2, dim3(grid_for(n_sel)), dim3(256), 0, st, (const uint64_t*)g.keys[0], n_sel, g.sbits,
+                    g.nbits, keys2[0], vals2[0]);
         HIP_TRY(ctx, hipGetLastError());
         int res2 = 0;
-        OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys2, vals2, n_sel, kbits, f->pl_hist, &res2));
-        HIP_TRY(ctx, hipMemcpyAsync(tb + lay.o_ord2, vals2[res2], (size_t)n_sel * 4, hipMemcpyDeviceToDevice, st));
+        OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys2, vals2, n_sel, g.kbits, f->pl_hist, &res2));
+        HIP_TRY(ctx, hipMemcpyAsync(Carve::at(tb, lay.ord2), vals2[res2], (size_t)n_sel * 4, hipMemcpyDeviceToDevice,
+                                    st));
       }
       HIP_TRY(ctx, hipStreamSynchronize(st));  // (the uploads above read host arrays that end with this call)
     }
@@ -462,19 +443,7 @@ int adj_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   f->adj_chunk_off = chunk_off;
   f->adj_blocks = n_sel;
   f->adj_rows = n_sel > 0 ? n_rows : 0;
-  f->adj_valid = true;
-  return OCTL_OK;
-}
-
-int adj_begin(octl_forest* f, const char* what, const uint8_t* slot_sel, int32_t n_sel, std::vector<uint8_t>* sel) {
-  OCTL_TRY(forest_settle(f));
-  octl_ctx* ctx = f->ctx;
-  if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "%s before build", what);
-  const int n_poses = (int)f->pose_off.size() - 1;
-  if (slot_sel && n_sel != n_poses)
-    return octl_set_error(ctx, OCTL_E_INVALID, "slot selection has %d entries for %d poses", n_sel, n_poses);
-  sel->clear();
-  if (slot_sel) sel->assign(slot_sel, slot_sel + n_poses);
+  f->adj_stamp = f->content_stamp;
   return OCTL_OK;
 }
 
@@ -486,9 +455,11 @@ int octl_forest_adjustment_system(octl_forest* f, const uint8_t* slot_sel, int32
                                   const double origin[3], int32_t min_points, int32_t min_poses, double max_variance,
                                   double* sums, int64_t* counts, int64_t n_leaves[2]) {
   if (!f) return OCTL_E_INVALID;
-  std::vector<uint8_t> sel;
-  OCTL_TRY(adj_begin(f, "adjustment_system", slot_sel, n_sel, &sel));
+  OCTL_TRY(forest_settle(f));
   octl_ctx* ctx = f->ctx;
+  if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "adjustment_system before build");
+  std::vector<uint8_t> sel;
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
   const int n_poses = (int)f->pose_off.size() - 1;
   int S = 0;
   for (int s = 0; s < n_poses; ++s) S += (sel.empty() || sel[s]) ? 1 : 0;
@@ -502,7 +473,7 @@ int octl_forest_adjustment_system(octl_forest* f, const uint8_t* slot_sel, int32
     if (!std::isfinite(origin[k]))
       return octl_set_error(ctx, OCTL_E_INVALID, "adjustment_system: the origin is not finite");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!(f->adj_valid && f->adj_sel == sel)) OCTL_TRY(adj_prepare(f, sel));
+  if (!(forest_table_valid(f, f->adj_stamp) && f->adj_sel == sel)) OCTL_TRY(adj_prepare(f, sel));
   f->adj_called = false;
   n_leaves[0] = f->adj_rows;
   n_leaves[1] = 0;
@@ -514,45 +485,39 @@ int octl_forest_adjustment_system(octl_forest* f, const uint8_t* slot_sel, int32
   }
   hipStream_t st = ctx->stream;
   const int64_t n_rows = f->adj_rows, n_chunks = f->adj_chunk_off[(size_t)S];
-  const AdjTab tab(f->adj_blocks, n_rows, n_chunks, S, n_poses);
+  const AdjTab tab(f->adj_blocks, n_rows, n_chunks, S);
   const AdjCall lay(n_rows, n_chunks, S);
-  OCTL_TRY(devbuf_reserve(ctx, f->adj_call, lay.total));
-  const char* tb = static_cast<const char*>(f->adj_tab.p);
-  char* cb = static_cast<char*>(f->adj_call.p);
+  OCTL_TRY(devbuf_reserve(ctx, f->adj_call, lay.plan.total));
+  DevBuf &tb = f->adj_tab, &cb = f->adj_call;
   AdjParams P;
   std::memcpy(P.c, origin, sizeof P.c);
   P.max_variance = max_variance >= 0.0 ? max_variance : -1.0;
   P.min_points = min_points;
   P.min_poses = min_poses;
-  const double* mom = reinterpret_cast<const double*>(tb);
-  const int32_t* blk_row = reinterpret_cast<const int32_t*>(tb + tab.o_row);
-  const int32_t* blk_pose = reinterpret_cast<const int32_t*>(tb + tab.o_pose);
-  const double* anchor = reinterpret_cast<const double*>(tb + tab.o_anchor);
-  double* T_d = reinterpret_cast<double*>(cb);
-  double* plane_d = reinterpret_cast<double*>(cb + lay.o_plane);
-  int32_t* used_d = reinterpret_cast<int32_t*>(cb + lay.o_used);
-  int32_t* wused_d = reinterpret_cast<int32_t*>(cb + lay.o_wused);
-  double* rows_d = reinterpret_cast<double*>(cb + lay.o_rows);
-  double* out_d = reinterpret_cast<double*>(cb + lay.o_out);
+  const double *mom = Carve::at(tb, tab.mom), *anchor = Carve::at(tb, tab.anchor);
+  const int32_t *blk_row = Carve::at(tb, tab.row), *blk_pose = Carve::at(tb, tab.pose);
+  double *T_d = Carve::at(cb, lay.T), *plane_d = Carve::at(cb, lay.plane), *rows_d = Carve::at(cb, lay.rows);
+  double* out_d = Carve::at(cb, lay.out);
+  int32_t *used_d = Carve::at(cb, lay.used), *wused_d = Carve::at(cb, lay.wused);
   HIP_TRY(ctx, hipMemcpyAsync(T_d, transforms, (size_t)S * 96, hipMemcpyHostToDevice, st));
   {
     KTimer t(ctx, "adj_leaf");
     OCTL_LAUNCH(k_adj_leaf, dim3(grid_for(n_rows)), dim3(256), 0, st, n_rows,
-                reinterpret_cast<const int32_t*>(tb + tab.o_first), anchor, mom, blk_pose, (const double*)T_d, P,
+                (const int32_t*)Carve::at(tb, tab.first), anchor, mom, blk_pose, (const double*)T_d, P,
                 plane_d, used_d, wused_d);
     HIP_TRY(ctx, hipGetLastError());
   }
   {
     KTimer t(ctx, "adj_partial");
     OCTL_LAUNCH(k_adj_partial, dim3((unsigned)n_chunks), dim3(256), 0, st,
-                reinterpret_cast<const int4*>(tb + tab.o_chunks), reinterpret_cast<const uint32_t*>(tb + tab.o_ord2),
-                mom, blk_row, anchor, (const double*)plane_d, (const int32_t*)used_d, (const double*)T_d, P, rows_d);
+                (const int4*)Carve::at(tb, tab.chunks), (const uint32_t*)Carve::at(tb, tab.ord2), mom, blk_row, anchor,
+                (const double*)plane_d, (const int32_t*)used_d, (const double*)T_d, P, rows_d);
     HIP_TRY(ctx, hipGetLastError());
   }
   {
     KTimer t(ctx, "adj_fold");
     OCTL_LAUNCH(k_adj_fold, dim3((unsigned)S + 1), dim3(256), 0, st, (const double*)rows_d,
-                reinterpret_cast<const int32_t*>(tb + tab.o_choff), S, (const int32_t*)wused_d, ceil_div(n_rows, 64),
+                (const int32_t*)Carve::at(tb, tab.choff), S, (const int32_t*)wused_d, ceil_div(n_rows, 64),
                 out_d);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -576,7 +541,7 @@ int octl_forest_adjustment_tables(octl_forest* f, int64_t cap_leaves, int32_t* n
   OCTL_TRY(forest_settle(f));
   octl_ctx* ctx = f->ctx;
   if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "adjustment_tables before build");
-  if (!(f->adj_valid && f->adj_called))
+  if (!(forest_table_valid(f, f->adj_stamp) && f->adj_called))
     return octl_set_error(ctx, OCTL_E_STATE,
                           "adjustment_tables: no octl_forest_adjustment_system call on the forest as it is now");
   if (!n_leaves || !n_blocks) return octl_set_error(ctx, OCTL_E_INVALID, "bad adjustment_tables arguments");
@@ -585,31 +550,30 @@ int octl_forest_adjustment_tables(octl_forest* f, int64_t cap_leaves, int32_t* n
   *n_leaves = n_rows;
   *n_blocks = nb;
   if (n_rows == 0) return OCTL_OK;
-  const int S = (int)f->adj_slots.size(), n_poses = (int)f->pose_off.size() - 1;
-  const AdjTab tab(nb, n_rows, f->adj_chunk_off[(size_t)S], S, n_poses);
+  const int S = (int)f->adj_slots.size();
+  const AdjTab tab(nb, n_rows, f->adj_chunk_off[(size_t)S], S);
   const AdjCall lay(n_rows, f->adj_chunk_off[(size_t)S], S);
-  const char* tb = static_cast<const char*>(f->adj_tab.p);
-  const char* cb = static_cast<const char*>(f->adj_call.p);
+  DevBuf &tb = f->adj_tab, &cb = f->adj_call;
   hipStream_t st = ctx->stream;
   const bool leaves = cap_leaves >= n_rows && (node || count || mean || normal || lambda0 || used);
   const bool blocks = cap_blocks >= nb && (blk_node || blk_slot || blk_moments);
   if (!leaves && !blocks) return OCTL_OK;
   std::vector<int32_t> node_h((size_t)n_rows), used_h, row_h, pose_h;
   std::vector<double> plane_h;
-  HIP_TRY(ctx, hipMemcpyAsync(node_h.data(), tb + tab.o_node, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(node_h.data(), Carve::at(tb, tab.node), (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
   if (leaves) {
     used_h.resize((size_t)n_rows);
     plane_h.resize((size_t)n_rows * 8);
-    HIP_TRY(ctx, hipMemcpyAsync(used_h.data(), cb + lay.o_used, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(plane_h.data(), cb + lay.o_plane, (size_t)n_rows * 64, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(used_h.data(), Carve::at(cb, lay.used), (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(plane_h.data(), Carve::at(cb, lay.plane), (size_t)n_rows * 64, hipMemcpyDeviceToHost, st));
   }
   if (blocks) {
     row_h.resize((size_t)nb);
     pose_h.resize((size_t)nb);
-    HIP_TRY(ctx, hipMemcpyAsync(row_h.data(), tb + tab.o_row, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(pose_h.data(), tb + tab.o_pose, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(row_h.data(), Carve::at(tb, tab.row), (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(pose_h.data(), Carve::at(tb, tab.pose), (size_t)nb * 4, hipMemcpyDeviceToHost, st));
     if (blk_moments)
-      HIP_TRY(ctx, hipMemcpyAsync(blk_moments, tb, (size_t)nb * AJ_MOM * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(blk_moments, Carve::at(tb, tab.mom), (size_t)nb * AJ_MOM * 8, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (leaves)

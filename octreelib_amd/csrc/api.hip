@@ -141,9 +141,9 @@ void octl_forest_destroy(octl_forest* f) {
         &f->hist, &f->idxbuf[0], &f->idxbuf[1], &f->pathbuf[0], &f->pathbuf[1], &f->flags,
         &f->entries, &f->split[0], &f->split[1], &f->split_tiles[0], &f->split_tiles[1],
         &f->child_sc, &f->pose_off_dev, &f->scheme_dev, &f->root_up, &f->vlin_dev, &f->vcode_dev[0],
-        &f->vcode_dev[1], &f->split_lambda, &f->split_n, &f->pl_rows, &f->pl_plane, &f->pl_node_row, &f->pl_sort,
-        &f->pl_hist, &f->q_stage, &f->rg_rows, &f->adj_tab, &f->adj_sort, &f->adj_call, &f->nn_tab, &f->nn_sort, &f->seg_tab,
-        &f->seg_out, &f->seg_sort})
+        &f->vcode_dev[1], &f->split_lambda, &f->split_n, &f->pl_rows, &f->pl_plane, &f->pl_node_row, &f->grp_scratch,
+        &f->pl_hist, &f->q_stage, &f->rg_rows, &f->adj_tab, &f->adj_call, &f->nn_tab, &f->seg_tab, &f->seg_out,
+        &f->seg_sort})
     devbuf_release(f->ctx, *b);
   delete f;
 }
@@ -184,7 +184,7 @@ int octl_forest_clear(octl_forest* f) {
   f->n_blocks = 0;
   f->mask_valid = false;
   f->split_stats_valid = false;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   return OCTL_OK;
 }
 
@@ -198,7 +198,7 @@ static void forest_drop_scheme(octl_forest* f) {
   f->mask_valid = false;
   f->store_dirty = true;
   f->split_stats_valid = false;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
 }
 
 int octl_forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
@@ -268,7 +268,7 @@ int octl_forest_set_scheme(octl_forest* f, const int32_t* first_child, const int
   f->n_internal = n_internal;
   f->uniform_epoch = false;
   f->split_stats_valid = false;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   if (new_epoch > f->epoch) f->epoch = new_epoch;
   // only first_child / epoch of this table are meaningful until the next (keep_scheme) build,
   // which has to place every point again
@@ -441,7 +441,7 @@ int octl_forest_set_contents(octl_forest* f, int64_t n_blocks, const int32_t* bl
   f->store_dirty = false;
   f->mask_valid = false;
   f->fast_order_valid = false;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   // the voxel box of the new points is not known (rows may have left their cubes): the next build finds it
   f->max_block_hint = INT64_MAX;
   f->bbox_stale = true;

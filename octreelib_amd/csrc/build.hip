@@ -2144,7 +2144,7 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   if (scheme_mask && !keep_scheme)
     for (int p = 0; p < rq.n_poses; ++p) rq.all_scheme = rq.all_scheme && scheme_mask[p];
   f->fast_order_valid = false;  // (the block table is about to change)
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   f->max_block_hint = INT64_MAX;
   BuildTrace trace;
   trace.on = ctx->opt.trace_build != 0;

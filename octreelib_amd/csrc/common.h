@@ -309,7 +309,27 @@ int octl_collect_timings(octl_ctx* ctx);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // byte offsets of the parts of a packed scratch buffer: every part starts 256-byte aligned
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// ... as a plan: add<T>(count) appends a part of `count` T behind the parts added so far, each rounded up by align256,
+// and returns its typed handle; `total` is what devbuf_reserve is asked for, at(buffer, part) the part in a buffer that
+// holds the plan from its first byte.
+struct Carve {
+  template <typename T>
+  struct Part {
+    size_t off = 0;
+  };
+  size_t total = 0;
+  template <typename T>
+  constexpr Part<T> add(size_t count) {
+    const Part<T> part{total};
+    total += align256(count * sizeof(T));
+    return part;
+  }
+  template <typename T>
+  static T* at(DevBuf& b, Part<T> part) {
+    return reinterpret_cast<T*>(static_cast<char*>(b.p) + part.off);
+  }
+};
 // workgroups of 256 threads for n items, one item per thread (n = 0: no workgroup - the caller guards or clamps)
 static inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n, 256); }
 // bits needed to hold max_value (0 for 0)
@@ -325,6 +345,16 @@ static inline int octl_readback(octl_ctx* ctx, const void* src_dev, int64_t coun
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   std::memcpy(out, ctx->small_host, (size_t)count * 4);
   return OCTL_OK;
+}
+
+// the download of the first `count` elements of a part of a device table into `dst`, enqueued when the caller asked
+// for that array (dst != nullptr) and it is not empty; *any = something is on its way: the caller waits once
+template <typename T>
+static inline hipError_t octl_download(octl_ctx* ctx, T* dst, DevBuf& src, Carve::Part<T> part, size_t count,
+                                       bool* any) {
+  if (!dst || count == 0) return hipSuccess;
+  *any = true;
+  return hipMemcpyAsync(dst, Carve::at(src, part), count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
 }
 
 // ---- device-wide primitives (scan.hip, radix_sort.hip) ------------------------------------

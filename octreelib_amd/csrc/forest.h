@@ -110,55 +110,61 @@ struct octl_forest {
   bool split_stats_valid = false;
   int64_t split_stats_nodes = 0;
 
-  // octl_forest_pooled_leaf_stats (query.hip): one plane per leaf over a selection of poses.  pl_rows holds the result
-  // table of the last call as it is downloaded ([node i32 | count i64 | mean 3 | cov 6 | eigval 3 | eigvec 9], every
-  // part 256-byte aligned for pl_cap rows), pl_plane the 64-byte rows octl_forest_point_to_plane gathers
-  // {nx, ny, nz, mx, my, mz, lambda0, (double)count}, pl_node_row the row of every scheme node (-1: none).  Valid
-  // while contents and scheme are the ones the call saw: every entry point that changes either clears pooled_valid.
-  DevBuf pl_rows, pl_plane, pl_node_row, pl_sort, pl_hist;
-  bool pooled_valid = false;
+  // ---- derived map tables: made from the block table, the ordered points, the node table and the pose offsets, and
+  // kept until one of those changes.  Whoever changes one calls forest_contents_changed (below), which moves
+  // content_stamp on.  A table records the stamp it was made at in X_stamp - 0: none; zeroed when its prepare / compute
+  // function starts, set when it has succeeded, so one that failed half way stays invalid - and is valid while that is
+  // the forest's (forest_table_valid).  Each keeps the pose selection it was made for too (X_sel, empty: every pose):
+  // another selection makes it again.  The packed tables are Carve plans (common.h).
+  uint64_t content_stamp = 1;
+  // what the pooled planes, the adjustment tables and the neighbour index need while they are made and nobody reads
+  // once that function has returned - the (node, slot) grouping of the blocks (leaf_moments.h: block_groups) with the
+  // function's own words behind it - and the histograms of every radix sort.  One stream per forest: one of each.
+  // (The three layouts differ by a few hundred bytes, which the slack of devbuf_reserve takes as a rule; where it does
+  // not, the first call of one behind another grows a buffer in use, which costs that call one host wait.)
+  DevBuf grp_scratch, pl_hist;
+
+  // octl_forest_pooled_leaf_stats (leaf_stats.hip): one plane per leaf over a selection of poses.  pl_rows holds the
+  // result table of the last call as it is downloaded (PoolLayout below, for pl_cap rows), pl_plane the 64-byte rows
+  // octl_forest_point_to_plane gathers {nx, ny, nz, mx, my, mz, lambda0, (double)count}, pl_node_row the row of every
+  // scheme node (-1: none; allocated by the first computation, which is how query_plane_table tells "none" from
+  // "stale").
+  DevBuf pl_rows, pl_plane, pl_node_row;
+  uint64_t pl_stamp = 0;
   int64_t pl_n = 0, pl_cap = 0;
-  std::vector<uint8_t> pl_sel;  // the pose selection of that call (empty: every pose)
+  std::vector<uint8_t> pl_sel;
   DevBuf q_stage;               // staging of the host forms of the queries (points in, answers out)
   DevBuf rg_rows;               // octl_forest_registration_system (register.hip): per-chunk partial sums, the result
 
-  // octl_forest_adjustment_system (adjust.hip).  Prepared once per map and pose selection, stamped as the pooled table
-  // is (every entry point that clears pooled_valid clears adj_valid; another selection recomputes):
+  // octl_forest_adjustment_system (adjust.hip), prepared once per map and pose selection:
   //  adj_tab   the selected (leaf, pose) blocks in (node, slot) order - 80-byte moments {n, sum d, sum d d^T} about the
   //            leaf's centre, leaf row and selection index of every block - the leaves (first block, node, anchor), the
   //            second order of the same blocks by (slot, node) and its chunks of at most 1024 blocks of one pose;
-  //  adj_sort  scratch of the two sorts (their histograms go through pl_hist, which nobody keeps anything in);
   //  adj_call  what one call writes: transforms, the plane row of every leaf, the per-chunk partial sums, the result.
-  DevBuf adj_tab, adj_sort, adj_call;
-  bool adj_valid = false;
+  DevBuf adj_tab, adj_call;
+  uint64_t adj_stamp = 0;
   bool adj_called = false;           // adj_call holds the leaf table of a call on this preparation
-  std::vector<uint8_t> adj_sel;      // the pose selection it was made for (empty: every pose)
+  std::vector<uint8_t> adj_sel;
   std::vector<int32_t> adj_slots;    // slot of every selected pose, ascending
   std::vector<int64_t> adj_chunk_off;  // [S + 1] first chunk of every selected pose
   int64_t adj_blocks = 0, adj_rows = 0;  // selected blocks, leaves that hold one
 
-  // octl_forest_nearest (nearest.hip): the index node -> run of selected (leaf, pose) blocks in slot order.  Made by
-  // the call that finds it missing, stale or made for another selection; stamped as the pooled table is (every entry
-  // point that clears pooled_valid clears nn_valid):
-  //  nn_tab   one 16-byte record {start, size, slot, store offset of the pose} per block in (node, slot) order, then
-  //           first record and number of records of every node of the scheme;
-  //  nn_sort  scratch of the sort (its histograms go through pl_hist).
-  DevBuf nn_tab, nn_sort;
-  bool nn_valid = false;
-  std::vector<uint8_t> nn_sel;  // the pose selection it was made for (empty: every pose)
+  // octl_forest_nearest (nearest.hip): the index node -> run of selected (leaf, pose) blocks in slot order, made by
+  // the call that finds none that is valid.  nn_tab: one 16-byte record {start, size, slot, store offset of the pose}
+  // per block in (node, slot) order, then first record and number of records of every node of the scheme.
+  DevBuf nn_tab;
+  uint64_t nn_stamp = 0;
+  std::vector<uint8_t> nn_sel;
 
   // octl_forest_plane_segments (segments.hip): the face adjacency of the rows of the pooled table, the connected
-  // components of the coplanar ones and one merged plane per component.  Cached with the arguments it was made for and
-  // stamped as the pooled table is (every entry point that clears pooled_valid clears seg_valid):
-  //  seg_tab   [neighbour i32 x6 per row | label i32 per row];
-  //  seg_out   for seg_cap segments [root i32 | leaves i32 | count i64 | mean 3 | cov 6 | eigval 3 | eigvec 9];
-  //  seg_sort  what one computation needs besides: parents, roots, head flags and their scan, the sort's keys and
-  //            values, the first sorted position of every segment (the histograms go through pl_hist).
-  // Every part of the three starts 256-byte aligned.
-  DevBuf seg_tab, seg_out, seg_sort;
-  bool seg_valid = false;
+  // components of the coplanar ones and one merged plane per component, cached with the arguments they were made for.
+  // A pooled table made again for another selection drops them too (octl_forest_plane_segments zeroes seg_stamp).
+  // seg_sort is the scratch of one computation (union-find, head flags, sort, segment starts).  It is not grp_scratch:
+  // sized by the rows, and a first call would grow that buffer while the pooled table's kernels read it - a host wait.
+  DevBuf seg_tab, seg_out, seg_sort;  // (SegRowLayout, SegOutLayout: segments.hip)
+  uint64_t seg_stamp = 0;
   int64_t seg_rows = 0, seg_n = 0, seg_cap = 0;  // rows the tables were made for, segments, segments the layout holds
-  std::vector<uint8_t> seg_sel;                  // the pose selection (empty: every pose)
+  std::vector<uint8_t> seg_sel;
   int32_t seg_min_points = 0;
   double seg_max_variance = -1.0, seg_cos_min = 0.0, seg_max_offset = 0.0;
 
@@ -256,21 +262,35 @@ int forest_fix_origin(octl_forest* f, const int bb[6]);
 int forest_sync_vcodes(octl_forest* f);
 int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info);
 
+// The block table, the ordered points, the node table or the pose offsets have changed or are about to (a pose added
+// or extended, a build, a scheme or contents installed, points masked or filtered away, a clear, a scheme dropped):
+// every derived map table of the forest is stale from here on.
+static inline void forest_contents_changed(octl_forest* f) { ++f->content_stamp; }
+// the table that recorded `stamp` describes the forest as it is now
+static inline bool forest_table_valid(const octl_forest* f, uint64_t stamp) { return stamp == f->content_stamp; }
+// the pose selection of a map query as the tables keep it (empty: every pose); one entry per pose or refused
+static inline int forest_selection(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, std::vector<uint8_t>* sel) {
+  const int n_poses = (int)f->pose_off.size() - 1;
+  if (slot_sel && n_sel != n_poses)
+    return octl_set_error(f->ctx, OCTL_E_INVALID, "slot selection has %d entries for %d poses", n_sel, n_poses);
+  sel->assign(slot_sel, slot_sel + (slot_sel ? n_poses : 0));
+  return OCTL_OK;
+}
+
 // leaf_stats.hip: layout of f->pl_rows for `cap` rows, and the pooled table of the selection `sel` (empty: every pose)
 // of the forest as it stands - what octl_forest_pooled_leaf_stats and octl_forest_plane_segments make when they find
 // none that is valid
 struct PoolLayout {
-  size_t o_count, o_mean, o_cov, o_w, o_v, total;
-  explicit PoolLayout(int64_t cap) {
-    const size_t c = (size_t)(cap > 1 ? cap : 1);
-    o_count = align256(c * 4);
-    o_mean = o_count + align256(c * 8);
-    o_cov = o_mean + align256(c * 24);
-    o_w = o_cov + align256(c * 48);
-    o_v = o_w + align256(c * 24);
-    total = o_v + align256(c * 72);
-  }
+  size_t c;  // rows (at least one)
+  Carve plan;
+  Carve::Part<int32_t> node = plan.add<int32_t>(c);
+  Carve::Part<int64_t> count = plan.add<int64_t>(c);
+  Carve::Part<double> mean = plan.add<double>(3 * c), cov = plan.add<double>(6 * c), w = plan.add<double>(3 * c),
+                      v = plan.add<double>(9 * c);
+  constexpr explicit PoolLayout(int64_t cap) : c((size_t)(cap > 1 ? cap : 1)) {}
 };
+static_assert(PoolLayout(100).cov.off == 4096 && PoolLayout(100).v.off == 11520 && PoolLayout(100).plan.total == 18944,
+              "PoolLayout offsets: a part starts where the 256-byte-rounded parts before it end");
 int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel);
 
 // mask.hip: wait for the counts an asynchronous apply_mask left in flight (octl_forest_apply_mask_async) and book

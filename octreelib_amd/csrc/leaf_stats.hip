@@ -181,30 +181,26 @@ extern "C" int octl_forest_leaf_stats(octl_forest* f, const int32_t* block_ids, 
   const bool chunked = f->max_block_hint > LS_CHUNK;
   // at most ceil(n / L) < 2 n / L chunks per block of n > L points, and the blocks are disjoint runs of xyz_ord
   const int64_t cap = chunked ? 2 * f->n_ord / LS_CHUNK + 2 : 0;
-  // ctx->ls_buf: [ids i32 | count i64 | mean 3 f64 | cov 6 f64 | eigval 3 f64 | eigvec 9 f64 | counter + claim i32
-  //               per table block | work items int2 | chunk partials 9 f64], every part 256-byte aligned
-  const size_t o_cnt = align256((size_t)nb * 4);
-  const size_t o_mean = o_cnt + align256((size_t)nb * 8);
-  const size_t o_cov = o_mean + align256((size_t)nb * 24);
-  const size_t o_w = o_cov + align256((size_t)nb * 48);
-  const size_t o_v = o_w + (eigen ? align256((size_t)nb * 24) : 0);
-  const size_t o_claim = o_v + (eigen ? align256((size_t)nb * 72) : 0);
-  const size_t claim_bytes = chunked ? 16 + (size_t)f->n_blocks * 4 : 0;
-  const size_t o_work = o_claim + align256(claim_bytes);
-  const size_t o_part = o_work + align256((size_t)cap * 8);
-  const size_t total = o_part + (size_t)cap * 72;
-  OCTL_TRY(devbuf_reserve(ctx, ctx->ls_buf, total));
-  char* base = static_cast<char*>(ctx->ls_buf.p);
-  int32_t* ids_d = reinterpret_cast<int32_t*>(base);
-  int64_t* cnt_d = reinterpret_cast<int64_t*>(base + o_cnt);
-  double* mean_d = reinterpret_cast<double*>(base + o_mean);
-  double* cov_d = reinterpret_cast<double*>(base + o_cov);
-  double* w_d = eigen ? reinterpret_cast<double*>(base + o_w) : nullptr;
-  double* v_d = eigen ? reinterpret_cast<double*>(base + o_v) : nullptr;
-  uint32_t* counter_d = reinterpret_cast<uint32_t*>(base + o_claim);
-  int32_t* claim_d = reinterpret_cast<int32_t*>(base + o_claim + 16);
-  int2* work_d = reinterpret_cast<int2*>(base + o_work);
-  double* part_d = reinterpret_cast<double*>(base + o_part);
+  // ctx->ls_buf: [ids i32 | count i64 | mean 3 f64 | cov 6 f64 | eigval 3 f64 | eigvec 9 f64 | counter (16 bytes) +
+  //               claim i32 per table block | work items int2 | chunk partials 9 f64]
+  Carve plan;
+  const size_t n = (size_t)nb, ne = eigen ? n : 0, claim_bytes = chunked ? 16 + (size_t)f->n_blocks * 4 : 0;
+  const auto ids_p = plan.add<int32_t>(n);
+  const auto cnt_p = plan.add<int64_t>(n);
+  const auto mean_p = plan.add<double>(3 * n), cov_p = plan.add<double>(6 * n);
+  const auto w_p = plan.add<double>(3 * ne), v_p = plan.add<double>(9 * ne);
+  const auto counter_p = plan.add<uint32_t>(claim_bytes / 4);
+  const auto work_p = plan.add<int2>((size_t)cap);
+  const auto part_p = plan.add<double>(9 * (size_t)cap);
+  OCTL_TRY(devbuf_reserve(ctx, ctx->ls_buf, plan.total));
+  DevBuf& lb = ctx->ls_buf;
+  int32_t* ids_d = Carve::at(lb, ids_p);
+  int64_t* cnt_d = Carve::at(lb, cnt_p);
+  double *mean_d = Carve::at(lb, mean_p), *cov_d = Carve::at(lb, cov_p), *part_d = Carve::at(lb, part_p);
+  double *w_d = eigen ? Carve::at(lb, w_p) : nullptr, *v_d = eigen ? Carve::at(lb, v_p) : nullptr;
+  uint32_t* counter_d = Carve::at(lb, counter_p);
+  int32_t* claim_d = reinterpret_cast<int32_t*>(counter_d + 4);
+  int2* work_d = Carve::at(lb, work_p);
   const uint32_t* bstart = f->blk_start.as<uint32_t>();
   const int32_t* bsize = f->blk_size.as<int32_t>();
   const double* xyz = f->xyz_ord.as<double>();
@@ -247,15 +243,16 @@ extern "C" int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t 
   if (n == 0) return OCTL_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t o_w = align256((size_t)n * 48), o_v = o_w + align256((size_t)n * 24);
-  OCTL_TRY(devbuf_reserve(ctx, ctx->ls_buf, o_v + (size_t)n * 72));
-  char* base = static_cast<char*>(ctx->ls_buf.p);
-  HIP_TRY(ctx, hipMemcpyAsync(base, cov6, (size_t)n * 48, hipMemcpyHostToDevice, st));
-  OCTL_LAUNCH(k_sym3_eigen, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const double*)base, n,
-              reinterpret_cast<double*>(base + o_w), reinterpret_cast<double*>(base + o_v));
+  Carve plan;
+  const auto c_p = plan.add<double>(6 * (size_t)n), w_p = plan.add<double>(3 * (size_t)n);
+  const auto v_p = plan.add<double>(9 * (size_t)n);
+  OCTL_TRY(devbuf_reserve(ctx, ctx->ls_buf, plan.total));
+  double *c_d = Carve::at(ctx->ls_buf, c_p), *w_d = Carve::at(ctx->ls_buf, w_p), *v_d = Carve::at(ctx->ls_buf, v_p);
+  HIP_TRY(ctx, hipMemcpyAsync(c_d, cov6, (size_t)n * 48, hipMemcpyHostToDevice, st));
+  OCTL_LAUNCH(k_sym3_eigen, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const double*)c_d, n, w_d, v_d);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(eigval, base + o_w, (size_t)n * 24, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(eigvec, base + o_v, (size_t)n * 72, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(eigval, w_d, (size_t)n * 24, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(eigvec, v_d, (size_t)n * 72, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return OCTL_OK;
 }
@@ -346,58 +343,34 @@ int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel) {
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
   const int64_t nb = f->n_blocks, n_nodes = f->nodes[f->cur].n;
-  const int n_poses = (int)f->pose_off.size() - 1;
-  f->pooled_valid = false;
+  f->pl_stamp = 0;
   OCTL_TRY(devbuf_reserve(ctx, f->pl_node_row, (size_t)std::max<int64_t>(n_nodes, 1) * 4));
   if (n_nodes > 0) HIP_TRY(ctx, hipMemsetAsync(f->pl_node_row.p, 0xFF, (size_t)n_nodes * 4, st));
   int64_t n_rows = 0;
   if (nb > 0) {
-    const int sbits = std::max(1, bits_for((uint64_t)std::max(n_poses, 1)));
-    const int kbits = sbits + std::max(1, bits_for((uint64_t)n_nodes));
-    // f->pl_sort: [key u64 x2 | val u32 x2 | heads u32 (+8: the scan's tail) | selection u8 | scan total u32]
-    const size_t o_key1 = align256((size_t)nb * 8), o_val0 = 2 * o_key1, o_val1 = o_val0 + align256((size_t)nb * 4);
-    const size_t o_heads = o_val1 + align256((size_t)nb * 4), o_sel = o_heads + align256(((size_t)nb + 8) * 4);
-    const size_t o_total = o_sel + align256((size_t)std::max(n_poses, 1));
-    OCTL_TRY(devbuf_reserve(ctx, f->pl_sort, o_total + 256));
-    char* base = static_cast<char*>(f->pl_sort.p);
-    uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base), reinterpret_cast<uint64_t*>(base + o_key1)};
-    uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(base + o_val0), reinterpret_cast<uint32_t*>(base + o_val1)};
-    uint32_t* heads = reinterpret_cast<uint32_t*>(base + o_heads);
-    uint8_t* sel_d = reinterpret_cast<uint8_t*>(base + o_sel);
-    uint32_t* total_d = reinterpret_cast<uint32_t*>(base + o_total);
-    if (!sel.empty()) HIP_TRY(ctx, hipMemcpyAsync(sel_d, sel.data(), sel.size(), hipMemcpyHostToDevice, st));
+    BlockGroups g(f, true);
+    const auto total_part = g.plan.add<uint32_t>(1);
+    OCTL_TRY(g.prepare(f, sel));
+    uint32_t* total_d = Carve::at(f->grp_scratch, total_part);
     {
       KTimer t(ctx, "pool_group");
-      OCTL_LAUNCH(k_pool_keys, dim3(grid_for(nb)), dim3(256), 0, st, (const int32_t*)f->blk_node.as<int32_t>(),
-                  (const int32_t*)f->blk_slot.as<int32_t>(), nb, sel.empty() ? (const uint8_t*)nullptr : sel_d,
-                  (int)sel.size(), sbits, kbits, keys[0], vals[0]);
-      HIP_TRY(ctx, hipGetLastError());
-      int res = 0;
-      OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys, vals, nb, kbits + 1, f->pl_hist, &res));
-      OCTL_LAUNCH(k_pool_heads, dim3(grid_for(nb)), dim3(256), 0, st, (const uint64_t*)keys[res], nb, sbits, kbits,
-                  heads);
-      HIP_TRY(ctx, hipGetLastError());
-      OCTL_TRY(octl_exclusive_scan_u32(ctx, heads, heads, nb, total_d));
-      keys[0] = keys[res];
-      vals[0] = vals[res];
+      OCTL_TRY(block_groups(f, (int)sel.size(), total_d, g));
     }
     uint32_t total = 0;
     OCTL_TRY(octl_readback(ctx, total_d, 1, &total));
     n_rows = total;
     if (n_rows > 0) {
       const PoolLayout lay(n_rows);
-      OCTL_TRY(devbuf_reserve(ctx, f->pl_rows, lay.total));
+      OCTL_TRY(devbuf_reserve(ctx, f->pl_rows, lay.plan.total));
       OCTL_TRY(devbuf_reserve(ctx, f->pl_plane, (size_t)n_rows * 64));
-      char* rb = static_cast<char*>(f->pl_rows.p);
-      int32_t* node_d = reinterpret_cast<int32_t*>(rb);
-      int64_t* cnt_d = reinterpret_cast<int64_t*>(rb + lay.o_count);
-      double* mean_d = reinterpret_cast<double*>(rb + lay.o_mean);
-      double* cov_d = reinterpret_cast<double*>(rb + lay.o_cov);
+      int32_t* node_d = Carve::at(f->pl_rows, lay.node);
+      int64_t* cnt_d = Carve::at(f->pl_rows, lay.count);
+      double *mean_d = Carve::at(f->pl_rows, lay.mean), *cov_d = Carve::at(f->pl_rows, lay.cov);
       {
         KTimer t(ctx, "pool_moments");
         const NodeTable& nt = f->nodes[f->cur];
-        OCTL_LAUNCH(k_pool_moments, dim3((unsigned)ceil_div(nb, 4)), dim3(256), 0, st, (const uint64_t*)keys[0],
-                    (const uint32_t*)vals[0], (const uint32_t*)heads, nb, sbits, kbits,
+        OCTL_LAUNCH(k_pool_moments, dim3((unsigned)ceil_div(nb, 4)), dim3(256), 0, st, (const uint64_t*)g.keys[0],
+                    (const uint32_t*)g.vals[0], (const uint32_t*)g.heads, nb, g.sbits, g.kbits,
                     (const uint32_t*)f->blk_start.as<uint32_t>(), (const int32_t*)f->blk_size.as<int32_t>(),
                     (const double*)f->xyz_ord.as<double>(), (const double*)nt.corner.as<double>(),
                     (const double*)nt.edge.as<double>(), n_rows, node_d, cnt_d, mean_d, cov_d);
@@ -407,15 +380,15 @@ int pooled_compute(octl_forest* f, const std::vector<uint8_t>& sel) {
         KTimer t(ctx, "pool_eigen");
         OCTL_LAUNCH(k_pool_eigen, dim3(grid_for(n_rows)), dim3(256), 0, st, n_rows, (const int32_t*)node_d,
                     (const int64_t*)cnt_d, (const double*)mean_d, (const double*)cov_d,
-                    reinterpret_cast<double*>(rb + lay.o_w), reinterpret_cast<double*>(rb + lay.o_v),
-                    f->pl_plane.as<double>(), f->pl_node_row.as<int32_t>());
+                    Carve::at(f->pl_rows, lay.w), Carve::at(f->pl_rows, lay.v), f->pl_plane.as<double>(),
+                    f->pl_node_row.as<int32_t>());
         HIP_TRY(ctx, hipGetLastError());
       }
     }
   }
   f->pl_n = f->pl_cap = n_rows;
   f->pl_sel = sel;
-  f->pooled_valid = true;
+  f->pl_stamp = f->content_stamp;
   return OCTL_OK;
 }
 
@@ -426,32 +399,22 @@ extern "C" int octl_forest_pooled_leaf_stats(octl_forest* f, const uint8_t* slot
   OCTL_TRY(forest_settle(f));
   octl_ctx* ctx = f->ctx;
   if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "pooled_leaf_stats before build");
-  const int n_poses = (int)f->pose_off.size() - 1;
-  if (slot_sel && n_sel != n_poses)
-    return octl_set_error(ctx, OCTL_E_INVALID, "slot selection has %d entries for %d poses", n_sel, n_poses);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<uint8_t> sel;
-  if (slot_sel) sel.assign(slot_sel, slot_sel + n_poses);
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
   // (a fill behind a size query finds the table the query made: the same selection on an unchanged forest)
-  if (!(f->pooled_valid && f->pl_sel == sel)) OCTL_TRY(pooled_compute(f, sel));
+  if (!(forest_table_valid(f, f->pl_stamp) && f->pl_sel == sel)) OCTL_TRY(pooled_compute(f, sel));
   *n_leaves = f->pl_n;
   const int64_t n = f->pl_n;
   if (n <= 0 || cap < n) return OCTL_OK;
-  hipStream_t st = ctx->stream;
   const PoolLayout lay(f->pl_cap);
-  const char* rb = static_cast<const char*>(f->pl_rows.p);
   bool any = false;
-  auto down = [&](void* dst, size_t off, size_t bytes) -> hipError_t {
-    if (!dst) return hipSuccess;
-    any = true;
-    return hipMemcpyAsync(dst, rb + off, bytes, hipMemcpyDeviceToHost, st);
-  };
-  HIP_TRY(ctx, down(node, 0, (size_t)n * 4));
-  HIP_TRY(ctx, down(count, lay.o_count, (size_t)n * 8));
-  HIP_TRY(ctx, down(mean, lay.o_mean, (size_t)n * 24));
-  HIP_TRY(ctx, down(cov6, lay.o_cov, (size_t)n * 48));
-  HIP_TRY(ctx, down(eigval, lay.o_w, (size_t)n * 24));
-  HIP_TRY(ctx, down(eigvec, lay.o_v, (size_t)n * 72));
-  if (any) HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, octl_download(ctx, node, f->pl_rows, lay.node, (size_t)n, &any));
+  HIP_TRY(ctx, octl_download(ctx, count, f->pl_rows, lay.count, (size_t)n, &any));
+  HIP_TRY(ctx, octl_download(ctx, mean, f->pl_rows, lay.mean, (size_t)n * 3, &any));
+  HIP_TRY(ctx, octl_download(ctx, cov6, f->pl_rows, lay.cov, (size_t)n * 6, &any));
+  HIP_TRY(ctx, octl_download(ctx, eigval, f->pl_rows, lay.w, (size_t)n * 3, &any));
+  HIP_TRY(ctx, octl_download(ctx, eigvec, f->pl_rows, lay.v, (size_t)n * 9, &any));
+  if (any) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return OCTL_OK;
 }

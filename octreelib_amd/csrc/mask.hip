@@ -309,8 +309,7 @@ int apply_device_mask(octl_forest* f, int64_t* n_alive_out, bool async = false) 
   const int64_t n = f->n_ord, nb = f->n_blocks;
   f->mask_valid = false;
   f->fast_order_valid = false;  // block ids change
-  // (the pooled planes, the adjustment tables and the neighbour index describe the points that are about to leave)
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);  // (the points that are about to leave)
   if (n > 0 && nb > 0) {
     KTimer t(ctx, "apply_mask");
     uint32_t* small = ctx->small.as<uint32_t>();

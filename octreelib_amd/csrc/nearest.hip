@@ -10,7 +10,7 @@
 // stack (parent / first_child; the child number of a node is node - first_child[parent[node]]), and a cube is skipped
 // when a lower bound of the d2 of anything it can hold exceeds the k-th best so far (cube_gap below has the argument).
 // What a leaf holds comes from an index node -> run of (leaf, pose) blocks in slot order that is made once per forest
-// state and pose selection (nn_prepare: the (node, slot) grouping of octl_forest_pooled_leaf_stats, leaf_moments.h).
+// state and pose selection (nn_prepare: the (node, slot) grouping of the selected blocks, leaf_moments.h: block_groups).
 #include <algorithm>
 #include <cmath>
 
@@ -262,13 +262,14 @@ int launch_nearest(octl_ctx* ctx, const double* xyz_dev, int64_t n, int k, doubl
 
 // f->nn_tab: [record uint4 per block | first i32 per node | count i32 per node]
 struct NNTab {
-  size_t o_first, o_cnt, total;
-  NNTab(int64_t nb, int64_t n_nodes) {
-    o_first = align256((size_t)std::max<int64_t>(nb, 1) * 16);
-    o_cnt = o_first + align256((size_t)std::max<int64_t>(n_nodes, 1) * 4);
-    total = o_cnt + align256((size_t)std::max<int64_t>(n_nodes, 1) * 4);
-  }
+  size_t nb, n_nodes;  // (at least one of each)
+  Carve plan;
+  Carve::Part<uint4> rec = plan.add<uint4>(nb);
+  Carve::Part<int32_t> first = plan.add<int32_t>(n_nodes), cnt = plan.add<int32_t>(n_nodes);
+  constexpr NNTab(int64_t blocks, int64_t nodes)
+      : nb((size_t)std::max<int64_t>(blocks, 1)), n_nodes((size_t)std::max<int64_t>(nodes, 1)) {}
 };
+static_assert(NNTab(100, 10).cnt.off == 2048 && NNTab(100, 10).plan.total == 2304, "NNTab offsets");
 
 // the index node -> run of blocks for the selection `sel` (empty: every pose) of the forest as it stands
 int nn_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
@@ -276,47 +277,33 @@ int nn_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   hipStream_t st = ctx->stream;
   const int64_t nb = f->n_blocks, n_nodes = f->nodes[f->cur].n;
   const int n_poses = (int)f->pose_off.size() - 1;
-  f->nn_valid = false;
+  f->nn_stamp = 0;
   const NNTab lay(nb, n_nodes);
-  OCTL_TRY(devbuf_reserve(ctx, f->nn_tab, lay.total));
-  char* tb = static_cast<char*>(f->nn_tab.p);
+  OCTL_TRY(devbuf_reserve(ctx, f->nn_tab, lay.plan.total));
   // (runs start empty: a node without a selected block, and every node of a forest without blocks, holds nothing)
-  HIP_TRY(ctx, hipMemsetAsync(tb + lay.o_first, 0, lay.total - lay.o_first, st));
+  HIP_TRY(ctx, hipMemsetAsync(Carve::at(f->nn_tab, lay.first), 0, lay.plan.total - lay.first.off, st));
   if (nb > 0 && n_poses > 0) {
-    const int sbits = std::max(1, bits_for((uint64_t)std::max(n_poses, 1)));
-    const int kbits = sbits + std::max(1, bits_for((uint64_t)n_nodes));
-    // f->nn_sort: [key u64 x2 | val u32 x2 | selection u8 | store offset u32 per pose]
-    const size_t o_key1 = align256((size_t)nb * 8), o_val0 = 2 * o_key1, o_val1 = o_val0 + align256((size_t)nb * 4);
-    const size_t o_sel = o_val1 + align256((size_t)nb * 4), o_off = o_sel + align256((size_t)n_poses);
-    OCTL_TRY(devbuf_reserve(ctx, f->nn_sort, o_off + align256((size_t)n_poses * 4)));
-    char* base = static_cast<char*>(f->nn_sort.p);
-    uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base), reinterpret_cast<uint64_t*>(base + o_key1)};
-    uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(base + o_val0), reinterpret_cast<uint32_t*>(base + o_val1)};
-    uint8_t* sel_d = reinterpret_cast<uint8_t*>(base + o_sel);
-    uint32_t* off_d = reinterpret_cast<uint32_t*>(base + o_off);
+    // f->grp_scratch: the grouping (no rows), then [store offset u32 per pose]
+    BlockGroups g(f, false);
+    const auto off_part = g.plan.add<uint32_t>((size_t)n_poses);
+    OCTL_TRY(g.prepare(f, sel));
+    uint32_t* off_d = Carve::at(f->grp_scratch, off_part);
     std::vector<uint32_t> off32((size_t)n_poses);
     for (int s = 0; s < n_poses; ++s) off32[(size_t)s] = (uint32_t)f->pose_off[(size_t)s];  // (store indices are u32)
-    if (!sel.empty()) HIP_TRY(ctx, hipMemcpyAsync(sel_d, sel.data(), sel.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(off_d, off32.data(), (size_t)n_poses * 4, hipMemcpyHostToDevice, st));
     {
       KTimer t(ctx, "nn_group");
-      OCTL_LAUNCH(k_pool_keys, dim3(grid_for(nb)), dim3(256), 0, st, (const int32_t*)f->blk_node.as<int32_t>(),
-                  (const int32_t*)f->blk_slot.as<int32_t>(), nb, sel.empty() ? (const uint8_t*)nullptr : sel_d,
-                  (int)sel.size(), sbits, kbits, keys[0], vals[0]);
-      HIP_TRY(ctx, hipGetLastError());
-      int res = 0;
-      OCTL_TRY(octl_radix_sort_u64_u32(ctx, keys, vals, nb, kbits + 1, f->pl_hist, &res));
-      OCTL_LAUNCH(k_nn_runs, dim3(grid_for(nb)), dim3(256), 0, st, (const uint64_t*)keys[res],
-                  (const uint32_t*)vals[res], nb, sbits, kbits, (const uint32_t*)f->blk_start.as<uint32_t>(),
+      OCTL_TRY(block_groups(f, (int)sel.size(), nullptr, g));
+      OCTL_LAUNCH(k_nn_runs, dim3(grid_for(nb)), dim3(256), 0, st, (const uint64_t*)g.keys[0],
+                  (const uint32_t*)g.vals[0], nb, g.sbits, g.kbits, (const uint32_t*)f->blk_start.as<uint32_t>(),
                   (const int32_t*)f->blk_size.as<int32_t>(), (const uint32_t*)off_d, n_nodes,
-                  reinterpret_cast<uint4*>(tb), reinterpret_cast<int32_t*>(tb + lay.o_first),
-                  reinterpret_cast<int32_t*>(tb + lay.o_cnt));
+                  Carve::at(f->nn_tab, lay.rec), Carve::at(f->nn_tab, lay.first), Carve::at(f->nn_tab, lay.cnt));
       HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));  // (the uploads above read host arrays that end with this call)
   }
   f->nn_sel = sel;
-  f->nn_valid = true;
+  f->nn_stamp = f->content_stamp;
   return OCTL_OK;
 }
 
@@ -325,7 +312,6 @@ int nearest_begin(octl_forest* f, int64_t n, int32_t k, double max_distance, con
                   bool pointers_ok, NNTables* T) {
   OCTL_TRY(query_begin(f, "nearest", &T->t));
   octl_ctx* ctx = f->ctx;
-  const int n_poses = (int)f->pose_off.size() - 1;
   if (query_bad_count(n) || !pointers_ok) return octl_set_error(ctx, OCTL_E_INVALID, "bad nearest arguments");
   if (k < 1 || k > OCTL_NN_MAX_K)
     return octl_set_error(ctx, OCTL_E_INVALID, "nearest: k = %d is outside 1 .. %d", k, OCTL_NN_MAX_K);
@@ -336,23 +322,20 @@ int nearest_begin(octl_forest* f, int64_t n, int32_t k, double max_distance, con
                           "nearest: max_distance %g exceeds twice the voxel edge %g (a query would touch more than 5 "
                           "voxels per axis)",
                           max_distance, f->edge);
-  if (slot_sel && n_sel != n_poses)
-    return octl_set_error(ctx, OCTL_E_INVALID, "slot selection has %d entries for %d poses", n_sel, n_poses);
+  std::vector<uint8_t> sel;
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
   if (f->displaced_rows)
     return octl_set_error(ctx, OCTL_E_STATE,
                           "nearest: map_leaf_points has moved rows outside their leaves - the search cannot bound "
                           "what a cube holds");
   if (n == 0) return OCTL_OK;
-  std::vector<uint8_t> sel;
-  if (slot_sel) sel.assign(slot_sel, slot_sel + n_poses);
-  if (!(f->nn_valid && f->nn_sel == sel)) OCTL_TRY(nn_prepare(f, sel));
+  if (!(forest_table_valid(f, f->nn_stamp) && f->nn_sel == sel)) OCTL_TRY(nn_prepare(f, sel));
   const NodeTable& nt = f->nodes[f->cur];
   const NNTab lay(f->n_blocks, nt.n);
-  const char* tb = static_cast<const char*>(f->nn_tab.p);
   T->parent = nt.parent.as<int32_t>();
-  T->rec = reinterpret_cast<const uint4*>(tb);
-  T->first = reinterpret_cast<const int32_t*>(tb + lay.o_first);
-  T->cnt = reinterpret_cast<const int32_t*>(tb + lay.o_cnt);
+  T->rec = Carve::at(f->nn_tab, lay.rec);
+  T->first = Carve::at(f->nn_tab, lay.first);
+  T->cnt = Carve::at(f->nn_tab, lay.cnt);
   T->xyz_ord = f->xyz_ord.as<double>();
   T->ord_idx = f->ord_idx.as<uint32_t>();
   T->max_steps = 4 * nt.n + 64;
@@ -375,17 +358,17 @@ int octl_forest_nearest(octl_forest* f, const double* xyz, int64_t n, int32_t k,
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
   const size_t nk = (size_t)n * (size_t)k;
-  const size_t o_idx = align256((size_t)n * 24), o_d2 = o_idx + align256(nk * 8), o_slot = o_d2 + align256(nk * 8);
-  const size_t o_cnt = o_slot + align256(nk * 4);
-  OCTL_TRY(devbuf_reserve(ctx, f->q_stage, o_cnt + (size_t)n * 4));
-  char* base = static_cast<char*>(f->q_stage.p);
-  int64_t* idx_d = reinterpret_cast<int64_t*>(base + o_idx);
-  double* d2_d = reinterpret_cast<double*>(base + o_d2);
-  int32_t* slot_d = reinterpret_cast<int32_t*>(base + o_slot);
-  int32_t* cnt_d = reinterpret_cast<int32_t*>(base + o_cnt);
-  HIP_TRY(ctx, hipMemcpyAsync(base, xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
-  OCTL_TRY(launch_nearest(ctx, reinterpret_cast<const double*>(base), n, k, max_distance, T, slot_d, idx_d, d2_d,
-                          cnt_d));
+  Carve plan;  // f->q_stage: [queries 3 f64 | index i64 x k | d2 f64 x k | slot i32 x k | count i32]
+  const auto q_part = plan.add<double>((size_t)n * 3);
+  const auto idx_part = plan.add<int64_t>(nk);
+  const auto d2_part = plan.add<double>(nk);
+  const auto slot_part = plan.add<int32_t>(nk), cnt_part = plan.add<int32_t>((size_t)n);
+  OCTL_TRY(devbuf_reserve(ctx, f->q_stage, plan.total));
+  double *q_d = Carve::at(f->q_stage, q_part), *d2_d = Carve::at(f->q_stage, d2_part);
+  int64_t* idx_d = Carve::at(f->q_stage, idx_part);
+  int32_t *slot_d = Carve::at(f->q_stage, slot_part), *cnt_d = Carve::at(f->q_stage, cnt_part);
+  HIP_TRY(ctx, hipMemcpyAsync(q_d, xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
+  OCTL_TRY(launch_nearest(ctx, q_d, n, k, max_distance, T, slot_d, idx_d, d2_d, cnt_d));
   HIP_TRY(ctx, hipMemcpyAsync(slot_out, slot_d, nk * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(index_out, idx_d, nk * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(d2_out, d2_d, nk * 8, hipMemcpyDeviceToHost, st));

@@ -97,7 +97,7 @@ int query_begin(octl_forest* f, const char* what, QueryTables* t) {
 
 int query_plane_table(octl_forest* f, const char* what, int32_t min_points, double max_variance, PlaneTable* pt) {
   octl_ctx* ctx = f->ctx;
-  if (!f->pooled_valid) {
+  if (!forest_table_valid(f, f->pl_stamp)) {
     if (!f->pl_node_row.p)
       return octl_set_error(ctx, OCTL_E_STATE,
                             "%s: the forest has no pooled leaf planes (call octl_forest_pooled_leaf_stats first)",

@@ -549,7 +549,7 @@ static int add_routed(octl_forest* f, octl_ctx* rctx, int32_t* slot) {
   f->n_alive += n;
   f->pose_off.push_back(f->n_store);
   f->store_dirty = true;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   return OCTL_OK;
 }
 

@@ -276,59 +276,52 @@ __global__ __launch_bounds__(256) void k_seg_merge(const uint32_t* __restrict__ 
 
 // f->seg_tab for `rows` rows: [neighbour i32 x6 | label i32]
 struct SegRowLayout {
-  size_t o_label, total;
-  explicit SegRowLayout(int64_t rows) {
-    const size_t r = (size_t)std::max<int64_t>(rows, 1);
-    o_label = align256(r * 24);
-    total = o_label + align256(r * 4);
-  }
+  size_t r;  // rows (at least one)
+  Carve plan;
+  Carve::Part<int32_t> neighbour = plan.add<int32_t>(6 * r), label = plan.add<int32_t>(r);
+  constexpr explicit SegRowLayout(int64_t rows) : r((size_t)std::max<int64_t>(rows, 1)) {}
 };
+static_assert(SegRowLayout(100).label.off == 2560 && SegRowLayout(100).plan.total == 3072, "SegRowLayout offsets");
 
 // f->seg_out for `cap` segments: [root i32 | leaves i32 | count i64 | mean 3 | cov 6 | eigval 3 | eigvec 9]
 struct SegOutLayout {
-  size_t o_leaves, o_count, o_mean, o_cov, o_w, o_v, total;
-  explicit SegOutLayout(int64_t cap) {
-    const size_t c = (size_t)std::max<int64_t>(cap, 1);
-    o_leaves = align256(c * 4);
-    o_count = o_leaves + align256(c * 4);
-    o_mean = o_count + align256(c * 8);
-    o_cov = o_mean + align256(c * 24);
-    o_w = o_cov + align256(c * 48);
-    o_v = o_w + align256(c * 24);
-    total = o_v + align256(c * 72);
-  }
+  size_t c;  // segments (at least one)
+  Carve plan;
+  Carve::Part<int32_t> root = plan.add<int32_t>(c), leaves = plan.add<int32_t>(c);
+  Carve::Part<int64_t> count = plan.add<int64_t>(c);
+  Carve::Part<double> mean = plan.add<double>(3 * c), cov = plan.add<double>(6 * c), w = plan.add<double>(3 * c),
+                      v = plan.add<double>(9 * c);
+  constexpr explicit SegOutLayout(int64_t cap) : c((size_t)std::max<int64_t>(cap, 1)) {}
 };
+static_assert(SegOutLayout(100).v.off == 12032 && SegOutLayout(100).plan.total == 19456, "SegOutLayout offsets");
 
 int segments_compute(octl_forest* f, const QueryTables& qt, const std::vector<uint8_t>& sel, const SegGate& g) {
   octl_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
-  f->seg_valid = false;
+  f->seg_stamp = 0;
   const int64_t R = f->pl_n, n_nodes = f->nodes[f->cur].n;
   int64_t S = 0;
   if (R > 0) {
     const SegRowLayout rl(R);
-    OCTL_TRY(devbuf_reserve(ctx, f->seg_tab, rl.total));
+    OCTL_TRY(devbuf_reserve(ctx, f->seg_tab, rl.plan.total));
     // f->seg_sort: [parent i32 | root i32 | heads u32 (+8: the scan's tail) | key u64 x2 | val u32 x2 |
     //               first u32 (rows + 1) | total, error word]
-    const size_t o_root = align256((size_t)R * 4), o_heads = 2 * o_root;
-    const size_t o_key0 = o_heads + align256(((size_t)R + 8) * 4), o_key1 = o_key0 + align256((size_t)R * 8);
-    const size_t o_val0 = o_key1 + align256((size_t)R * 8), o_val1 = o_val0 + align256((size_t)R * 4);
-    const size_t o_first = o_val1 + align256((size_t)R * 4), o_words = o_first + align256(((size_t)R + 1) * 4);
-    OCTL_TRY(devbuf_reserve(ctx, f->seg_sort, o_words + 256));
-    char* tb = static_cast<char*>(f->seg_tab.p);
-    char* sb = static_cast<char*>(f->seg_sort.p);
-    int32_t* neighbour = reinterpret_cast<int32_t*>(tb);
-    int32_t* label = reinterpret_cast<int32_t*>(tb + rl.o_label);
-    int32_t* parent = reinterpret_cast<int32_t*>(sb);
-    int32_t* root = reinterpret_cast<int32_t*>(sb + o_root);
-    uint32_t* heads = reinterpret_cast<uint32_t*>(sb + o_heads);
-    uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(sb + o_key0), reinterpret_cast<uint64_t*>(sb + o_key1)};
-    uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(sb + o_val0), reinterpret_cast<uint32_t*>(sb + o_val1)};
-    uint32_t* first = reinterpret_cast<uint32_t*>(sb + o_first);
-    uint32_t* words = reinterpret_cast<uint32_t*>(sb + o_words);
+    Carve plan;
+    const size_t r = (size_t)R;
+    const auto parent_part = plan.add<int32_t>(r), root_part = plan.add<int32_t>(r);
+    const auto heads_part = plan.add<uint32_t>(r + 8);
+    const auto key0_part = plan.add<uint64_t>(r), key1_part = plan.add<uint64_t>(r);
+    const auto val0_part = plan.add<uint32_t>(r), val1_part = plan.add<uint32_t>(r);
+    const auto first_part = plan.add<uint32_t>(r + 1), words_part = plan.add<uint32_t>(2);
+    OCTL_TRY(devbuf_reserve(ctx, f->seg_sort, plan.total));
+    DevBuf& sb = f->seg_sort;
+    int32_t *neighbour = Carve::at(f->seg_tab, rl.neighbour), *label = Carve::at(f->seg_tab, rl.label);
+    int32_t *parent = Carve::at(sb, parent_part), *root = Carve::at(sb, root_part);
+    uint32_t *heads = Carve::at(sb, heads_part), *first = Carve::at(sb, first_part), *words = Carve::at(sb, words_part);
+    uint64_t* keys[2] = {Carve::at(sb, key0_part), Carve::at(sb, key1_part)};
+    uint32_t* vals[2] = {Carve::at(sb, val0_part), Carve::at(sb, val1_part)};
     const PoolLayout pl(f->pl_cap);
-    const char* rb = static_cast<const char*>(f->pl_rows.p);
-    const int32_t* r_node = reinterpret_cast<const int32_t*>(rb);
+    const int32_t* r_node = Carve::at(f->pl_rows, pl.node);
     PlaneTable pt;
     pt.node_row = f->pl_node_row.as<int32_t>();
     pt.rows = f->pl_plane.as<double2>();
@@ -371,16 +364,10 @@ int segments_compute(octl_forest* f, const QueryTables& qt, const std::vector<ui
     }
     if (S > 0) {
       const SegOutLayout ol(S);
-      OCTL_TRY(devbuf_reserve(ctx, f->seg_out, ol.total));
-      char* ob = static_cast<char*>(f->seg_out.p);
-      SegOut o;
-      o.root = reinterpret_cast<int32_t*>(ob);
-      o.n_leaves = reinterpret_cast<int32_t*>(ob + ol.o_leaves);
-      o.count = reinterpret_cast<int64_t*>(ob + ol.o_count);
-      o.mean = reinterpret_cast<double*>(ob + ol.o_mean);
-      o.cov = reinterpret_cast<double*>(ob + ol.o_cov);
-      o.eigval = reinterpret_cast<double*>(ob + ol.o_w);
-      o.eigvec = reinterpret_cast<double*>(ob + ol.o_v);
+      OCTL_TRY(devbuf_reserve(ctx, f->seg_out, ol.plan.total));
+      DevBuf& ob = f->seg_out;
+      const SegOut o{Carve::at(ob, ol.root), Carve::at(ob, ol.leaves), Carve::at(ob, ol.count), Carve::at(ob, ol.mean),
+                     Carve::at(ob, ol.cov),  Carve::at(ob, ol.w),      Carve::at(ob, ol.v)};
       int res = 0;
       {
         KTimer t(ctx, "seg_sort");
@@ -391,9 +378,9 @@ int segments_compute(octl_forest* f, const QueryTables& qt, const std::vector<ui
                   first);
       HIP_TRY(ctx, hipGetLastError());
       OCTL_LAUNCH(k_seg_merge, dim3((unsigned)ceil_div(S, 4)), dim3(256), 0, st, (const uint32_t*)vals[res],
-                  (const uint32_t*)first, R, (uint32_t)S, r_node, reinterpret_cast<const int64_t*>(rb + pl.o_count),
-                  reinterpret_cast<const double*>(rb + pl.o_mean), reinterpret_cast<const double*>(rb + pl.o_cov),
-                  reinterpret_cast<const double*>(rb + pl.o_w), reinterpret_cast<const double*>(rb + pl.o_v), o);
+                  (const uint32_t*)first, R, (uint32_t)S, r_node, (const int64_t*)Carve::at(f->pl_rows, pl.count),
+                  (const double*)Carve::at(f->pl_rows, pl.mean), (const double*)Carve::at(f->pl_rows, pl.cov),
+                  (const double*)Carve::at(f->pl_rows, pl.w), (const double*)Carve::at(f->pl_rows, pl.v), o);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
@@ -404,7 +391,7 @@ int segments_compute(octl_forest* f, const QueryTables& qt, const std::vector<ui
   f->seg_max_variance = g.max_variance;
   f->seg_cos_min = g.cos_min;
   f->seg_max_offset = g.max_offset;
-  f->seg_valid = true;
+  f->seg_stamp = f->content_stamp;
   return OCTL_OK;
 }
 
@@ -427,46 +414,39 @@ extern "C" int octl_forest_plane_segments(octl_forest* f, const uint8_t* slot_se
   if (std::isnan(max_variance)) return octl_set_error(ctx, OCTL_E_INVALID, "plane_segments: max_variance is NaN");
   QueryTables qt;
   OCTL_TRY(query_begin(f, "plane_segments", &qt));
-  const int n_poses = (int)f->pose_off.size() - 1;
-  if (slot_sel && n_sel != n_poses)
-    return octl_set_error(ctx, OCTL_E_INVALID, "slot selection has %d entries for %d poses", n_sel, n_poses);
   std::vector<uint8_t> sel;
-  if (slot_sel) sel.assign(slot_sel, slot_sel + n_poses);
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
   SegGate g;
   g.min_points = min_points;
   g.max_variance = max_variance >= 0.0 ? max_variance : -1.0;
   g.cos_min = cos_min;
   g.max_offset = max_offset;
-  if (!(f->pooled_valid && f->pl_sel == sel)) {
-    f->seg_valid = false;  // (made from another table)
+  if (!(forest_table_valid(f, f->pl_stamp) && f->pl_sel == sel)) {
+    f->seg_stamp = 0;  // (made from another table)
     OCTL_TRY(pooled_compute(f, sel));
   }
   // (a fill behind a size query finds the tables the query made: the same arguments on an unchanged forest)
-  if (!(f->seg_valid && f->seg_sel == sel && f->seg_rows == f->pl_n && f->seg_min_points == g.min_points &&
-        f->seg_max_variance == g.max_variance && f->seg_cos_min == g.cos_min && f->seg_max_offset == g.max_offset))
+  if (!(forest_table_valid(f, f->seg_stamp) && f->seg_sel == sel && f->seg_rows == f->pl_n &&
+        f->seg_min_points == g.min_points && f->seg_max_variance == g.max_variance && f->seg_cos_min == g.cos_min &&
+        f->seg_max_offset == g.max_offset))
     OCTL_TRY(segments_compute(f, qt, sel, g));
   const int64_t R = f->seg_rows, S = f->seg_n;
   *n_rows = R;
   *n_segments = S;
   if (cap_rows < R || cap_segments < S) return OCTL_OK;
-  hipStream_t st = ctx->stream;
   bool any = false;
-  auto down = [&](void* dst, const DevBuf& src, size_t off, size_t bytes) -> hipError_t {
-    if (!dst || bytes == 0) return hipSuccess;
-    any = true;
-    return hipMemcpyAsync(dst, static_cast<const char*>(src.p) + off, bytes, hipMemcpyDeviceToHost, st);
-  };
   const SegRowLayout rl(R);
   const SegOutLayout ol(f->seg_cap);
-  HIP_TRY(ctx, down(neighbour, f->seg_tab, 0, (size_t)R * 24));
-  HIP_TRY(ctx, down(label, f->seg_tab, rl.o_label, (size_t)R * 4));
-  HIP_TRY(ctx, down(root, f->seg_out, 0, (size_t)S * 4));
-  HIP_TRY(ctx, down(n_leaves, f->seg_out, ol.o_leaves, (size_t)S * 4));
-  HIP_TRY(ctx, down(count, f->seg_out, ol.o_count, (size_t)S * 8));
-  HIP_TRY(ctx, down(mean, f->seg_out, ol.o_mean, (size_t)S * 24));
-  HIP_TRY(ctx, down(cov6, f->seg_out, ol.o_cov, (size_t)S * 48));
-  HIP_TRY(ctx, down(eigval, f->seg_out, ol.o_w, (size_t)S * 24));
-  HIP_TRY(ctx, down(eigvec, f->seg_out, ol.o_v, (size_t)S * 72));
-  if (any) HIP_TRY(ctx, hipStreamSynchronize(st));
+  const size_t r = (size_t)R, n = (size_t)S;
+  HIP_TRY(ctx, octl_download(ctx, neighbour, f->seg_tab, rl.neighbour, r * 6, &any));
+  HIP_TRY(ctx, octl_download(ctx, label, f->seg_tab, rl.label, r, &any));
+  HIP_TRY(ctx, octl_download(ctx, root, f->seg_out, ol.root, n, &any));
+  HIP_TRY(ctx, octl_download(ctx, n_leaves, f->seg_out, ol.leaves, n, &any));
+  HIP_TRY(ctx, octl_download(ctx, count, f->seg_out, ol.count, n, &any));
+  HIP_TRY(ctx, octl_download(ctx, mean, f->seg_out, ol.mean, n * 3, &any));
+  HIP_TRY(ctx, octl_download(ctx, cov6, f->seg_out, ol.cov, n * 6, &any));
+  HIP_TRY(ctx, octl_download(ctx, eigval, f->seg_out, ol.w, n * 3, &any));
+  HIP_TRY(ctx, octl_download(ctx, eigvec, f->seg_out, ol.v, n * 9, &any));
+  if (any) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return OCTL_OK;
 }

@@ -404,7 +404,7 @@ static int commit_new_pose(octl_forest* f, int64_t n, int32_t* slot) {
   f->n_alive += n;
   f->pose_off.push_back(f->n_store);
   f->store_dirty = true;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   return OCTL_OK;
 }
 
@@ -448,7 +448,7 @@ static int extend_pose_impl(octl_forest* f, int32_t slot, const void* xyz, int64
   f->n_alive += n;
   for (int p = slot + 1; p <= n_poses; ++p) f->pose_off[p] += n;
   f->store_dirty = true;
-  f->pooled_valid = f->adj_valid = f->nn_valid = f->seg_valid = false;
+  forest_contents_changed(f);
   f->append_only = false;  // the store was rotated: the next build re-places everything
   return OCTL_OK;
 }
