@@ -411,6 +411,28 @@ int octl_forest_adjustment_tables(octl_forest* f, int64_t cap_leaves, int32_t* n
                                   double* normal, double* lambda0, uint8_t* used, int64_t* n_leaves,
                                   int64_t cap_blocks, int32_t* blk_node, int32_t* blk_slot, double* blk_moments,
                                   int64_t* n_blocks);
+/* Write adjusted poses back into the map: one rigid transform per selected pose, applied in place to the rows of the
+ * point store, on the device.  slot_sel / n_sel select the poses as octl_forest_adjustment_system takes them (NULL:
+ * all); S = number of selected poses, in ascending slot order; transforms = S row-major 3x4 (R | t) - the transforms
+ * octl_forest_adjustment_system was evaluated at can be passed straight in.  Every alive row p of a selected pose
+ * becomes p'_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i in f64, every product and sum rounded, no fma
+ * (octreelib_amd/registration.py: transform_np, bit for bit).  Rows of the other poses are COPIED bit for bit, not
+ * multiplied by an identity (1 * -0.0 + 0 * y is +0.0); a selected pose given the identity does follow the formula.
+ * Rows that a mask or filter removed stay removed and keep their place; their coordinates are unspecified afterwards.
+ * After a successful call the forest is what a fresh forest of the same configuration would be after the poses had been
+ * added again in slot order, each with its surviving rows as moved - no scheme, the voxels the moved points fall into,
+ * every derived table stale, the next build starts from the top-level voxels - except that rows keep their positions in
+ * the store, so octl_forest_get_perm and octl_forest_nearest still name rows of the clouds as they were first added.
+ * TRANSACTIONAL: when an alive moved coordinate is not finite or has a top-level voxel index outside +-2^30 (mode 0),
+ * or fails the cube's placement test 0 <= fl(p - corner) < edge (mode 1), the call returns OCTL_E_DOMAIN and nothing
+ * observable has changed: the forest is still built and every query answers as before.  A caller's buffer the store
+ * reads in place (octl_forest_add_pose_adopt) is never written; after a successful call the store is the forest's own.
+ * One upload, one kernel (a stream over the whole store: 24 B read and written per row, plus the alive flag) and one
+ * host wait, whatever the size; the moved rows are written out of place into the bucket build's partition scratch,
+ * which then swaps with the store (no memory beyond what a build holds).  Works built or not.  S = 0 or an empty store:
+ * a successful no-op that changes no state.  OCTL_E_INVALID: n_sel is not the number of poses, NULL transforms with
+ * S > 0, a non-finite transform entry (checked before anything runs).  No reference counterpart.                    */
+int octl_forest_transform_poses(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, const double* transforms);
 /* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
 int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 

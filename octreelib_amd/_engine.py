@@ -893,6 +893,34 @@ class Forest:
                                                   pose_numbers)
         return adjust_np(system, len(chosen), initial, fixed, max_iterations, tolerance, damping)
 
+    def transform_poses(self, transforms, slots=None):
+        """Move the stored rows of the poses of `slots` (None: all; ascending slot order, as adjust orders its
+        result) by one rigid transform each, in place on the device (octl_forest_transform_poses: one kernel, one
+        host wait).  Afterwards this is the mirror of a fresh forest that holds the same slots: no scheme, nothing
+        built, voxel membership and creation order not captured yet.  A DomainError changes nothing, here or there."""
+        from octreelib_amd.adjustment import as_transforms
+
+        sel, n_sel, chosen = self._adjust_selection(slots)
+        S = len(chosen)
+        T = np.ascontiguousarray(as_transforms(transforms, S).reshape(S, 12))
+        self.ctx.check(self.lib.octl_forest_transform_poses(self.handle, nat.ptr(sel), n_sel,
+                                                            nat.ptr(T) if S else None))
+        if S == 0 or sum(self.slot_sizes) == 0:
+            return   # (the library's no-op: nothing moved, whatever was built stays built)
+        self.epoch = 0
+        self.slot_epoch = [0] * self.n_slots
+        self.has_scheme = False
+        self.info = None
+        self._dirty = True
+        self.n_ord = 0
+        self.slot_voxel_keys = [None] * self.n_slots
+        self._creation_codes = np.empty(0, dtype=np.int64)
+        self._code_origin = None
+        self._member_next = 0
+        self._member_pending = []
+        self._in_place = None   # (the moved store is the forest's own)
+        self._invalidate()
+
     @property
     def perm(self) -> np.ndarray:
         """perm[i] = index (in the concatenation of all pose clouds, slot order) of the point at

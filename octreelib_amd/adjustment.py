@@ -10,7 +10,8 @@ adjustment_system_np is the same on the host: the specification, the higher-prec
 the classes built on the caller's own plug types run through query.HostMap.
 
 The transforms are increments applied to the points as they were inserted; leaf membership stays what the last build
-made it.  With T_p = (R, t) of the block's pose, every line evaluated as written (dot products left to right):
+made it until Grid.transform_poses / OctreeManager.transform_poses write the result back into the map (the points move
+on the device, the map is then subdivided and fitted again).  With T_p = (R, t) of the block's pose, every line evaluated as written (dot products left to right):
   a'  = ((R_i0 a_x + R_i1 a_y) + R_i2 a_z) + t_i in f64 (transform_np),  delta = a' - a in f64
   s'  = R s,  M' = (R M) R^T                                   in `dtype` from here on
   s'' = s' + n delta,  M'' = ((M' + delta s'^T) + s' delta^T) + (n delta) delta^T     the moved points, still about a

@@ -92,6 +92,34 @@ __global__ __launch_bounds__(256) void k_gather_rows(const int32_t* __restrict__
 
 }  // namespace
 
+void forest_reset_scheme(octl_forest* f) {
+  forest_forget_pending(f);   // (counts of a compaction still in flight: nobody will ask for them)
+  f->max_block_hint = INT64_MAX;
+  f->displaced_rows = false;
+  f->store_dirty = true;
+  f->nodes[0].n = f->nodes[1].n = 0;
+  f->cur = 0;
+  f->epoch = 0;
+  f->built = false;
+  f->vkeys.clear();
+  f->vkeys_stale = false;
+  f->vorg_set = false;
+  f->vcode_valid = false;
+  f->fast_order_valid = false;
+  f->built_store = 0;
+  f->built_poses = 0;
+  f->append_only = true;
+  f->n_voxels = 0;
+  f->level_segs.clear();
+  f->n_internal = 0;
+  f->max_depth_reached = 0;
+  f->n_ord = 0;
+  f->n_blocks = 0;
+  f->mask_valid = false;
+  f->split_stats_valid = false;
+  forest_contents_changed(f);
+}
+
 extern "C" {
 
 int octl_forest_create(octl_ctx* ctx, int mode, const double corner[3], double edge,
@@ -143,15 +171,13 @@ void octl_forest_destroy(octl_forest* f) {
         &f->child_sc, &f->pose_off_dev, &f->scheme_dev, &f->root_up, &f->vlin_dev, &f->vcode_dev[0],
         &f->vcode_dev[1], &f->split_lambda, &f->split_n, &f->pl_rows, &f->pl_plane, &f->pl_node_row, &f->grp_scratch,
         &f->pl_hist, &f->q_stage, &f->rg_rows, &f->adj_tab, &f->adj_call, &f->nn_tab, &f->seg_tab, &f->seg_out,
-        &f->seg_sort})
+        &f->seg_sort, &f->xf_tab})
     devbuf_release(f->ctx, *b);
   delete f;
 }
 
 int octl_forest_clear(octl_forest* f) {
   if (!f) return OCTL_E_INVALID;
-  forest_forget_pending(f);   // (counts of a compaction still in flight: nobody will ask for them)
-  f->max_block_hint = INT64_MAX;
   f->bbox_stale = true;   // (nothing is launched: whoever fills the box next resets it first)
   f->alive_stale = false;
   if (f->store_borrowed) {  // back to the forest's own block; the caller's buffer is the caller's again
@@ -160,31 +186,9 @@ int octl_forest_clear(octl_forest* f) {
     f->store_borrowed = false;
   }
   f->bbox_pending = false;
-  f->displaced_rows = false;
   f->pose_off.assign(1, 0);
   f->n_store = f->n_alive = 0;
-  f->store_dirty = true;
-  f->nodes[0].n = f->nodes[1].n = 0;
-  f->cur = 0;
-  f->epoch = 0;
-  f->built = false;
-  f->vkeys.clear();
-  f->vkeys_stale = false;
-  f->vorg_set = false;
-  f->vcode_valid = false;
-  f->fast_order_valid = false;
-  f->built_store = 0;
-  f->built_poses = 0;
-  f->append_only = true;
-  f->n_voxels = 0;
-  f->level_segs.clear();
-  f->n_internal = 0;
-  f->max_depth_reached = 0;
-  f->n_ord = 0;
-  f->n_blocks = 0;
-  f->mask_valid = false;
-  f->split_stats_valid = false;
-  forest_contents_changed(f);
+  forest_reset_scheme(f);
   return OCTL_OK;
 }
 

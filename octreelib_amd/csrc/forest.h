@@ -83,6 +83,9 @@ struct octl_forest {
   // the alive flags of a cloud taken in place (adopted, routed) are not written until something needs them
   // (alive_ensure: a second pose, a re-placement; apply_mask fills them in its first kernel): every point is alive
   bool alive_stale = false;
+  // octl_forest_transform_poses (store.hip): the table one call uploads - the fresh box, the poses' end offsets, a
+  // 3x4 and a selected flag per pose
+  DevBuf xf_tab;
 
   // scheme of the last build
   NodeTable nodes[2];
@@ -266,6 +269,9 @@ int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info);
 // or extended, a build, a scheme or contents installed, points masked or filtered away, a clear, a scheme dropped):
 // every derived map table of the forest is stale from here on.
 static inline void forest_contents_changed(octl_forest* f) { ++f->content_stamp; }
+// api.hip: the forest forgets its scheme, its voxels and every table made from them - what octl_forest_clear leaves,
+// whatever the store holds (octl_forest_clear empties it first; octl_forest_transform_poses has just moved its rows)
+void forest_reset_scheme(octl_forest* f);
 // the table that recorded `stamp` describes the forest as it is now
 static inline bool forest_table_valid(const octl_forest* f, uint64_t stamp) { return stamp == f->content_stamp; }
 // the pose selection of a map query as the tables keep it (empty: every pose); one entry per pose or refused

@@ -1,5 +1,6 @@
 // The point store of a forest: the ingest kernels that copy (or widen) a pose into it, mark its points alive and
-// fold their voxel box, and the C entries that add or extend poses.
+// fold their voxel box, the kernel that moves the stored rows of poses by a rigid transform each, and the C entries
+// that add, extend or move poses.
 #include "forest.h"
 #include "ref_arith.h"
 
@@ -207,6 +208,157 @@ __global__ __launch_bounds__(256) void k_ingest_f32(const float* __restrict__ sr
   }
   if (mode != 0 && (u0 < n_units || (u0 == 0 && n_flat > 0))) box.zero();
   ingest_alive(alive, n);
+  vox_fold_publish(box, bbox);
+}
+
+// ---- transform_poses: the stored rows of the selected poses moved by one rigid transform each --------------------
+// One pass over the WHOLE store, out of place: a row of a selected pose becomes ((R_i0 x + R_i1 y) + R_i2 z) + t_i
+// (registration.py: transform_np - every product and sum rounded, the library is built without contraction), a row of
+// any other pose is copied bit for bit (1 * -0.0 + 0 * y would lose the sign), and the alive rows are folded into a
+// FRESH voxel box, which is where a moved coordinate outside the domain shows.  Dead rows travel along (their
+// coordinates mean nothing) and stay out of the box and of the domain flag.
+// A thread owns XF_PAIRS pairs of consecutive rows (2p, 2p + 1): 48 bytes = three 16-byte units, and a pair starts
+// 16-byte aligned whatever the poses' sizes because the store starts aligned.  A pose may start at an odd row, so the
+// two rows of one pair - and the rows of one workgroup - can belong to different poses: the pose of a row is found
+// from the end offsets (ascending; an empty pose has the end of the one before it).
+constexpr int XF_PAIRS = 2;                        // row pairs per thread
+constexpr int XF_ROWS_PER_WG = 256 * 2 * XF_PAIRS; // 1024
+
+// the table one call uploads: the box the kernel folds into, the end offset of every pose, then per pose the 3x4 and
+// whether the pose is selected
+struct XfSlot {
+  double m[12];
+  int64_t selected;
+  int64_t pad;  // (112 bytes: every record starts 16-byte aligned)
+};
+struct XfLayout {
+  Carve plan;
+  Carve::Part<int32_t> box = plan.add<int32_t>(8);
+  Carve::Part<int64_t> end;
+  Carve::Part<XfSlot> slot;
+  explicit XfLayout(int n_poses) : end(plan.add<int64_t>((size_t)n_poses)), slot(plan.add<XfSlot>((size_t)n_poses)) {}
+};
+
+// first pose at or behind `s` whose end offset lies behind `row` (row < n_store = end[n_poses - 1]: there is one)
+__device__ __forceinline__ int xf_pose_of(const int64_t* __restrict__ end, int s, int n_poses, int64_t row) {
+  int lo = s, hi = n_poses - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (end[mid] > row) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_transform_poses(const double* __restrict__ src, double* __restrict__ dst,
+                                                         const uint8_t* __restrict__ alive /* nullptr: all alive */,
+                                                         int64_t n, const int64_t* __restrict__ end,
+                                                         const XfSlot* __restrict__ slots, int n_poses, int mode,
+                                                         double L, double c0, double c1, double c2,
+                                                         int32_t* __restrict__ bbox) {
+  VoxFold box;
+  const int64_t p0 = (int64_t)blockIdx.x * (256 * XF_PAIRS) + threadIdx.x;
+  const bool al16 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  double2 v[XF_PAIRS][3];
+  uint32_t live[XF_PAIRS];
+#pragma unroll
+  for (int k = 0; k < XF_PAIRS; ++k) {
+    const int64_t r = 2 * (p0 + k * 256);
+    live[k] = 0;
+    v[k][0] = v[k][1] = v[k][2] = make_double2(0.0, 0.0);
+    if (r + 1 < n) {
+      if (al16) {
+        const double2* s2 = reinterpret_cast<const double2*>(src) + 3 * (p0 + k * 256);
+        v[k][0] = s2[0];
+        v[k][1] = s2[1];
+        v[k][2] = s2[2];
+      } else {
+        const double* s1 = src + 3 * r;
+        v[k][0] = make_double2(s1[0], s1[1]);
+        v[k][1] = make_double2(s1[2], s1[3]);
+        v[k][2] = make_double2(s1[4], s1[5]);
+      }
+      // (the flags' block is 16-byte aligned and r is even)
+      live[k] = alive ? (uint32_t)*reinterpret_cast<const uint16_t*>(alive + r) : 0x0101u;
+    } else if (r < n) {  // the last row of an odd number of rows
+      const double* s1 = src + 3 * r;
+      v[k][0] = make_double2(s1[0], s1[1]);
+      v[k][1].x = s1[2];
+      live[k] = alive ? (uint32_t)alive[r] : 1u;
+    }
+  }
+  // the poses of the thread's first and last row bracket those of every row between them
+  const int64_t r_first = 2 * p0, r_last = min(2 * (p0 + (XF_PAIRS - 1) * 256) + 1, n - 1);
+  int s_lo = 0, s_hi = 0;
+  if (r_first < n) {
+    s_lo = xf_pose_of(end, 0, n_poses, r_first);
+    s_hi = end[s_lo] > r_last ? s_lo : xf_pose_of(end, s_lo, n_poses, r_last);
+  }
+  int cur = -1;
+  bool sel = false, any_alive = false;
+  double m[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) m[j] = 0.0;
+#pragma unroll
+  for (int k = 0; k < XF_PAIRS; ++k) {
+    const int64_t r = 2 * (p0 + k * 256);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (r + h >= n) continue;
+      const int s = s_lo == s_hi ? s_lo : xf_pose_of(end, s_lo, n_poses, r + h);
+      if (s != cur) {
+        cur = s;
+        sel = slots[s].selected != 0;
+        if (sel) {
+#pragma unroll
+          for (int j = 0; j < 12; ++j) m[j] = slots[s].m[j];
+        }
+      }
+      double x = h ? v[k][1].y : v[k][0].x, y = h ? v[k][2].x : v[k][0].y, z = h ? v[k][2].y : v[k][1].x;
+      if (sel) {
+        const double tx = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+        const double ty = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+        const double tz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+        x = tx, y = ty, z = tz;
+        if (h) {
+          v[k][1].y = x, v[k][2].x = y, v[k][2].y = z;
+        } else {
+          v[k][0].x = x, v[k][0].y = y, v[k][1].x = z;
+        }
+      }
+      if ((live[k] >> (8 * h)) & 0xFFu) {
+        any_alive = true;
+        if (mode == 0) {
+          box.add(x, 0, L);
+          box.add(y, 1, L);
+          box.add(z, 2, L);
+        } else {
+          // the root's placement test (octree.py:73-75,94-98): 0 <= fl(p - c) < e on every axis, NaN fails
+          const double dx = x - c0, dy = y - c1, dz = z - c2;
+          if (!(dx >= 0.0 && dx < L && dy >= 0.0 && dy < L && dz >= 0.0 && dz < L)) box.bad = true;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < XF_PAIRS; ++k) {
+    const int64_t r = 2 * (p0 + k * 256);
+    if (r + 1 < n) {
+      if (al16) {
+        double2* d2 = reinterpret_cast<double2*>(dst) + 3 * (p0 + k * 256);
+        d2[0] = v[k][0];
+        d2[1] = v[k][1];
+        d2[2] = v[k][2];
+      } else {
+        double* d1 = dst + 3 * r;
+        d1[0] = v[k][0].x, d1[1] = v[k][0].y, d1[2] = v[k][1].x;
+        d1[3] = v[k][1].y, d1[4] = v[k][2].x, d1[5] = v[k][2].y;
+      }
+    } else if (r < n) {
+      double* d1 = dst + 3 * r;
+      d1[0] = v[k][0].x, d1[1] = v[k][0].y, d1[2] = v[k][1].x;
+    }
+  }
+  if (mode != 0 && any_alive) box.zero();
   vox_fold_publish(box, bbox);
 }
 
@@ -507,6 +659,84 @@ int octl_forest_add_pose_adopt(octl_forest* f, const double* xyz_dev, int64_t n,
     return rc;
   }
   return commit_new_pose(f, n, slot);
+}
+
+int octl_forest_transform_poses(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, const double* transforms) {
+  if (!f) return OCTL_E_INVALID;
+  OCTL_TRY(forest_settle(f));
+  octl_ctx* ctx = f->ctx;
+  std::vector<uint8_t> sel;
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
+  const int n_poses = (int)f->pose_off.size() - 1;
+  int S = 0;
+  for (int s = 0; s < n_poses; ++s) S += (sel.empty() || sel[s]) ? 1 : 0;
+  if (S > 0 && !transforms) return octl_set_error(ctx, OCTL_E_INVALID, "transform_poses: null transforms");
+  for (int k = 0; k < 12 * S; ++k)
+    if (!std::isfinite(transforms[k]))
+      return octl_set_error(ctx, OCTL_E_INVALID, "transform_poses: the transform of selected pose %d is not finite",
+                            k / 12);
+  const int64_t n = f->n_store;
+  if (S == 0 || n == 0) return OCTL_OK;  // (nothing moves: the forest, built or not, stays as it is)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // The moved store is written OUT of place, so that a call that fails leaves every byte the forest reads where it
+  // was: into the forest's own block while the store is the caller's buffer (never written), else into the first
+  // partition scratch of the bucket build, which then swaps with the store (a bucket build leaves 32 bytes per point
+  // there and a swapped-out store block holds the store: neither grows here again).  Every allocation comes before
+  // the first launch.
+  DevBuf& target = f->store_borrowed ? f->xyz_own : f->part_xyz[0];
+  OCTL_TRY(devbuf_reserve(ctx, target, (size_t)n * 24 + 16));
+  const XfLayout lay(n_poses);
+  OCTL_TRY(devbuf_reserve(ctx, f->xf_tab, lay.plan.total));
+  OCTL_TRY(devbuf_reserve(ctx, f->bbox_dev, 32));
+  std::vector<char> host(lay.plan.total, 0);
+  {
+    int32_t* box = reinterpret_cast<int32_t*>(host.data() + lay.box.off);
+    for (int a = 0; a < 8; ++a) box[a] = a < 3 ? (1 << 30) : (a < 6 ? -(1 << 30) : 0);
+    std::memcpy(host.data() + lay.end.off, f->pose_off.data() + 1, (size_t)n_poses * 8);
+    XfSlot* slot = reinterpret_cast<XfSlot*>(host.data() + lay.slot.off);
+    for (int s = 0, k = 0; s < n_poses; ++s) {
+      if (!(sel.empty() || sel[s])) continue;
+      std::memcpy(slot[s].m, transforms + 12 * (size_t)k++, sizeof slot[s].m);
+      slot[s].selected = 1;
+    }
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(f->xf_tab.p, host.data(), host.size(), hipMemcpyHostToDevice, st));
+  int32_t* box_d = Carve::at(f->xf_tab, lay.box);
+  {
+    KTimer t(ctx, "transform_poses");
+    OCTL_LAUNCH(k_transform_poses, dim3((unsigned)ceil_div(n, XF_ROWS_PER_WG)), dim3(256), 0, st,
+                (const double*)f->xyz.as<double>(), target.as<double>(),
+                f->alive_stale ? (const uint8_t*)nullptr : (const uint8_t*)f->alive.as<uint8_t>(), n,
+                (const int64_t*)Carve::at(f->xf_tab, lay.end), (const XfSlot*)Carve::at(f->xf_tab, lay.slot), n_poses,
+                f->mode, f->edge, f->corner[0], f->corner[1], f->corner[2], box_d);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  // the one host wait: the box and the domain flag through the context's mirror (also: `host` is ours again)
+  int32_t bb[8];
+  {
+    int32_t* mirror = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->small_host) + MIRROR_BBOX_WORD * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(mirror, box_d, 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(bb, mirror, sizeof bb);
+  }
+  if (bb[6])  // (the output is dropped where it lies: scratch, or the forest's idle own block)
+    return octl_set_error(ctx, OCTL_E_DOMAIN,
+                          "transform_poses: a moved point %s; the map is unchanged",
+                          f->mode == 0 ? "has a non-finite coordinate or a top-level voxel index outside +-2^30"
+                                       : "lies outside the cube or is not finite");
+  // ---- commit: the moved store, the box just folded, and a forest without a scheme --------------------------------
+  HIP_TRY(ctx, hipMemcpyAsync(f->bbox_dev.p, box_d, 32, hipMemcpyDeviceToDevice, st));
+  if (f->store_borrowed) {
+    f->xyz = f->xyz_own;
+    f->xyz_own = DevBuf{};
+    f->store_borrowed = false;
+  } else {
+    std::swap(f->xyz, f->part_xyz[0]);
+  }
+  f->bbox_stale = f->bbox_pending = false;
+  forest_reset_scheme(f);
+  return OCTL_OK;
 }
 
 int octl_forest_extend_pose(octl_forest* f, int32_t slot, const double* xyz, int64_t n) {

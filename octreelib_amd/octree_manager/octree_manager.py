@@ -236,13 +236,32 @@ class OctreeManager(VoxelBase):
         (transforms (S, 4, 4), iterations, converged, costs, reason).  `fixed` (pose numbers; None: the first selected
         pose) stay where they are.  Per iteration T_p <- se3_exp(xi_p, origin) T_p; ends when max |xi_p| < tolerance,
         at max_iterations, or - not converged, last good transforms - when a free pose has fewer than six used
-        points.  The transforms are returned, not written back into the map."""
+        points.  The transforms are returned; transform_poses writes them back into the map."""
         sel = self._query_slots(pose_numbers)
         if self._plug is not None:
             return self._host_map().adjust(initial, sel, origin, min_points, min_poses, max_variance, fixed,
                                            max_iterations, tolerance, damping)
         return self._forest.adjust(initial, sel, origin, min_points, min_poses, max_variance, fixed, max_iterations,
                                    tolerance, damping, self._adjust_names(pose_numbers))
+
+    def transform_poses(self, transforms, pose_numbers: Optional[List[int]] = None) -> None:
+        """Write poses back into the map: move the stored points of the given poses (None: all) by one rigid transform
+        each (4x4 or 3x4, in the order the poses were inserted - Adjustment.transforms of the same pose_numbers can be
+        passed straight in), in place on the device.  A point p of a selected pose becomes transform_np(T, p), bit for
+        bit; the points of the other poses keep their bits; points that a mask or filter removed stay removed.
+        Afterwards the map is what a fresh OctreeManager would be after inserting every pose again with its surviving
+        points as moved: no subdivision, every cached table dropped - subdivide, fit planes and adjust again - except that
+        Neighbours.index still names rows of the clouds as they were first inserted.  Transactional: DomainError (a
+        moved point is not finite or lies outside the cube) leaves the map exactly as it was.  One kernel over the
+        stored points and one host wait (octl_forest_transform_poses).  ValueError for transforms that are not one
+        valid transform per selected pose; KeyError for an unknown pose; NotImplementedError on the caller's own plug
+        types."""
+        if self._plug is not None:
+            raise NotImplementedError(
+                "transform_poses moves the points of the device-resident map: an OctreeManager on the caller's own plug "
+                "types keeps its points in those types on the host, and there is no host path for them")
+        sel = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+        self._forest.transform_poses(transforms, sel)
 
     def _adjust_names(self, pose_numbers):
         """The selected pose numbers in ascending slot order: the order of the transforms and of every result row."""
