@@ -315,6 +315,44 @@ int octl_forest_nearest(octl_forest* f, const double* xyz, int64_t n, int32_t k,
 int octl_forest_nearest_device(octl_forest* f, const double* xyz_dev, int64_t n, int32_t k, double max_distance,
                                const uint8_t* slot_sel, int32_t n_sel, int32_t* slot_dev, int64_t* index_dev,
                                double* d2_dev, int32_t* count_dev);
+/* What does a ray hit first?  For each of n rays o + t d, t_min <= t <= t_max (origins, directions (n,3) f64, t_min,
+ * t_max (n) f64; directions are taken as given - t is the ray parameter, a distance only for unit vectors): the first
+ * occupied leaf (surface = OCTL_RAY_CUBE) or the first accepted pooled plane (OCTL_RAY_PLANE) of the selected poses
+ * (slot_sel: n_sel = number of poses flags, NULL = every pose).  octreelib_amd/query.py: raycast_np is the same by
+ * brute force over the leaves, bit for bit; all arithmetic in f64, every product, sum and quotient rounded (no fma):
+ *   dead ray   any of o, d, t_min, t_max not finite; t_max < t_min; a component with |d| > 1; every component of d zero
+ *              or with a reciprocal that is not finite.  Answer node -1, t +inf, row -1; never an error;
+ *   interval   of the leaf (corner c, edge e), lo = c, hi = fl(c + e): an axis whose d is zero or whose inv = fl(1 / d)
+ *              is not finite passes iff lo <= o <= hi and bounds nothing; otherwise a = fl(fl(lo - o) inv), b =
+ *              fl(fl(hi - o) inv), near = min(a, b), far = max(a, b).  t_in = max(near_x, near_y, near_z, t_min), t_out
+ *              = min(far_x, far_y, far_z, t_max); the leaf is crossed iff every such axis passes and t_in <= t_out;
+ *   cube       candidates: crossed scheme leaves (never inner nodes) that hold at least min_points points of the
+ *              selection that are alive and in the leaf-ordered arrays; t = t_in;
+ *   plane      candidates: crossed leaves whose row of the pooled table passes octl_forest_point_to_plane's gates
+ *              (count >= min_points and, with max_variance >= 0, not lambda0 > max_variance), with num = (nx fl(mx -
+ *              ox) + ny fl(my - oy)) + nz fl(mz - oz), den = (nx dx + ny dy) + nz dz, t = fl(num / den), den != 0 and
+ *              t_in <= t <= t_out (n the eigenvector of lambda0, m the mean, the table's own bits);
+ *   answer     the candidate smallest in (t, node): node[i] its id, t[i] its t, row[i] its row of the pooled table
+ *              (plane) or -1 (cube).  The order is total, so the answer is a function of the input.
+ * A grid caps a ray that is not dead at t_max - t_min <= 256 voxel edges and |t_min|, |t_max| <= 2^40 voxel edges
+ * (the cap bounds a call's cost; a 1 m grid answers 256 m rays): OCTL_E_INVALID above it.  A single cube has no cap.
+ * OCTL_E_INVALID also: a surface that is neither, min_points < 0, max_variance NaN, a selection of the wrong length.
+ * OCTL_E_STATE: before the first build; a forest whose rows map_leaf_points moved outside their leaves.  The tables
+ * a call reads - the index of the blocks by node of octl_forest_nearest (cube), the pooled planes (plane) - are made
+ * by the call that finds them missing, stale or made for another selection; with them in place a call is one kernel,
+ * plus four uploads, three downloads and one wait.  Read-only otherwise.  No reference counterpart.              */
+#define OCTL_RAY_CUBE 0
+#define OCTL_RAY_PLANE 1
+int octl_forest_raycast(octl_forest* f, const double* origins, const double* directions, const double* t_min,
+                        const double* t_max, int64_t n, const uint8_t* slot_sel, int32_t n_sel, int32_t surface,
+                        int32_t min_points, double max_variance, int32_t* node, double* t, int32_t* row);
+/* The same with pointers from octl_dev_alloc (slot_sel stays a host array): one kernel, nothing is downloaded and
+ * the host does not wait.  The cap cannot be checked without reading the rays: one above it is answered as a dead
+ * ray is.  No reference counterpart.                                                                              */
+int octl_forest_raycast_device(octl_forest* f, const double* origins_dev, const double* directions_dev,
+                               const double* t_min_dev, const double* t_max_dev, int64_t n, const uint8_t* slot_sel,
+                               int32_t n_sel, int32_t surface, int32_t min_points, double max_variance,
+                               int32_t* node_dev, double* t_dev, int32_t* row_dev);
 /* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
  * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
  * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in

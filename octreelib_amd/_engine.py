@@ -694,6 +694,54 @@ class Forest:
             slot = names[slot]
         return Neighbours(slot, index, d2, count)
 
+    def _raycast_args(self, max_range, min_range, surface, min_points, max_variance, origins, directions):
+        from octreelib_amd.query import check_raycast_args, check_raycast_cap, normalize_directions, ray_inputs
+
+        code, min_points, mv = check_raycast_args(surface, min_points, max_variance)
+        o, d, tmin, tmax = ray_inputs(origins, normalize_directions(directions), min_range, max_range)
+        if self.mode == 0:
+            check_raycast_cap(tmin, tmax, float(self._cube[1]))
+        return code, min_points, mv, o, d, tmin, tmax
+
+    def raycast(self, origins, directions, max_range, min_range=0.0, slots=None, surface: str = "cube",
+                min_points=None, max_variance=None):
+        """What every ray hits first between min_range and max_range (octl_forest_raycast: one kernel once the block
+        index - "cube" - or the pooled planes - "plane" - of the selection exist): a query.RayHits as query.raycast_np
+        defines it on the directions normalised by query.normalize_directions."""
+        from octreelib_amd.query import RayHits
+
+        code, min_points, mv, o, d, tmin, tmax = self._raycast_args(max_range, min_range, surface, min_points,
+                                                                   max_variance, origins, directions)
+        self.ensure_built()
+        if code == 1:
+            self.leaf_planes(slots)    # (the table `row` names; this mirror's copy stays the device's)
+        sel, n_sel, _ = self._adjust_selection(slots)
+        n = len(o)
+        node = np.full(n, -1, dtype=np.int32)
+        t = np.full(n, np.inf, dtype=np.float64)
+        row = np.full(n, -1, dtype=np.int32)
+        # (n = 0 still goes to the library: what it refuses whatever the rays is refused for no rays too)
+        self.ctx.check(self.lib.octl_forest_raycast(self.handle, nat.ptr(o), nat.ptr(d), nat.ptr(tmin), nat.ptr(tmax), n,
+                                                    nat.ptr(sel), n_sel, code, min_points, mv, nat.ptr(node),
+                                                    nat.ptr(t), nat.ptr(row)))
+        return RayHits(node, t, row)
+
+    def raycast_device(self, origins_dptr, directions_dptr, t_min_dptr, t_max_dptr, n: int, node_dptr, t_dptr, row_dptr,
+                       slots=None, surface: str = "cube", min_points=None, max_variance=None):
+        """raycast for rays that are in device memory already (pointers from octl_dev_alloc; the directions as the
+        kernel is to see them - nothing is normalised - and t_min, t_max one per ray), the answers left there;
+        enqueued on the context's stream, the host does not wait.  A ray above a grid's cap finds nothing."""
+        from octreelib_amd.query import check_raycast_args
+
+        code, min_points, mv = check_raycast_args(surface, min_points, max_variance)
+        self.ensure_built()
+        if code == 1:
+            self.leaf_planes(slots)
+        sel, n_sel, _ = self._adjust_selection(slots)
+        self.ctx.check(self.lib.octl_forest_raycast_device(self.handle, origins_dptr, directions_dptr, t_min_dptr,
+                                                           t_max_dptr, int(n), nat.ptr(sel), n_sel, code, min_points, mv,
+                                                           node_dptr, t_dptr, row_dptr))
+
     def plane_segments(self, slots=None, min_points: int = 8, max_variance=None, max_angle: float = 0.1,
                        max_offset: float = 0.05):
         """The rows of leaf_planes(slots) merged across leaf faces into connected coplanar segments

@@ -260,17 +260,9 @@ int launch_nearest(octl_ctx* ctx, const double* xyz_dev, int64_t n, int k, doubl
   return OCTL_OK;
 }
 
-// f->nn_tab: [record uint4 per block | first i32 per node | count i32 per node]
-struct NNTab {
-  size_t nb, n_nodes;  // (at least one of each)
-  Carve plan;
-  Carve::Part<uint4> rec = plan.add<uint4>(nb);
-  Carve::Part<int32_t> first = plan.add<int32_t>(n_nodes), cnt = plan.add<int32_t>(n_nodes);
-  constexpr NNTab(int64_t blocks, int64_t nodes)
-      : nb((size_t)std::max<int64_t>(blocks, 1)), n_nodes((size_t)std::max<int64_t>(nodes, 1)) {}
-};
-static_assert(NNTab(100, 10).cnt.off == 2048 && NNTab(100, 10).plan.total == 2304, "NNTab offsets");
+}  // namespace
 
+// (NNTab, the declaration: query_walk.h - raycast.hip reads the same index)
 // the index node -> run of blocks for the selection `sel` (empty: every pose) of the forest as it stands
 int nn_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   octl_ctx* ctx = f->ctx;
@@ -306,6 +298,8 @@ int nn_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   f->nn_stamp = f->content_stamp;
   return OCTL_OK;
 }
+
+namespace {
 
 // what both forms start with: the refusals, the tables, the index
 int nearest_begin(octl_forest* f, int64_t n, int32_t k, double max_distance, const uint8_t* slot_sel, int32_t n_sel,

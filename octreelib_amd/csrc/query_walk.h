@@ -3,6 +3,8 @@
 // One definition, so that the registration kernel's node / row / residual are the bits octl_forest_point_to_plane
 // answers - by construction, not by a copy that has to be kept in step.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 #include "forest.h"
 #include "scheme_walk.h"
@@ -70,3 +72,17 @@ int query_begin(octl_forest* f, const char* what, QueryTables* t);
 // ... and the pooled plane table is the one of the forest as it stands (OCTL_E_STATE with the cause otherwise)
 int query_plane_table(octl_forest* f, const char* what, int32_t min_points, double max_variance, PlaneTable* pt);
 static inline bool query_bad_count(int64_t n) { return n < 0 || n >= ((int64_t)1 << 31); }
+
+// nearest.hip.  f->nn_tab, the index node -> run of selected (leaf, pose) blocks that octl_forest_nearest searches and
+// octl_forest_raycast takes a leaf's occupancy from: [record uint4 per block | first i32 per node | count i32 per node]
+struct NNTab {
+  size_t nb, n_nodes;  // (at least one of each)
+  Carve plan;
+  Carve::Part<uint4> rec = plan.add<uint4>(nb);
+  Carve::Part<int32_t> first = plan.add<int32_t>(n_nodes), cnt = plan.add<int32_t>(n_nodes);
+  constexpr NNTab(int64_t blocks, int64_t nodes)
+      : nb((size_t)std::max<int64_t>(blocks, 1)), n_nodes((size_t)std::max<int64_t>(nodes, 1)) {}
+};
+static_assert(NNTab(100, 10).cnt.off == 2048 && NNTab(100, 10).plan.total == 2304, "NNTab offsets");
+// ... made for the selection `sel` (empty: every pose) of the forest as it stands; stamps f->nn_stamp, keeps f->nn_sel
+int nn_prepare(octl_forest* f, const std::vector<uint8_t>& sel);

@@ -18,7 +18,7 @@ from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, VisualizationConfig
 from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
-from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane
+from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane, RayHits
 from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
@@ -143,6 +143,26 @@ class Grid(GridBase):
             return self._host_map().nearest(points, k, max_distance=max_distance, pose_numbers=sel)
         names = [p for p, _ in sorted(self._slots.items(), key=lambda kv: kv[1])]
         return self._forest.neighbours(points, k, max_distance, sel, names)
+
+    def raycast(self, origins, directions, max_range, *, min_range=0.0, pose_numbers: Optional[List[int]] = None,
+                surface: str = "cube", min_points: Optional[int] = None,
+                max_variance: Optional[float] = None) -> RayHits:
+        """What every ray hits first: for n rays from `origins` (n, 3) along `directions` (n, 3; normalised here, any
+        length; a zero vector hits nothing) between min_range and max_range (scalars or (n,)), the first occupied
+        leaf (surface="cube": at least min_points, default 1, alive points of the given poses - None: all - and t
+        where the ray enters its cube) or the first accepted leaf plane (surface="plane": the pooled plane of
+        leaf_planes(pose_numbers) under point_to_plane's gates, min_points default 8 and max_variance, where the ray
+        meets it inside the leaf's cube).  A RayHits (node, t, row (n,); .hit, .points(origins, directions)): node -1,
+        t +inf, row -1 where nothing is hit or the ray is dead (a value that is not finite, max_range < min_range);
+        ties in t go to the smaller node id.  One kernel once the tables of the selection exist
+        (octreelib_amd/query.py: raycast_np is the definition, bit for bit).  ValueError for shapes that do not fit, an
+        unknown surface, a ray that spans more than 256 voxel edges; RuntimeError after map_leaf_points moved rows
+        outside their leaves; KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().raycast(origins, directions, max_range, min_range=min_range, pose_numbers=sel,
+                                            surface=surface, min_points=min_points, max_variance=max_variance)
+        return self._forest.raycast(origins, directions, max_range, min_range, sel, surface, min_points, max_variance)
 
     def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
         """One least-squares plane per leaf over the given poses (None: all), all their points pooled: a LeafPlanes in

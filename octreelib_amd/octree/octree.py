@@ -108,6 +108,13 @@ class Octree(OctreeBase, Generic[T]):
         self._query_ready()
         return self._forest.neighbours(points, k, max_distance, None, [0] * self._forest.n_slots)
 
+    def raycast(self, origins, directions, max_range, *, min_range=0.0, surface: str = "cube", min_points=None,
+                max_variance=None):
+        """What every ray hits first between min_range and max_range: the first occupied leaf ("cube") or the first
+        accepted leaf plane ("plane") - a RayHits; Grid.raycast describes it.  One cube has no cap on the range."""
+        self._query_ready()
+        return self._forest.raycast(origins, directions, max_range, min_range, None, surface, min_points, max_variance)
+
     def leaf_planes(self):
         """One least-squares plane per non-empty leaf, in ascending node id (a LeafPlanes)."""
         self._query_ready()

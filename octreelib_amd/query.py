@@ -3,8 +3,11 @@ Queries against the map: which leaf of the scheme does a point fall into (locate
 over a set of poses (leaf_planes) and the signed distance of a point to the plane of its own leaf (point_to_plane) -
 the inner loop of scan-to-map registration and of every plane-factor residual.
 
+Further down: the stored points nearest to a point (nearest), the leaves merged into plane segments (plane_segments)
+and what a ray hits first (raycast).
+
 Grid / OctreeManager / Octree answer them on the device (octl_forest_locate, octl_forest_pooled_leaf_stats,
-octl_forest_point_to_plane).  The functions of this module are the same on the host in NumPy: they are the
+octl_forest_point_to_plane, octl_forest_nearest, octl_forest_plane_segments, octl_forest_raycast).  The functions of this module are the same on the host in NumPy: they are the
 specification, the higher-precision reference of the tests, and what the classes built on the caller's own plug types
 use, so that the whole feature also runs, slowly, without a GPU.
 """
@@ -20,10 +23,14 @@ from octreelib_amd.leaf_stats import LeafStatistics, cov6_to_full, leaf_statisti
 
 __all__ = ["LeafPlanes", "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np",
            "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K", "PlaneSegments",
-           "SegmentTable", "plane_segments_np", "segment_probes_np"]
+           "SegmentTable", "plane_segments_np", "segment_probes_np", "RayHits", "raycast_np", "normalize_directions",
+           "RAY_CAP_EDGES"]
 
 VOX_ABS_LIMIT = 1 << 30   # absolute voxel indices travel as int32
 NN_MAX_K = 8              # OCTL_NN_MAX_K: the largest k of nearest()
+RAY_CAP_EDGES = 256.0     # a grid's raycast: t_max - t_min in voxel edges at most ...
+RAY_T_LIMIT = 2.0 ** 40   # ... and |t_min|, |t_max| in voxel edges at most
+RAY_SURFACES = {"cube": 0, "plane": 1}   # OCTL_RAY_CUBE, OCTL_RAY_PLANE
 
 
 @dataclass
@@ -225,6 +232,193 @@ def nearest_np(points, clouds, k: int = 1, *, max_distance: float, dtype=np.floa
                 dist2[a + i, :c] = d2[i, cand]
                 count[a + i] = c
     return Neighbours(pose, index, dist2, count)
+
+
+@dataclass
+class RayHits:
+    """Answer of raycast for n rays: what every ray o + t d hits first between its t_min and t_max."""
+
+    node: np.ndarray   # (n,) int32 leaf hit (LeafView.node, locate), -1: nothing
+    t: np.ndarray      # (n,) float64 ray parameter of the hit - a range, the directions being unit vectors; +inf: nothing
+    row: np.ndarray    # (n,) int32 row of leaf_planes of the same poses for surface="plane", else -1
+
+    @property
+    def hit(self) -> np.ndarray:
+        """(n,) bool: the ray hit something."""
+        return self.node >= 0
+
+    def points(self, origins, directions) -> np.ndarray:
+        """(n, 3) o + t d for the origins and directions the rays were cast with (normalised as raycast does); NaN
+        rows where nothing was hit."""
+        o, d = _as_queries(origins), normalize_directions(directions)
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = o + self.t[:, None] * d
+        p[~self.hit] = np.nan
+        return p
+
+
+def normalize_directions(directions) -> np.ndarray:
+    """(n, 3) float64 d / sqrt((dx dx + dy dy) + dz dz), every operation rounded, in that order: what every raycast
+    method of the package applies to its directions before the definition or the device sees them.  A vector whose
+    length rounds to zero stays as it is (the zero vector stays zero: a dead ray); one whose squared length overflows
+    becomes zero."""
+    d = _as_queries(directions)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+        r = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        return np.ascontiguousarray(np.where((r > 0.0)[:, None], d / r[:, None], d))
+
+
+def check_raycast_args(surface, min_points, max_variance):
+    """(surface code, min_points, max_variance or -1.0); ValueError for what raycast refuses whatever the map.
+    min_points None: 1 for "cube", 8 for "plane" (point_to_plane's default)."""
+    if surface not in RAY_SURFACES:
+        raise ValueError(f"raycast: surface = {surface!r} is neither 'cube' nor 'plane'")
+    if min_points is None:
+        min_points = 1 if surface == "cube" else 8
+    if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 0:
+        raise ValueError(f"raycast: min_points = {min_points!r} is not an integer >= 0")
+    mv = -1.0
+    if max_variance is not None:
+        mv = float(max_variance)
+        if np.isnan(mv):
+            raise ValueError("raycast: max_variance is NaN")
+        if mv < 0:
+            mv = -1.0           # (as point_to_plane: a negative bound is no bound)
+    return RAY_SURFACES[surface], int(min_points), mv
+
+
+def ray_inputs(origins, directions, t_min, t_max):
+    """(origins (n, 3), directions (n, 3), t_min (n,), t_max (n,)) as contiguous float64; t_min and t_max are scalars
+    or (n,).  ValueError for shapes that do not fit."""
+    o, d = _as_queries(origins), _as_queries(directions)
+    if len(o) != len(d):
+        raise ValueError(f"raycast: {len(o)} origins for {len(d)} directions")
+    n = len(o)
+    out = [o, d]
+    for name, v in (("t_min / min_range", t_min), ("t_max / max_range", t_max)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n, float(a))
+        elif a.shape != (n,):
+            raise ValueError(f"raycast: {name} must be a scalar or of shape ({n},), got {a.shape}")
+        out.append(np.ascontiguousarray(a))
+    return tuple(out)
+
+
+def check_raycast_cap(t_min, t_max, edge: float):
+    """ValueError when a ray of a grid with voxel edge `edge` that is not dead spans more than RAY_CAP_EDGES voxel
+    edges or has |t| above RAY_T_LIMIT of them: the cap bounds a call's cost (a 1 m grid answers 256 m rays)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        live = np.isfinite(t_min) & np.isfinite(t_max) & (t_min <= t_max)
+        span = ~(t_max - t_min <= RAY_CAP_EDGES * edge) & live
+        far = ~((np.abs(t_min) <= RAY_T_LIMIT * edge) & (np.abs(t_max) <= RAY_T_LIMIT * edge)) & live
+    if span.any():
+        i = int(np.nonzero(span)[0][0])
+        raise ValueError(f"raycast: ray {i} spans t_max - t_min = {t_max[i] - t_min[i]}, more than {RAY_CAP_EDGES:g} "
+                         f"voxel edges of {edge}")
+    if far.any():
+        i = int(np.nonzero(far)[0][0])
+        raise ValueError(f"raycast: ray {i} has |t| above 2^40 voxel edges of {edge}")
+
+
+def raycast_np(origins, directions, t_max, node, corner, edge, *, t_min=0.0, count=None,
+               planes: Optional[LeafPlanes] = None, surface: str = "cube", min_points: Optional[int] = None,
+               max_variance: Optional[float] = None, chunk: int = 128) -> RayHits:
+    """What every ray o + t d, t_min <= t <= t_max, hits first, by brute force over the leaves: the definition of
+    raycast.  The directions are taken as given (normalize_directions is what the methods apply first).  Leaves: node
+    (m,) ids, corner (m, 3), edge (m,); surface "cube" takes count (m,) = the alive points of the selected poses in
+    every leaf, "plane" the pooled table `planes` (leaf_planes of the selected poses - data, not recomputed; a leaf
+    without a row has no plane).  All arithmetic in float64, every product, sum and quotient rounded, in this order:
+
+    dead ray   any of o, d, t_min, t_max not finite; t_max < t_min; a component with |d| > 1; every component of d zero
+               or with a reciprocal that is not finite: node -1, t +inf, row -1;
+    interval   lo = corner, hi = corner + edge.  An axis whose d is zero or whose inv = 1 / d is not finite passes iff
+               lo <= o <= hi and bounds nothing; otherwise a = (lo - o) * inv, b = (hi - o) * inv, near = min(a, b),
+               far = max(a, b).  t_in = max(near_x, near_y, near_z, t_min), t_out = min(far_x, far_y, far_z, t_max);
+               the leaf is crossed iff every such axis passes and t_in <= t_out (both ends inclusive);
+    cube       candidates: crossed leaves with count >= min_points (default 1); t = t_in;
+    plane      candidates: crossed leaves whose row passes point_to_plane's gates (count >= min_points, default 8; not
+               lambda0 > max_variance when one is given), num = (nx (mx - ox) + ny (my - oy)) + nz (mz - oz),
+               den = (nx dx + ny dy) + nz dz, t = num / den, den != 0 and t_in <= t <= t_out;
+    answer     the candidate smallest in (t, node) - a total order, so the answer is a function of the input."""
+    code, min_points, mv = check_raycast_args(surface, min_points, max_variance)
+    o, d, tmin, tmax = ray_inputs(origins, directions, t_min, t_max)
+    n = len(o)
+    out = RayHits(np.full(n, -1, dtype=np.int32), np.full(n, np.inf), np.full(n, -1, dtype=np.int32))
+    node = np.asarray(node, dtype=np.int64).reshape(-1)
+    corner = np.asarray(corner, dtype=np.float64).reshape(-1, 3)
+    edge = np.asarray(edge, dtype=np.float64).reshape(-1)
+    if not len(node) == len(corner) == len(edge):
+        raise ValueError("raycast_np: node, corner and edge describe different numbers of leaves")
+    # the leaves that can be candidates at all, in ascending node id (the first of equal t is then the answer)
+    if code == 0:
+        if count is None:
+            raise ValueError("raycast_np: surface='cube' needs the leaves' counts")
+        keep = np.asarray(count).reshape(-1) >= min_points
+        rows = np.full(len(node), -1, dtype=np.int64)
+    else:
+        if planes is None:
+            raise ValueError("raycast_np: surface='plane' needs the pooled planes")
+        ids = np.asarray(planes.node, dtype=np.int64)
+        rows = np.full(len(node), -1, dtype=np.int64)
+        keep = np.zeros(len(node), dtype=bool)
+        if len(ids):
+            pos = np.minimum(np.searchsorted(ids, node), len(ids) - 1)
+            keep = ids[pos] == node
+            keep &= np.asarray(planes.count)[pos] >= min_points
+            if mv >= 0:
+                keep &= ~(np.asarray(planes.eigenvalues, dtype=np.float64)[pos, 0] > mv)
+            rows = np.where(keep, pos, -1)
+    sel = np.nonzero(keep)[0]
+    sel = sel[np.argsort(node[sel], kind="stable")]
+    node, lo, rows = node[sel], corner[sel], rows[sel]
+    hi = lo + edge[sel][:, None]
+    m = len(node)
+    if n == 0 or m == 0:
+        return out
+    if code == 1:
+        nrm = np.asarray(planes.normal, dtype=np.float64)[rows]
+        mean = np.asarray(planes.mean, dtype=np.float64)[rows]
+    with np.errstate(all="ignore"):
+        inv = 1.0 / d
+        zero = (d == 0.0) | ~np.isfinite(inv)
+        dead = ~(np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1) & np.isfinite(tmin) & np.isfinite(tmax))
+        dead |= ~(tmin <= tmax) | zero.all(axis=1) | ~(np.abs(d) <= 1.0).all(axis=1)
+        for a0 in range(0, n, chunk):
+            live = np.nonzero(~dead[a0: a0 + chunk])[0] + a0
+            if len(live) == 0:
+                continue
+            oc, dc, ic, zc = o[live], d[live], inv[live], zero[live]
+            t_in = np.repeat(tmin[live][:, None], m, axis=1)
+            t_out = np.repeat(tmax[live][:, None], m, axis=1)
+            ok = np.ones((len(live), m), dtype=bool)
+            for a in range(3):
+                oa, ia, za = oc[:, a, None], np.where(zc[:, a], 1.0, ic[:, a])[:, None], zc[:, a, None]
+                ta = (lo[None, :, a] - oa) * ia
+                tb = (hi[None, :, a] - oa) * ia
+                t_in = np.maximum(t_in, np.where(za, -np.inf, np.minimum(ta, tb)))
+                t_out = np.minimum(t_out, np.where(za, np.inf, np.maximum(ta, tb)))
+                ok &= ~za | ((lo[None, :, a] <= oa) & (oa <= hi[None, :, a]))
+            ok &= t_in <= t_out
+            if code == 0:
+                t = t_in
+            else:
+                num = (nrm[None, :, 0] * (mean[None, :, 0] - oc[:, 0, None])
+                       + nrm[None, :, 1] * (mean[None, :, 1] - oc[:, 1, None])) \
+                    + nrm[None, :, 2] * (mean[None, :, 2] - oc[:, 2, None])
+                den = (nrm[None, :, 0] * dc[:, 0, None] + nrm[None, :, 1] * dc[:, 1, None]) \
+                    + nrm[None, :, 2] * dc[:, 2, None]
+                t = num / den
+                ok &= (den != 0.0) & (t_in <= t) & (t <= t_out)
+            tt = np.where(ok, t, np.inf)
+            best = tt.min(axis=1)
+            first = np.argmax(ok & (tt == best[:, None]), axis=1)     # (ascending node id: the smallest of a tie)
+            got = ok.any(axis=1)
+            h = live[got]
+            out.node[h] = node[first[got]]
+            out.t[h] = best[got]
+            out.row[h] = rows[first[got]]
+    return out
 
 
 @dataclass
@@ -491,6 +685,29 @@ class HostMap:
         if self.mode == 0 and r > 2.0 * self.edge:
             raise ValueError(f"nearest: max_distance {r} exceeds twice the voxel edge {self.edge}")
         return nearest_np(points, self.clouds(pose_numbers), k, max_distance=r)
+
+    def raycast(self, origins, directions, max_range, *, min_range=0.0, pose_numbers=None, surface="cube",
+                min_points=None, max_variance=None) -> RayHits:
+        """raycast_np over the leaves of the node table: the directions normalised, the grid's cap checked, counts
+        and planes pooled over the chosen poses."""
+        check_raycast_args(surface, min_points, max_variance)
+        o, d, tmin, tmax = ray_inputs(origins, normalize_directions(directions), min_range, max_range)
+        if self.mode == 0:
+            check_raycast_cap(tmin, tmax, self.edge)
+        leaf = np.nonzero(np.asarray(self.nodes["first_child"]) < 0)[0]
+        corner, edge = self.nodes["corner"][leaf], self.nodes["edge"][leaf]
+        count = planes = None
+        if surface == "cube":
+            chosen = list(self._leaves) if pose_numbers is None else [p for p in self._leaves if p in set(pose_numbers)]
+            per_node = np.zeros(len(self.nodes["edge"]), dtype=np.int64)
+            for p in chosen:
+                for v in self._leaves[p]:
+                    per_node[self._id(v)] += len(np.asarray(v.get_points()).reshape(-1, 3))
+            count = per_node[leaf]
+        else:
+            planes = self.leaf_planes(pose_numbers)
+        return raycast_np(o, d, tmax, leaf, corner, edge, t_min=tmin, count=count, planes=planes, surface=surface,
+                          min_points=min_points, max_variance=max_variance)
 
     def plane_segments(self, pose_numbers=None, min_points=8, max_variance=None, max_angle=0.1,
                        max_offset=0.05) -> PlaneSegments:
