@@ -24,6 +24,12 @@ the pooled plane table stays valid, which the model books (a point-count filter 
 invalidates it).
 K of a count-driven re-subdivide is drawn below the smallest count the scheme poses have in any internal node of the
 current scheme, which makes it equal-or-finer by construction.
+The second generation (SEEDS2, _Generator2) adds the map queries - nearest, raycast, plane_segments,
+registration_system, adjustment_system - and transform_poses with its refused form; SEEDS keep the logs they had.
+Every parameter is still in the record: rigid motions as {"xi", "origin"} (motion()), queries, rays and scans by seed.
+transform_poses rebuilds the model as a fresh one with every pose's surviving rows inserted again in store order, so
+the model carries, per row, its number in the cloud as first inserted (Model.identity(): what Neighbours.index names);
+a motion that takes a row out of the cube or the voxel domain is Rejected - or, for the refused form, required.
 Not drawn at all: map functions that reorder a leaf's own rows (the library keeps insertion order for a selection
 of a leaf's rows, the reference the returned order - visible to a later RANSAC), a displacing map anywhere but as
 the last mutating operation.
@@ -46,12 +52,22 @@ MUTATING = ("insert", "extend", "subdivide_count", "subdivide_planar_count", "su
             "filter_count", "filter_opaque", "filter_subset", "map_select", "map_transform", "apply_mask", "ransac")
 READ_ONLY = ("leaf_statistics", "locate", "leaf_planes", "point_to_plane", "node_cubes", "get_leaf_points",
              "counters", "split_stats")
+# the second generation of the generator (SEEDS2) draws these too; the first one never does, so its logs stay as they are
+NEW_MUTATING = ("transform_poses", "transform_poses_refused")
+NEW_READ_ONLY = ("nearest", "raycast", "plane_segments", "registration_system", "adjustment_system")
+ALL_MUTATING = MUTATING + NEW_MUTATING
+ALL_READ_ONLY = READ_ONLY + NEW_READ_ONLY
 SUBDIVIDES = ("subdivide_count", "subdivide_planar_count", "subdivide_planar", "subdivide_callable")
 FILTERS = ("filter_count", "filter_opaque", "filter_subset")
 TRANSITIONS = ("ransac>leaf_planes", "ransac>subdivide", "ransac>insert", "filter>insert", "filter>point_to_plane",
                "map_transform>subdivide", "map_select>ransac", "leaf_planes(S)>insert>point_to_plane(S)",
                "planar>count>split_stats", "extend>leaf_statistics", "point_to_plane>ransac>point_to_plane",
                "two_ransac")
+SEEDS2 = list(range(100, 124))      # container, first subdivision and motif by (seed - 100) as SEEDS has them by seed
+TRANSITIONS2 = ("transform_poses>subdivide>nearest", "transform_poses>subdivide>ransac>apply_mask", "apply_mask>raycast",
+                "leaf_planes(S)>raycast_plane(S')>point_to_plane(S)", "nearest(S)>raycast_cube(S')>nearest(S)",
+                "plane_segments>filter>plane_segments", "adjustment_system>transform_poses>subdivide>adjustment_system",
+                "transform_poses_refused>point_to_plane", "map_transform(shift_z)>nearest")
 # container and motif (index into TRANSITIONS) by seed % 12; the second entry is for seeds >= 12
 _CONTAINER = {0: "grid", 1: "grid", 2: "grid", 3: "manager", 4: ("octree", "octree"), 5: ("octree", "grid"), 6: "grid",
               7: "manager", 8: ("grid", "manager"), 9: ("manager", "octree"), 10: "grid", 11: "grid"}
@@ -172,6 +188,30 @@ def leaf_digests(rows, sizes):
     return [(int(n), int(a), int(b)) for n, a, b in zip(sizes.tolist(), s.tolist(), x.tolist())]
 
 
+def row_hashes(rows):
+    """The 64-bit hash of every row's bits that leaf_digests sums (-0.0 folded into +0.0)."""
+    u = (np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 3) + 0.0).view(np.uint64)
+    with np.errstate(over="ignore"):
+        h = _mix(u[:, 0] + np.uint64(0x9E3779B97F4A7C15))
+        h = _mix(h ^ u[:, 1])
+        return _mix(h ^ u[:, 2])
+
+
+def motion(m):
+    """The 4x4 rigid transform of a record {"xi": (w, v), "origin": c}: Rot(w)(p - c) + c + v."""
+    from octreelib_amd.registration import se3_exp
+
+    return se3_exp(m["xi"], m["origin"])
+
+
+def inverse_motion(m):
+    T = motion(m)
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return out
+
+
 # ---- the model ---------------------------------------------------------------------------------------------------------
 class Model:
     """The oracle behind one container: OGrid / OManager / OTree, with the bookkeeping the library keeps on its own
@@ -197,6 +237,10 @@ class Model:
         self.n_ransac = 0
         self.closest = np.inf        # NotPlanar margin over every node a rule evaluated, in e^2
         self.flags = {"depth2": False, "emptied": False, "late100": False}
+        # Neighbours.index: every tree carries `orig`, the row number in the pose's cloud as first inserted of every
+        # row of tree.points (-1: a row a map function made); n_inserted counts the rows a pose was ever given
+        self.n_inserted = {}
+        self.renumbered = False      # a map function replaced the contents: the library numbers the store anew
 
     @classmethod
     def replay(cls, container, log):
@@ -311,7 +355,9 @@ class Model:
     # -- operations -------------------------------------------------------------------------------------------------------
     def apply(self, op):
         kind = op["op"]
-        if kind in MUTATING:
+        if kind == "transform_poses_refused":      # (raises DomainError in the library: nothing changes, nothing is invalidated)
+            self._transform(op)
+        elif kind in ALL_MUTATING:
             self.untouched = False
             getattr(self, "_" + kind.split("_")[0])(op)
             if not self.untouched:
@@ -321,9 +367,10 @@ class Model:
                 self.stats_fresh = False
             if self.max_depth() >= 2:
                 self.flags["depth2"] = True
-        elif kind in ("leaf_planes", "point_to_plane"):
-            self.pooled = True
-            self.pooled_key = None if op["poses"] is None else tuple(sorted(op["poses"]))
+        elif kind in ("leaf_planes", "point_to_plane", "plane_segments", "registration_system") \
+                or (kind == "raycast" and op["surface"] == "plane"):
+            self.pooled = True      # (each of them makes the pooled table of its selection when the device's is not that)
+            self.pooled_key = None if op.get("poses") is None else tuple(sorted(op["poses"]))
 
     def _insert(self, op):
         p, pts = op["pose"], model_cloud(op["cloud"])
@@ -333,9 +380,19 @@ class Model:
         else:
             self.o.insert_points(p, pts)
         self.poses.append(p)
+        self._set_orig(p, np.arange(len(pts), dtype=np.int64))
+        self.n_inserted[p] = len(pts)
         self._distinct([p])
         if late >= 100:
             self.flags["late100"] = True
+
+    def _set_orig(self, p, orig):
+        """`orig` of the trees of a pose whose rows were just inserted: orig[i] belongs to row i of what was inserted."""
+        if self.kind == "grid":
+            for key in self.o.pose_voxels[p]:
+                self.o.managers[key].octrees[p].orig = orig[self.o.local_to_pose[(key, p)]]
+        else:
+            self.trees_of(p)[0].orig = orig
 
     def _extend(self, op):
         p, pts = op["pose"], model_cloud(op["cloud"])
@@ -344,6 +401,9 @@ class Model:
             self.o.insert_points(pts)
         else:
             self.o.insert_points(p, pts)
+        tree = self.trees_of(p)[0]      # (a manager or an octree: one tree per pose)
+        tree.orig = np.concatenate([tree.orig, self.n_inserted[p] + np.arange(len(pts), dtype=np.int64)])
+        self.n_inserted[p] += len(pts)
         self._distinct([p])
         if late >= 100:
             self.flags["late100"] = True
@@ -388,10 +448,29 @@ class Model:
 
     def _map(self, op):
         fn = build_map(op["fn"], cloud_edge(self.c))
+        before = {id(t): (t, {id(v): v.idx.copy() for v in t.cached.values()}) for p in self.poses for t in self.trees_of(p)}
         if self.kind == "octree":
             self.o.map_leaf_points(fn)
         else:
             self.o.map_leaf_points(fn, op["poses"])
+        # the rows a leaf keeps are matched with its own rows by value, as the library does: a selection keeps the
+        # identity of its rows, anything else replaces the contents and the store is numbered anew
+        for t, old in before.values():
+            orig = np.full(len(t.points), -1, dtype=np.int64)
+            orig[: len(t.orig)] = t.orig
+            for v in t.cached.values():
+                if len(v.idx) and v.idx[0] >= len(t.orig):
+                    was = old[id(v)]
+                    where = {}
+                    for i in was[::-1].tolist():
+                        where.setdefault((t.points[i] + 0.0).tobytes(), []).append(i)
+                    for i in v.idx.tolist():
+                        hit = where.get((t.points[i] + 0.0).tobytes())
+                        if hit:
+                            orig[i] = t.orig[hit.pop()]
+                        else:
+                            self.renumbered = True
+            t.orig = orig
         if op["fn"] == "shift_z":
             self.displaced = True
             return
@@ -401,6 +480,66 @@ class Model:
                     if len(rows) and not np.all((rows - c) // e == 0):
                         raise Rejected("a row left its leaf's cube")
                 self._distinct([p])
+
+    def pose_rows_orig(self, p):
+        """(rows, orig) of the surviving rows of a pose in store order: ascending row number of the inserted cloud."""
+        rows, orig = [np.empty((0, 3))], [np.empty(0, dtype=np.int64)]
+        for t in self.trees_of(p):
+            idx = np.concatenate([v.idx for v in t.leaves(True)] + [np.empty(0, dtype=np.int64)])
+            rows.append(t.points[idx])
+            orig.append(t.orig[idx])
+        rows, orig = np.vstack(rows), np.concatenate(orig)
+        order = np.argsort(orig, kind="stable")
+        return np.ascontiguousarray(rows[order]), orig[order]
+
+    def identity(self):
+        """{pose: (orig, hash)} of the surviving rows in store order - what Neighbours.index must name for the row
+        with that hash (row_hashes; rows are distinct within a pose) - or None once the store was numbered anew."""
+        if self.renumbered:
+            return None
+        out = {}
+        for p in self.poses:
+            rows, orig = self.pose_rows_orig(p)
+            out[p] = (orig, row_hashes(rows))
+        return out
+
+    def outside(self, rows):
+        """The rows the library refuses: not finite, outside the cube (a manager) or the voxel key window (a grid)."""
+        if not np.all(np.isfinite(rows)):
+            return True
+        if self.kind == "grid":
+            return bool(len(rows)) and float(np.abs(rows / float(self.c["edge"])).max()) >= 2.0 ** 30
+        d = rows - np.array(self.c["corner"], dtype=np.float64)
+        return not (np.all(d >= 0.0) and np.all(d < float(self.c["edge"])))
+
+    def _transform(self, op):
+        """transform_poses: a fresh model of the same container with every pose inserted again, in slot order: its
+        surviving rows in store order, those of the selected poses through transform_np."""
+        from octreelib_amd.registration import transform_np
+
+        chosen = [p for p in self.poses if op["poses"] is None or p in op["poses"]]      # (ascending slot order)
+        T = {p: motion(m) for p, m in zip(chosen, op["motions"])}
+        assert len(T) == len(op["motions"]) and not self.renumbered and not self.displaced
+        moved = {}
+        for p in self.poses:
+            rows, orig = self.pose_rows_orig(p)
+            moved[p] = (transform_np(T[p], rows) if p in T else rows, orig)
+        refused = any(self.outside(moved[p][0]) for p in chosen)
+        if op["op"] == "transform_poses_refused":
+            if not refused:
+                raise Rejected("the motion stays inside the domain")
+            return
+        if refused:
+            raise Rejected("a moved row leaves the domain")
+        fresh = Model(self.c)
+        for p in self.poses:
+            rows, orig = moved[p]
+            fresh.o.insert_points(p, rows)
+            fresh.poses.append(p)
+            fresh._set_orig(p, orig)
+            fresh._distinct([p])
+        self.o = fresh.o
+        self.stats, self.stats_fresh = "none", False
 
     def _apply(self, op):
         p = op["pose"]
@@ -438,9 +577,10 @@ class Model:
 
 # ---- the generator ---------------------------------------------------------------------------------------------------
 class Sequence:
-    def __init__(self, seed, container, log, obs, meta, draws, rejected, flags, closest):
+    def __init__(self, seed, container, log, obs, meta, draws, rejected, flags, closest, ident=None):
         self.seed, self.container, self.log, self.obs, self.meta = seed, container, log, obs, meta
         self.draws, self.rejected, self.flags, self.closest = draws, rejected, flags, closest
+        self.ident = ident      # per step Model.identity() (the second generation only)
 
     def printed(self, upto=None):
         ops = self.log if upto is None else self.log[: upto + 1]
@@ -458,9 +598,13 @@ def _container(seed, rng):
 
 
 class _Generator:
-    def __init__(self, seed):
+    read_kinds = READ_ONLY
+
+    def __init__(self, seed, index=None):
         self.seed = seed
         self.rng = np.random.default_rng([seed, 0x0B5E9])
+        seed = self.index = seed if index is None else index      # (what the seed's number fixes goes by this)
+        self.ident = None
         self.container = _container(seed, self.rng)
         self.kind = self.container["kind"]
         self.model = Model(self.container)
@@ -612,8 +756,10 @@ class _Generator:
                 self.model.flags, self.model.closest = flags, min(closest, self.model.closest)
                 continue
             self.log.append(op)
-            mutating = op["op"] in MUTATING
+            mutating = op["op"] in ALL_MUTATING
             self.obs.append(self.model.observe() if mutating or not self.obs else self.obs[-1])
+            if self.ident is not None:
+                self.ident.append(self.model.identity() if mutating or not self.ident else self.ident[-1])
             st = self.model.stats
             self.meta.append({"mutating": mutating, "pooled": self.model.pooled,
                               "stats": st if isinstance(st, str) or self.model.stats_fresh else "stale"})
@@ -622,7 +768,7 @@ class _Generator:
 
     def reads(self, lo, hi, avoid=()):
         for _ in range(int(self.rng.integers(lo, hi + 1))):
-            kinds = [k for k in READ_ONLY if k not in avoid]
+            kinds = [k for k in self.read_kinds if k not in avoid]
             self.step(str(self.rng.choice(kinds)))
 
     def run(self):
@@ -698,9 +844,234 @@ class _Generator:
         self.in_motif = False
 
 
+class _Generator2(_Generator):
+    """The second generation: the map queries (nearest, raycast, plane_segments, registration_system,
+    adjustment_system) among the read-only kinds, transform_poses and its refused form among the mutating ones.  A
+    transform_poses leaves no scheme, so a subdivide is always the next mutating operation."""
+
+    read_kinds = ALL_READ_ONLY
+
+    def __init__(self, seed):
+        super().__init__(seed, seed - SEEDS2[0])
+        self.cloud_seed = 1000 * seed
+        self.ident = []
+
+    def _centre(self):
+        return [float(x) for x in (UTM if self.container["utm"] else np.zeros(3))]
+
+    def _motion(self, angle, shift):
+        """A drawn rigid motion about the scene's centre: a rotation of up to `angle` about a drawn axis, a translation
+        of up to `shift` per axis (a scalar or one bound per axis and sign: (3, 2))."""
+        rng = self.rng
+        axis = rng.normal(size=3)
+        w = axis / np.linalg.norm(axis) * float(rng.uniform(0.2, 1.0)) * angle
+        b = np.broadcast_to(np.asarray(shift, dtype=np.float64).reshape(-1, 1), (3, 2)) if np.ndim(shift) < 2 else shift
+        u = rng.uniform(-1.0, 1.0, 3)
+        v = np.where(u < 0, u * b[:, 0], u * b[:, 1])
+        return {"xi": [float(x) for x in np.concatenate([w, v])], "origin": self._centre()}
+
+    def _pose_motions(self, chosen):
+        """One small motion per chosen pose.  A manager's clouds fill its cube, so there the motion is scaled by the
+        room the pose's rows leave to the walls."""
+        e, out = float(self.cloud_edge), []
+        for p in chosen:
+            if self.kind == "grid":
+                out.append(self._motion(0.05, 0.25 * e))
+                continue
+            rows = self.model.pose_rows(p)
+            lo = np.array(self.container["corner"], dtype=np.float64)
+            hi = lo + float(self.container["edge"])
+            if len(rows) == 0:
+                out.append(self._motion(0.05, 0.25 * e))
+                continue
+            room = np.stack([(rows - lo).min(axis=0), (hi - rows).min(axis=0)], axis=1)      # (3, 2): towards -, towards +
+            reach = float(np.abs(rows).max()) * np.sqrt(3.0)
+            angle = min(0.05, 0.3 * float(room.min()) / reach)
+            out.append(self._motion(angle, np.minimum(0.25 * e, 0.5 * np.maximum(room - angle * reach, 0.0))))
+        return out
+
+    def params(self, kind):
+        m, rng = self.model, self.rng
+        e = float(self.cloud_edge)
+        if kind not in NEW_MUTATING + NEW_READ_ONLY:
+            if m.displaced and kind in ("leaf_planes", "locate", "node_cubes", "get_leaf_points", "counters", "split_stats"):
+                return None      # (after rows were displaced: the queries that must refuse, and the two gen-1 draws)
+            return super().params(kind)
+        has_points = bool(m.poses) and any(m.counters(p)[2] > 0 for p in m.poses)
+        if not has_points:
+            return None
+        gates = lambda: {"min_points": int(rng.choice([1, 8, 16])),
+                         "max_variance": [None, 1e-3 * e ** 2][int(rng.integers(0, 2))]}
+        if kind in NEW_MUTATING:
+            if self.kind == "octree" or m.displaced or m.renumbered:
+                return None
+            poses = self._subset()
+            chosen = [p for p in m.poses if poses is None or p in poses]
+            if kind == "transform_poses":
+                return {"op": kind, "poses": poses, "motions": self._pose_motions(chosen)}
+            motions = [self._motion(0.01, 0.0) for _ in chosen]
+            far = 2.0 ** 31 * float(self.container["edge"]) if self.kind == "grid" else 5.0 * float(self.container["edge"])
+            motions[int(rng.integers(0, len(chosen)))]["xi"][3 + int(rng.integers(0, 3))] = float(far)
+            return {"op": kind, "poses": poses, "motions": motions}
+        if m.displaced and kind not in ("nearest", "raycast"):
+            return None
+        if kind == "nearest":
+            return {"op": kind, "seed": int(rng.integers(1 << 30)), "n": 300, "k": int(rng.choice([1, 3, 8])),
+                    "r": float(rng.choice([0.05, 0.5, 2.0])) * e, "poses": self._subset()}
+        if kind == "raycast":
+            return {"op": kind, "seed": int(rng.integers(1 << 30)), "n": 300, "surface": str(rng.choice(["cube", "plane"])),
+                    "poses": self._subset(), **gates(), "max_range": float(rng.uniform(0.5, 8.0)) * e,
+                    "min_range": [0.0, 0.1 * e][int(rng.integers(0, 2))]}
+        if kind == "plane_segments":
+            return {"op": kind, "poses": self._subset(), "min_points": int(rng.choice([8, 16])),
+                    "max_variance": [None, 1e-3 * e ** 2][int(rng.integers(0, 2))],
+                    "max_angle": float(rng.choice([0.1, 0.3])), "max_offset": float(rng.choice([0.05, 0.02])) * e}
+        if kind == "registration_system":
+            with_points = [p for p in m.poses if m.counters(p)[2] > 0]
+            return {"op": kind, "pose": int(rng.choice(with_points)), "seed": int(rng.integers(1 << 30)),
+                    "n": int(rng.integers(300, 1001)), "motion": self._motion(0.02, 0.02 * e),
+                    "inverse": bool(rng.integers(0, 2)), "poses": self._subset(), **gates(),
+                    "max_distance": [None, 0.2 * e][int(rng.integers(0, 2))],
+                    "huber_delta": [None, 0.02 * e][int(rng.integers(0, 2))]}
+        # adjustment_system
+        if self.kind == "octree" or len(m.poses) < 2:
+            return None
+        poses = self._subset()
+        if poses is not None and len(poses) < 2:
+            poses = None
+        S = len(m.poses) if poses is None else len(poses)
+        return {"op": kind, "poses": poses, "min_points": 8, "min_poses": 2,
+                "max_variance": [None, 1e-3 * e ** 2][int(rng.integers(0, 2))],
+                "motions": None if rng.random() < 0.5 else [self._motion(0.003, 0.004 * e) for _ in range(S)]}
+
+    def must(self, kind, fix=None):
+        ok = self.step(kind, fix)
+        assert ok, f"seed {self.seed}: step {kind} cannot be drawn\n{Sequence.printed(self)}"
+
+    def subdivide_again(self):
+        """The subdivide that follows a transform_poses."""
+        for kind in self.rng.permutation(["subdivide_count", "subdivide_planar_count", "subdivide_callable",
+                                          "subdivide_count"]).tolist():
+            if self.step(kind):
+                return
+        raise AssertionError(f"seed {self.seed}: no subdivide can be drawn\n{Sequence.printed(self)}")
+
+    def transform_then_subdivide(self, fix=None, reads=(0, 1)):
+        if not self.step("transform_poses", fix):
+            return False
+        self.reads(*reads)      # (as on a map that was never subdivided)
+        self.subdivide_again()
+        return True
+
+    def mutate(self, weights):
+        kinds = list(weights)
+        w = np.array([weights[k] for k in kinds], dtype=float)
+        for _ in range(6):
+            kind = str(self.rng.choice(kinds, p=w / w.sum()))
+            if self.transform_then_subdivide() if kind == "transform_poses" else self.step(kind):
+                return True
+        return False
+
+    def run(self):
+        rng, j = self.rng, self.index % 12
+        second = self.index >= 12
+        for _ in range(1 if self.kind == "octree" else int(rng.integers(2, 4))):
+            self.step("insert")
+        self.reads(0, 1)
+        self.step(self.first_subdivide)
+        self.first_subdivide = None
+        self.reads(1, 2)
+        self.step("extend" if self.kind == "octree" else "insert")      # a late pose into the scheme
+        self.reads(1, 1)
+        weights = {"insert": 1, "extend": 2, "subdivide_count": 2, "subdivide_planar_count": 1, "subdivide_callable": 1,
+                   "filter_count": 4, "filter_opaque": 2, "filter_subset": 3, "map_select": 3, "map_transform": 1,
+                   "apply_mask": 6, "ransac": 2, "transform_poses": 5, "transform_poses_refused": 3}
+        if self.index % 3 != 1 or j in (2, 3):      # rows leave before the motif: a mask or a filter
+            for kind in ("apply_mask", "ransac", "filter_count"):
+                if kind != "ransac" or j not in (1, 10):      # (the motif's own RANSAC: at most two per sequence)
+                    if self.step(kind):
+                        break
+            self.reads(1, 1)
+        self._motif2(j, second)
+        self.reads(1, 1)
+        if self.index % 4 == 2 and self.step("transform_poses_refused"):
+            self.reads(1, 1)
+        for _ in range(int(rng.integers(1, 3))):
+            if len(self.log) >= 17:
+                break
+            self.mutate(weights)
+            self.reads(1, 2)
+        if not self.model.flags["emptied"] and not self.model.displaced:
+            self.step("filter_count", {"crit": ["ge", 6]})
+            self.reads(1, 1)
+        if (j == 4 or (j == 0 and len(self.log) <= 18)) and not self.model.displaced:
+            # rows displaced out of their cubes: the last mutating operation; nearest and raycast must refuse
+            self.must("map_transform", {"fn": "shift_z", "poses": None})
+            self.must("nearest")
+            for k in ("raycast", "point_to_plane", "leaf_statistics"):
+                self.step(k)
+        return Sequence(self.seed, self.container, self.log, self.obs, self.meta, self.draws, self.rejected,
+                        self.model.flags, self.model.closest, self.ident)
+
+    def _motif2(self, j, second):
+        """The transition the seed's number fixes, with nothing mutating in between but what it names."""
+        self.in_motif = True
+        part = self._subset(always=True)      # (a proper subset S; S' is all poses)
+        sub = (j in (2, 7, 11)) != second
+        tp = {"poses": part if sub else None}
+        if j in (0, 7) and part is not None:
+            self.must("nearest", {"poses": part})
+            self.must("raycast", {"poses": None, "surface": "cube"})
+            self.must("nearest", {"poses": part})
+        elif j == 1:
+            self.must("ransac")
+            self.must("raycast")
+        elif j in (2, 10):
+            self._fixed_transform(tp)
+            self.subdivide_again()
+            self.must("nearest" if j == 2 else "ransac")
+        elif j in (3, 11):
+            self.must("adjustment_system")
+            self._fixed_transform(tp)
+            self.subdivide_again()
+            self.must("adjustment_system")
+        elif j == 5 or (j == 4 and second):
+            self.must("plane_segments")
+            first = dict(self.log[-1])
+            self.must("filter_count")
+            self.must("plane_segments", first)
+        elif j == 6 and part is not None:
+            self.must("leaf_planes", {"poses": part})
+            self.must("raycast", {"poses": None, "surface": "plane"})
+            self.must("point_to_plane", {"poses": part})
+        elif j == 8:
+            self.must("point_to_plane", {"poses": part})
+            self.must("transform_poses_refused")
+            self.must("point_to_plane", {"poses": part})
+        elif j == 9:
+            self.must("apply_mask")
+            self.must("raycast")
+        elif j == 4:
+            self.must("registration_system")
+        if j == 7:
+            self._fixed_transform(tp)
+            self.subdivide_again()
+            self.must("apply_mask")
+        self.in_motif = False
+
+    def _fixed_transform(self, fix):
+        """transform_poses for the selection `fix` names (the motions are drawn for it)."""
+        chosen = [p for p in self.model.poses if fix["poses"] is None or p in fix["poses"]]
+        for _ in range(4):
+            if self.step("transform_poses", {"poses": fix["poses"], "motions": self._pose_motions(chosen)}):
+                self.reads(0, 1)
+                return
+        raise AssertionError(f"seed {self.seed}: no transform_poses can be drawn\n{Sequence.printed(self)}")
+
+
 @functools.lru_cache(maxsize=None)
 def generate(seed):
-    return _Generator(seed).run()
+    return _Generator(seed).run() if seed < SEEDS2[0] else _Generator2(seed).run()
 
 
 # ---- what the logs must cover ------------------------------------------------------------------------------------------
@@ -749,4 +1120,51 @@ def transitions(log):
                     found.add("point_to_plane>ransac>point_to_plane")
     if sum(op["op"] == "ransac" for op in log) >= 2:
         found.add("two_ransac")
+    return found
+
+
+def transitions2(log):
+    """The names of TRANSITIONS2 that occur in a log of the second generation, with nothing mutating in between but
+    what the name itself lists."""
+    found = set()
+    fam = lambda k: "subdivide" if k in SUBDIVIDES else "filter" if k in FILTERS else k
+    mut = [i for i, op in enumerate(log) if op["op"] in ALL_MUTATING]
+    sel = lambda op: None if op.get("poses") is None else tuple(sorted(op["poses"]))
+
+    def reads_between(a):
+        """The read-only operations after the a-th mutating one, up to the next."""
+        end = mut[a + 1] if a + 1 < len(mut) else len(log)
+        return log[mut[a] + 1: end]
+
+    for a, i in enumerate(mut):
+        k = fam(log[i]["op"])
+        after = reads_between(a)
+        chain = [fam(log[m]["op"]) for m in mut[a: a + 3]]
+        if chain[:2] == ["transform_poses", "subdivide"]:
+            if any(op["op"] == "nearest" for op in reads_between(a + 1)):
+                found.add("transform_poses>subdivide>nearest")
+            if len(chain) == 3 and chain[2] in ("ransac", "apply_mask"):      # (a grid's RANSAC applies its mask itself)
+                found.add("transform_poses>subdivide>ransac>apply_mask")
+            before = log[(mut[a - 1] + 1 if a else 0): i]
+            if any(op["op"] == "adjustment_system" for op in before) \
+                    and any(op["op"] == "adjustment_system" for op in reads_between(a + 1)):
+                found.add("adjustment_system>transform_poses>subdivide>adjustment_system")
+        if k in ("ransac", "apply_mask") and after and after[0]["op"] == "raycast":
+            found.add("apply_mask>raycast")      # (the first call that looks at the forest after the mask)
+        if k == "transform_poses_refused" and after and after[0]["op"] == "point_to_plane":
+            found.add("transform_poses_refused>point_to_plane")
+        if log[i].get("fn") == "shift_z" and any(op["op"] == "nearest" for op in after):
+            found.add("map_transform(shift_z)>nearest")
+        if k == "filter" and a and after:
+            before = [op for op in reads_between(a - 1) if op["op"] == "plane_segments"]
+            again = [op for op in after if op["op"] == "plane_segments"]
+            if before and again and {n: v for n, v in before[-1].items()} == dict(again[0]):
+                found.add("plane_segments>filter>plane_segments")
+    for i in range(len(log) - 2):
+        x, y, z = log[i: i + 3]
+        if sel(x) is not None and sel(x) == sel(z) and sel(y) != sel(x):
+            if x["op"] == "leaf_planes" and y["op"] == "raycast" and y["surface"] == "plane" and z["op"] == "point_to_plane":
+                found.add("leaf_planes(S)>raycast_plane(S')>point_to_plane(S)")
+            if x["op"] == "nearest" and y["op"] == "raycast" and y["surface"] == "cube" and z["op"] == "nearest":
+                found.add("nearest(S)>raycast_cube(S')>nearest(S)")
     return found

@@ -3,6 +3,7 @@ tests/test_gpu_opseq.py): the caps the seed set must meet, the replay that forks
 scenes, and the NumPy specifications of the queries on the model's own tables."""
 
 import collections
+import hashlib
 
 import numpy as np
 import pytest
@@ -70,6 +71,99 @@ def test_seed_set_covers_kinds_containers_and_transitions():
     assert forms == {"f64", "f32", "fortran", "strided"}
 
 
+# sha256(repr((repr(q.log), q.obs, q.meta)))[:16] of generate(seed), computed in a worktree of the commit before the
+# second generation was added to tests/_opseq.py: the logs, observations and bookkeeping of the old seeds have not moved
+OLD_SEED_DIGESTS = {
+    0: "95a2e04756336fe4", 1: "a47d2a41cdd7313f", 2: "4785a4e202a0f090", 3: "692243ba79e4e1c6", 4: "1740aa98184586af",
+    5: "8fc1ed819b922469", 6: "8e1940261ed01b41", 7: "93c8547dfeb7a130", 8: "c54241329f2602e6", 9: "e781eea442ff06c9",
+    10: "8544a8e2e0447059", 11: "2c085854707350f1", 12: "6218001093344c3d", 13: "a5bfab1d125c972a",
+    14: "9f6dbed3ae3e5502", 15: "29200b693b0239a3", 16: "d3a26c6200974371", 17: "a16e3c9fca33e683",
+    18: "b7eea9eddb465ae1", 19: "8d3661ac86cc7b6c", 20: "cb2d2af59969bbe3", 21: "5c50425115225781",
+    22: "cf2ece52637c0c4d", 23: "3bf9f27738f50aaa"}
+
+
+@pytest.mark.parametrize("seed", S.SEEDS)
+def test_old_seeds_are_what_they_were(seed):
+    q = S.generate(seed)
+    assert hashlib.sha256(repr((repr(q.log), q.obs, q.meta)).encode()).hexdigest()[:16] == OLD_SEED_DIGESTS[seed]
+    assert not any(op["op"] in S.NEW_MUTATING + S.NEW_READ_ONLY for op in q.log)
+
+
+# ---- the second generation: the map queries and transform_poses ------------------------------------------------------------
+def _total(obs):
+    return sum(counters[2] for _, counters in obs.values())
+
+
+@pytest.mark.parametrize("seed", S.SEEDS2)
+def test_second_generation_caps_replay_and_scene(seed):
+    q = S.generate(seed)
+    assert 8 <= len(q.log) <= 24, q.printed()
+    assert len(q.log) == len(q.obs) == len(q.meta) == len(q.ident)
+    assert q.rejected <= 0.25 * q.draws, (q.rejected, q.draws)
+    m = S.Model(q.container)
+    for i, op in enumerate(q.log):
+        before = (m.observe(), m.pooled) if op["op"] == "transform_poses_refused" else None
+        m.apply(op)
+        assert m.observe() == q.obs[i], f"step {i}\n{q.printed(i)}"
+        assert m.pooled == q.meta[i]["pooled"]
+        if before is not None:      # a refused call changes nothing and invalidates nothing
+            assert (q.obs[i], q.meta[i]["pooled"]) == before and q.meta[i]["pooled"] == q.meta[i - 1]["pooled"]
+        ident = m.identity()
+        assert (ident is None) == (q.ident[i] is None)
+        for p in ident or ():
+            assert np.array_equal(ident[p][0], q.ident[i][p][0]) and np.array_equal(ident[p][1], q.ident[i][p][1])
+            # the identity: strictly ascending row numbers of the cloud as first inserted, one per surviving row
+            assert len(ident[p][0]) == q.obs[i][p][1][2] and np.all(np.diff(ident[p][0]) > 0)
+            assert len(ident[p][0]) == 0 or 0 <= ident[p][0][0] and ident[p][0][-1] < m.n_inserted[p]
+        if op["op"] == "transform_poses":      # no scheme remains, and a subdivide is the next mutating operation
+            assert not m.internal_nodes() and all(c[0] == len(t) for t, c in q.obs[i].values() if q.container["kind"] != "grid")
+            nxt = next(o["op"] for o in q.log[i + 1:] if o["op"] in S.ALL_MUTATING)
+            assert nxt in S.SUBDIVIDES, q.printed()
+    assert q.flags["depth2"] and q.flags["emptied"], q.printed()
+    assert q.closest > 1e-9
+    for p, (table, counters) in q.obs[-1].items():
+        assert counters[1] == len(table) and counters[2] == sum(d[0] for _, d in table)
+    shifted = [i for i, op in enumerate(q.log) if op.get("fn") == "shift_z"]
+    if shifted:      # only as the last mutating operation
+        assert not any(op["op"] in S.ALL_MUTATING for op in q.log[shifted[0] + 1:])
+
+
+def test_second_generation_covers_kinds_containers_and_transitions():
+    kinds, trans, containers = collections.Counter(), collections.Counter(), collections.Counter()
+    tp = collections.Counter()
+    utm = after_removal = async_mask = 0
+    worst = 0.0
+    for seed in S.SEEDS2:
+        q = S.generate(seed)
+        kinds.update(op["op"] for op in q.log)
+        kinds.update("raycast_" + op["surface"] for op in q.log if op["op"] == "raycast")
+        trans.update(S.transitions2(q.log))
+        containers[q.container["kind"]] += 1
+        worst = max(worst, q.rejected / q.draws)
+        moves = [i for i, op in enumerate(q.log) if op["op"] == "transform_poses"]
+        for i in moves:
+            tp[q.container["kind"]] += 1
+            tp["subset" if q.log[i]["poses"] is not None else "all"] += 1
+        utm += bool(moves) and q.container["utm"]
+        removers = S.FILTERS + ("apply_mask", "ransac", "map_select")
+        after_removal += any(q.log[k]["op"] in removers and _total(q.obs[k]) < _total(q.obs[k - 1])
+                             for i in moves for k in range(1, i))
+        async_mask += any(a["op"] == "ransac" and b["op"] == "raycast" for a, b in zip(q.log, q.log[1:]))
+    print("kinds:", dict(kinds))
+    print("transitions:", dict(trans))
+    print("containers:", dict(containers), "transform_poses:", dict(tp), "on UTM clouds:", utm,
+          "after rows were removed:", after_removal, "worst rejection share:", worst)
+    for k in S.NEW_MUTATING + S.NEW_READ_ONLY + ("raycast_cube", "raycast_plane"):
+        assert kinds[k] >= 5, (k, kinds[k])
+    for t in S.TRANSITIONS2:
+        assert trans[t] >= 2, (t, trans[t])
+    for c in ("grid", "manager", "octree"):
+        assert containers[c] >= 4, containers
+    for k in ("grid", "manager", "subset", "all"):
+        assert tp[k] >= 2, tp
+    assert utm >= 2 and after_removal >= 3 and async_mask >= 2
+
+
 class _Leaf:
     def __init__(self, corner, edge, rows):
         self.corner_min, self.edge_length, self._rows = corner, edge, rows
@@ -78,10 +172,12 @@ class _Leaf:
         return self._rows
 
 
-@pytest.mark.parametrize("seed", [0, 7])
+@pytest.mark.parametrize("seed", [0, 7, 106, 115])
 def test_numpy_specifications_answer_the_models_tables(seed):
     """locate_np, pooled_leaf_statistics_np, point_to_plane_np (through HostMap, which rebuilds the node table from
-    the leaves) and leaf_statistics_np on the model at the end of a sequence."""
+    the leaves) and leaf_statistics_np on the model at the end of a sequence; at the end of two sequences of the second
+    generation (115 contains a transform_poses) nearest_np, raycast_np, plane_segments_np, registration_system_np and
+    adjustment_system_np too."""
     q = S.generate(seed)
     m = S.Model.replay(q.container, q.log)
     leaves = {p: [_Leaf(c, e, r) for c, e, r in m.leaf_rows(p, non_empty=False)] for p in m.poses}
@@ -104,3 +200,35 @@ def test_numpy_specifications_answer_the_models_tables(seed):
         rows = [r for _, _, r in m.leaf_rows(p)]
         st = leaf_statistics_np(rows)
         assert st.count.tolist() == [len(r) for r in rows] and np.all(np.isfinite(st.covariance))
+    if seed < S.SEEDS2[0]:
+        return
+    assert (seed == 115) == any(op["op"] == "transform_poses" for op in q.log)
+    e = S.cloud_edge(m.c)
+    nn = hm.nearest(stored[::20] + 0.003 * e, 3, max_distance=0.5 * e)
+    assert (nn.count > 0).all() and np.all(nn.distance2[:, 0] <= 3 * (0.003 * e) ** 2 * (1 + 1e-12))
+    assert np.all(np.diff(nn.distance2, axis=1)[np.isfinite(nn.distance2[:, 1:])] >= 0)
+    own = hm.nearest(stored[::20], 1, max_distance=0.05 * e)
+    sizes = {p: len(m.pose_rows(p)) for p in m.poses}
+    assert np.all(own.distance2[:, 0] == 0.0) and all(0 <= i < sizes[p] for p, i in zip(own.pose[:, 0], own.index[:, 0]))
+    # rays from outside towards stored points hit an occupied leaf no later than the leaf of the point they aim at
+    aim = stored[::20]
+    O = aim + np.array([0.0, 0.0, 6.0 * e])
+    for surface in ("cube", "plane"):
+        hits = hm.raycast(O, aim - O, 8.0 * e, surface=surface)
+        assert hits.node.shape == (len(O),) and np.all(hits.t[hits.hit] <= 8.0 * e) and np.all(np.isinf(hits.t[~hits.hit]))
+        assert np.all(hm.nodes["first_child"][hits.node[hits.hit]] < 0) and np.all((hits.row >= 0) == (hits.hit & (surface == "plane")))
+    cube = hm.raycast(O, aim - O, 8.0 * e)
+    assert cube.hit.all() and np.all(cube.t <= 6.0 * e)
+    assert hm.raycast(O, np.zeros_like(O), 8.0 * e).hit.sum() == 0
+    seg = hm.plane_segments(None, 8, 1e-3 * e ** 2)
+    assert len(seg.label) == len(seg.planes) and seg.neighbour.shape == (len(seg.planes), 6)
+    assert seg.segments.n_leaves.sum() == (seg.label >= 0).sum() and seg.label.max() + 1 == len(seg.segments.count)
+    p0 = m.poses[0]
+    scan = m.pose_rows(p0)[:800]
+    rs = hm.registration_system(scan, None, None, per_point=True)
+    assert rs.n_located == len(scan) and 0 < rs.n_used <= rs.n_located and np.array_equal(rs.H, rs.H.T)
+    assert np.array_equal(rs.node, hm.locate(scan)) and np.all(np.isfinite(rs.residual[rs.row >= 0]))
+    if m.kind != "octree":
+        ad = hm.adjustment_system(None, None, leaves=True)
+        assert ad.H.shape == (len(m.poses), 6, 6) and np.all(np.isfinite(ad.H)) and ad.n_leaves[0] == len(ad.leaves)
+        assert int(ad.blocks.count.sum()) == len(stored)

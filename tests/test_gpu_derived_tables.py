@@ -7,13 +7,18 @@ whatever its stamp says.  So the stamp decides only in the first call after a ch
 table holds.  For every mutator and for both selections, a forest A that holds all four tables for that selection is
 changed and asked for the same selection first: the library's timers must show that all four tables were made again,
 every array must equal, byte for byte, what a forest B that never made a table answers, and point_to_plane at the ABI,
-which never recomputes, must refuse the old planes as stale."""
+which never recomputes, must refuse the old planes as stale.
+
+raycast and registration_system keep no table of their own: the cube cast answers from the neighbour index (made in the
+timed region nn_group), the plane cast and registration_system from the pooled planes (pool_group) - so MADE covers them.
+A transform_poses that is refused (DomainError) is the opposite case: nothing may be made again, every answer stays."""
 
 import numpy as np
 import pytest
 
 from octreelib_amd import _native as nat
 from octreelib_amd._engine import Forest
+from octreelib_amd.registration import se3_exp
 from tests._util import set_option
 from tests.test_cpu_segments import floor_and_wall
 
@@ -21,6 +26,16 @@ pytestmark = pytest.mark.gpu
 
 K = 64
 ORIGIN = np.array([2.0, 2.0, 1.5])
+MOVE = [se3_exp([0.01, -0.02, 0.015, 0.05, -0.03, 0.02], ORIGIN), se3_exp([-0.015, 0.01, 0.02, -0.02, 0.04, 0.01], ORIGIN),
+        se3_exp([0.02, 0.015, -0.01, 0.03, 0.02, -0.04], ORIGIN)]
+
+
+def _rays(Q):
+    """A fixed fan of rays from the queries: three directions per origin, one of them along an axis."""
+    O = np.repeat(Q[:150], 3, axis=0)
+    D = np.random.default_rng(3).normal(size=(len(O), 3))
+    D[::3] = np.eye(3)[np.arange(len(O[::3])) % 3]
+    return np.ascontiguousarray(O), np.ascontiguousarray(D)
 
 
 def _scene():
@@ -60,6 +75,9 @@ def _consume(f, Q, selections, made=None):
             nn = f.nearest(Q, 4, 0.2, slots)
             ad = f.adjustment_system(slots=slots, origin=ORIGIN)
             sg = f.plane_segments(slots)
+            rc = f.raycast(*_rays(Q), 3.0, 0.0, slots, "cube")
+            rp = f.raycast(*_rays(Q), 3.0, 0.0, slots, "plane")
+            rg = f.registration_system(Q, slots=slots, origin=ORIGIN, per_point=True)
             if i == 0 and made is not None:
                 timers = f.ctx.timings()
                 assert tuple(k for k in MADE if k in timers) == tuple(made), (tag, sorted(timers))
@@ -76,7 +94,12 @@ def _consume(f, Q, selections, made=None):
                         ("adj.n_leaves", np.asarray(ad.n_leaves, dtype=np.int64)), ("seg.neighbour", sg.neighbour),
                         ("seg.label", sg.label), ("seg.root", t.root), ("seg.n_leaves", t.n_leaves),
                         ("seg.count", t.count), ("seg.mean", t.mean), ("seg.covariance", t.covariance),
-                        ("seg.eigenvalues", t.eigenvalues), ("seg.eigenvectors", t.eigenvectors)):
+                        ("seg.eigenvalues", t.eigenvalues), ("seg.eigenvectors", t.eigenvectors),
+                        ("ray.cube.node", rc.node), ("ray.cube.t", rc.t), ("ray.cube.row", rc.row),
+                        ("ray.plane.node", rp.node), ("ray.plane.t", rp.t), ("ray.plane.row", rp.row),
+                        ("reg.H", rg.H), ("reg.g", rg.g), ("reg.cost", np.float64(rg.cost)),
+                        ("reg.counts", np.array([rg.n_used, rg.n_located], dtype=np.int64)), ("reg.node", rg.node),
+                        ("reg.row", rg.row), ("reg.residual", rg.residual)):
             out[f"{name}[{tag}]"] = np.ascontiguousarray(a)
     return out
 
@@ -164,11 +187,22 @@ def _clear_and_again(f, poses, late, extra):
     f.subdivide(K)
 
 
+def _transform_poses(slots):
+    """Move the poses of `slots` (None: all), then subdivide again: transform_poses leaves no scheme."""
+    def run(f, poses, late, extra):
+        f.transform_poses(MOVE if slots is None else [MOVE[s] for s in slots], slots)
+        assert not f.has_scheme and f.info is None
+        f.subdivide(K)
+    return run
+
+
 MUTATORS = [("late pose, incremental", _late_pose(True)), ("late pose, re-placed", _late_pose(False)),
             ("extend_pose", _extend_pose), ("rebuild with another K", _rebuild_other_k),
             ("planar build", _planar_build), ("adopt_scheme", _adopt_scheme), ("set_contents", _set_contents),
             ("RANSAC and apply_device_mask", _ransac_device_mask), ("apply_host_mask", _host_mask),
-            ("filter_count", _filter_count), ("clear and the same poses again", _clear_and_again)]
+            ("filter_count", _filter_count), ("clear and the same poses again", _clear_and_again),
+            ("transform_poses then subdivide", _transform_poses(None)),
+            ("transform_poses of 0 2 then subdivide", _transform_poses([0, 2]))]
 
 
 @pytest.mark.parametrize("held", [None, [0, 2]], ids=["holds_all", "holds_0_2"])
@@ -204,6 +238,59 @@ def test_no_table_survives(what, mutate, held):
         changed = [n for n in got if got[n].shape != before[n].shape or got[n].tobytes() != before[n].tobytes()]
         if mutate is not _clear_and_again:
             assert any(n.startswith("planes.") for n in changed) and any(n.startswith("adj.") for n in changed), changed
+    finally:
+        a.close()
+        b.close()
+
+
+@pytest.mark.parametrize("held", [None, [0, 2]], ids=["holds_all", "holds_0_2"])
+def test_refused_transform_poses_keeps_every_table(held):
+    """The row of the matrix that is no mutator: a transform_poses the library refuses (a moved point leaves the voxel
+    domain) changes nothing, so nothing may be made again and every answer is the one from before."""
+    poses, late, extra, Q = _scene()
+    other = [0, 2] if held is None else None
+    a = _make(poses)
+    try:
+        before = _consume(a, Q, (other, held), made=MADE)
+        far = np.eye(4)
+        far[0, 3] = 2.0 ** 31      # 2^31 voxel edges
+        mirror = (a.epoch, a.has_scheme, a._dirty, list(a.slot_epoch), a.n_ord)
+        with pytest.raises(nat.DomainError):
+            a.transform_poses([MOVE[0], far] if held is not None else [MOVE[0], MOVE[1], far], held)
+        assert (a.epoch, a.has_scheme, a._dirty, list(a.slot_epoch), a.n_ord) == mirror and a.info is not None
+        assert _point_to_plane_abi(a, Q)[0] == nat.OCTL_OK
+        a._pooled = None
+        got = _consume(a, Q, (held,), made=())
+        assert got and set(got) <= set(before)
+        for name in got:
+            x, y = got[name], before[name]
+            assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), name
+    finally:
+        a.close()
+
+
+@pytest.mark.parametrize("what,mutate", MUTATORS, ids=[m[0].replace(" ", "_").replace(",", "") for m in MUTATORS])
+def test_raycast_on_two_tables_held_for_two_selections(what, mutate):
+    """raycast is the consumer with two tables behind it, each with its own (stamp, selection) pair: the pooled planes
+    for the plane cast, the neighbour index for the cube cast.  Forest A holds the planes for ALL poses and the
+    neighbour index for [0, 2]; after the change both casts, for both selections, must equal what a forest B that held
+    nothing answers, byte for byte - one stale table is enough for a wrong answer."""
+    poses, late, extra, Q = _scene()
+    a, b = _make(poses), _make(poses)
+    try:
+        a.leaf_planes(None)
+        a.nearest(Q, 4, 0.2, [0, 2])
+        mutate(a, poses, late, extra)
+        mutate(b, poses, late, extra)
+        O, D = _rays(Q)
+        hit = 0
+        # (each table is asked first for the selection it holds: nothing but its stamp can tell A that it is stale)
+        for slots, surface in ((None, "plane"), ([0, 2], "cube"), ([0, 2], "plane"), (None, "cube")):
+            x, y = a.raycast(O, D, 3.0, 0.0, slots, surface), b.raycast(O, D, 3.0, 0.0, slots, surface)
+            for name in ("node", "t", "row"):
+                assert getattr(x, name).tobytes() == getattr(y, name).tobytes(), (what, slots, surface, name)
+            hit += int((x.node >= 0).sum())
+        assert hit > len(O)      # (the fan sees the map)
     finally:
         a.close()
         b.close()

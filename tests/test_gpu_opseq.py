@@ -10,6 +10,15 @@ project states elsewhere (no tolerance is introduced here):
   * locate == locate_np on tables downloaded now; every stored, undisplaced point locates to the leaf that stores it;
   * leaf_planes: the pooled bound of tests/test_gpu_query.py (_check_planes); point_to_plane rows / NaN rules equal to
     point_to_plane_np on the returned table, distances within 4 eps sum |n_i d_i| of the longdouble value;
+  * nearest == nearest_np and raycast == raycast_np (both surfaces), bit for bit, on rows, leaves and planes downloaded
+    now (tests/test_gpu_nearest.py, tests/test_gpu_raycast.py); Neighbours.index names rows of the clouds as first
+    inserted, by the MODEL's bookkeeping (Sequence.ident), through masks, filters, extend and transform_poses;
+  * plane_segments: neighbour, label, root, n_leaves equal to plane_segments_np, the merged table within the bound of
+    tests/test_gpu_segments.py; registration_system: per-point answers and the sums under the contract of
+    tests/test_gpu_registration.py; adjustment_system: the block table is that of the leaves downloaded now (moments
+    within the bound of tests/test_gpu_adjustment.py::test_block_moments), the sums under _check_system;
+  * transform_poses_refused raises DomainError and changes nothing; after rows were displaced nearest and raycast raise
+    RuntimeError;
   * the queries are read-only (tables, permutation, coordinates, counters, the error word);
   * at the C ABI octl_forest_point_to_plane answers OCTL_E_STATE exactly when the model says something mutating has
     happened since the last pooled table.
@@ -56,6 +65,8 @@ class Device:
             self.o = Octree(OctreeConfig(), np.array(container["corner"]), np.float64(container["edge"]))
         self.f = self.o._forest
         self.poses = []
+        self.displaced = False
+        self.replaced = False      # a map function replaced the contents: the store is numbered anew, in block order
 
     def leaves(self, p):
         if self.kind == "grid":
@@ -78,6 +89,56 @@ class Device:
         if self.kind == "octree":
             return self.o.point_to_plane(Q, mp, mv)
         return self.o.point_to_plane(Q, poses, mp, mv)
+
+    def nearest(self, Q, k, r, poses):
+        if self.kind == "octree":
+            return self.o.nearest(Q, k, max_distance=r)
+        return self.o.nearest(Q, k, max_distance=r, pose_numbers=poses)
+
+    def raycast(self, rays, poses, surface, mp, mv):
+        O, D, tmin, tmax = rays
+        sel = {} if self.kind == "octree" else {"pose_numbers": poses}
+        return self.o.raycast(O, D, tmax, min_range=tmin, surface=surface, min_points=mp, max_variance=mv, **sel)
+
+    def plane_segments(self, poses, **gates):
+        return self.o.plane_segments(**gates) if self.kind == "octree" else self.o.plane_segments(poses, **gates)
+
+    def registration_system(self, scan, T, poses, **gates):
+        if self.kind == "octree":
+            return self.o.registration_system(scan, T, per_point=True, **gates)
+        return self.o.registration_system(scan, T, poses, per_point=True, **gates)
+
+    def name(self, p):
+        """The pose column of Neighbours for pose p (an Octree's is 0)."""
+        return 0 if self.kind == "octree" else p
+
+    def rays(self, seed, n, max_range, min_range):
+        """(origins, directions, min_range (n,), max_range (n,)): origins at jittered stored points, a third of them
+        pushed out of the scene; directions random, a quarter axis-parallel, four zero; six dead rays (max_range <
+        min_range, a NaN component)."""
+        rng = np.random.default_rng([seed, 0x4A7])
+        e = S.cloud_edge(self.c)
+        xyz = self.f.xyz
+        O = (xyz[rng.integers(0, len(xyz), n)] if len(xyz) else np.zeros((n, 3))) + rng.normal(0.0, 0.01 * e, (n, 3))
+        O[: n // 3] += rng.uniform(-3.0, 3.0, (n // 3, 3)) * e
+        D = rng.normal(size=(n, 3))
+        q = n // 4
+        D[n // 3: n // 3 + q] = np.eye(3)[rng.integers(0, 3, q)] * rng.choice([-1.0, 1.0], q)[:, None]
+        D[-10:-6] = 0.0
+        tmin, tmax = np.full(n, float(min_range)), np.full(n, float(max_range))
+        tmax[-6:-3] = min_range - 0.5 * e
+        O[-3, 1], D[-2, 0], O[-1, 2] = np.nan, np.nan, np.inf
+        return np.ascontiguousarray(O), np.ascontiguousarray(D), tmin, tmax
+
+    def scan(self, op):
+        """(scan, transform) of a registration_system record: stored points of one pose moved by the record's motion;
+        the transform is None or that motion's inverse."""
+        from octreelib_amd.registration import transform_np
+
+        lv = self.leaves(op["pose"])
+        rows = np.vstack([v.get_points() for v in lv]) if lv else np.empty((0, 3))
+        pick = np.random.default_rng([op["seed"], 0x5CA]).permutation(len(rows))[: op["n"]]
+        return transform_np(S.motion(op["motion"]), rows[pick]), S.inverse_motion(op["motion"]) if op["inverse"] else None
 
     def queries(self, seed, n):
         """Stored points jittered, some pushed out of the scene, and the BAD rows of tests/test_gpu_query.py."""
@@ -107,6 +168,8 @@ class Device:
         elif k in ("map_select", "map_transform"):
             fn = S.build_map(op["fn"], S.cloud_edge(self.c))
             o.map_leaf_points(fn) if self.kind == "octree" else o.map_leaf_points(fn, op["poses"])
+            self.displaced = self.displaced or op["fn"] == "shift_z"
+            self.replaced = self.replaced or k == "map_transform"
         elif k == "apply_mask":
             n = self.counters(op["pose"])[2]
             mask = np.random.default_rng([op["seed"], 0x3A5C]).random(n) < op["keep"]
@@ -127,6 +190,42 @@ class Device:
         elif k == "point_to_plane":
             Q = self.queries(op["seed"], op["n"])
             return Q, self.point_to_plane(Q, op["poses"], op["min_points"], op["max_variance"])
+        elif k in ("transform_poses", "transform_poses_refused"):
+            from octreelib_amd import _native as nat
+
+            T = [S.motion(m) for m in op["motions"]]
+            if k == "transform_poses":
+                o.transform_poses(T, op["poses"])
+            else:
+                with pytest.raises(nat.DomainError):
+                    o.transform_poses(T, op["poses"])
+        elif k == "nearest":
+            Q = self.queries(op["seed"], op["n"])
+            if self.displaced:
+                with pytest.raises(RuntimeError):
+                    self.nearest(Q, op["k"], op["r"], op["poses"])
+                return None
+            return Q, self.nearest(Q, op["k"], op["r"], op["poses"])
+        elif k == "raycast":
+            rays = self.rays(op["seed"], op["n"], op["max_range"], op["min_range"])
+            args = (rays, op["poses"], op["surface"], op["min_points"], op["max_variance"])
+            if self.displaced:
+                with pytest.raises(RuntimeError):
+                    self.raycast(*args)
+                return None
+            hits = self.raycast(*args)
+            # (the table `row` names: the mirror's copy of the one the cast was made against, no device call)
+            return rays, hits, self.leaf_planes(op["poses"]) if op["surface"] == "plane" else None
+        elif k == "plane_segments":
+            return self.plane_segments(op["poses"], **{g: op[g] for g in ("min_points", "max_variance", "max_angle", "max_offset")})
+        elif k == "registration_system":
+            scan, T = self.scan(op)
+            gates = {g: op[g] for g in ("min_points", "max_variance", "max_distance", "huber_delta")}
+            return scan, T, self.registration_system(scan, T, op["poses"], **gates)
+        elif k == "adjustment_system":
+            T = None if op["motions"] is None else np.stack([S.motion(m) for m in op["motions"]])
+            return T, o.adjustment_system(T, op["poses"], min_points=op["min_points"], min_poses=op["min_poses"],
+                                          max_variance=op["max_variance"], leaves=True)
         elif k == "node_cubes":
             return o.node_cubes()
         elif k == "counters":
@@ -155,8 +254,13 @@ class Device:
         """Inside, every getter downloads its table NOW; afterwards the forest's host-side caches and its booked
         point count are exactly what they were, so that looking does not change what a later call answers from."""
         f = self.f
-        names = ("_nodes", "_voxels", "_blocks", "_order", "_xyz", "_perm", "_slot_blocks", "_counts", "_internal",
-                 "_pooled", "_n_ord", "_n_ord_pending")
+        # every host-side cache Forest._invalidate() clears - read off the method itself, so that a cache added there
+        # is saved here too - and the booked point count
+        probe = object.__new__(type(f))
+        type(f)._invalidate(probe)
+        names = tuple(vars(probe)) + ("_n_ord", "_n_ord_pending")
+        assert {"_nodes", "_voxels", "_blocks", "_order", "_xyz", "_perm", "_slot_blocks", "_counts", "_internal",
+                "_pooled"} <= set(names)
         f.ensure_built()      # (a pending insertion is placed first: the build clears the caches itself)
         saved = {n: getattr(f, n) for n in names}
         f._invalidate()
@@ -190,6 +294,58 @@ class Device:
         out.append(_stats_bytes(pl) + (pl.node.tobytes(),))
         cnt, lam = self.f.split_stats()
         out.append((cnt.tobytes(), lam.tobytes()))
+        near, hits, seg = self.map_answers()
+        if near is not None:
+            out.append(tuple(a.tobytes() for a in (near.index, near.pose, near.distance2, near.count)))
+            out.append(tuple(a.tobytes() for h in hits for a in (h.node, h.t, h.row)))
+        t = seg.segments
+        out.append(tuple(np.ascontiguousarray(a).tobytes() for a in (seg.neighbour, seg.label, t.root, t.n_leaves, t.count,
+                                                                      t.mean, t.covariance, t.eigenvalues, t.eigenvectors)))
+        return out
+
+    def map_answers(self):
+        """nearest, raycast (both surfaces) and plane_segments for a fixed set of queries and rays that does not depend
+        on the build history: drawn from the stored rows in lexicographic order.  (None, None, segments) once rows
+        are displaced."""
+        e = S.cloud_edge(self.c)
+        seg = self.plane_segments(None, min_points=8, max_variance=1e-3 * e ** 2, max_angle=0.1, max_offset=0.05 * e)
+        if self.displaced:
+            return None, None, seg
+        rows = [v.get_points() for p in self.poses for v in self.leaves(p)]
+        U = np.unique(np.vstack(rows), axis=0) if rows else np.zeros((1, 3))
+        rng = np.random.default_rng(0xF1A7)
+        Q = U[rng.integers(0, len(U), 200)] + rng.normal(0.0, 0.01 * e, (200, 3))
+        Q[:20] += rng.uniform(-3.0, 3.0, (20, 3)) * e
+        D = rng.normal(size=(200, 3))
+        D[:50] = np.eye(3)[rng.integers(0, 3, 50)]
+        rays = (Q, D, np.zeros(200), np.full(200, 6.0 * e))
+        near = self.nearest(Q, 4, 0.5 * e, None)
+        return near, [self.raycast(rays, None, surface, None, None) for surface in ("cube", "plane")], seg
+
+    def map_by_cube(self):
+        """map_answers() with everything that belongs to one build history - node ids, plane rows, segment labels -
+        named by the leaf's cube instead: nearest as bytes, raycast as (t bytes, cubes hit) per surface, the
+        segments as the set of their leaves' cubes and the neighbour table by cube."""
+        near, hits, seg = self.map_answers()
+        corner, edge = self.o.node_cubes()
+        cube = lambda n: None if n < 0 else ((corner[n] + 0.0).tobytes(), float(edge[n]))
+        out = {}
+        if near is not None:
+            # (the numbers of a store that was numbered anew follow the block table: one build history's)
+            out["nearest"] = tuple(a.tobytes() for a in ((near.pose, near.distance2, near.count) if self.replaced else
+                                                         (near.index, near.pose, near.distance2, near.count)))
+            pl = self.leaf_planes(None)
+            for surface, h in zip(("cube", "plane"), hits):
+                assert np.all((h.row >= 0) == ((h.node >= 0) & (surface == "plane")))
+                assert surface == "cube" or np.array_equal(pl.node[h.row[h.row >= 0]], h.node[h.row >= 0])
+                out["raycast " + surface] = (h.t.tobytes(), [cube(n) for n in h.node.tolist()])
+        ids = seg.planes.node.tolist()
+        parts = {}
+        for n, lab in zip(ids, seg.label.tolist()):
+            if lab >= 0:
+                parts.setdefault(lab, []).append(cube(n))
+        out["segments"] = sorted(sorted(v) for v in parts.values())
+        out["neighbour"] = {cube(n): [cube(b) for b in nb] for n, nb in zip(ids, seg.neighbour.tolist())}
         return out
 
     def by_cube(self):
@@ -264,6 +420,134 @@ def _check_stats_value(seq, i, last_build, nd, cnt, lam):
         assert len(cnt) == len(nd["edge"]) and not cnt.any() and np.isnan(lam).all()
 
 
+# ---- the map queries against their definitions, on tables that are downloaded now ----------------------------------------
+def _stored(dev, ident):
+    """{pose: (rows, index)} of what the forest stores now - call inside Device.neutral(): the rows of every pose
+    from the ordered coordinates, index = the row number of each in the cloud as first inserted.  The device's own
+    account of it is the permutation (tests/test_gpu_nearest._survivors); where the model keeps one (ident: {pose:
+    (index, row hash)} of Sequence.ident) it is the model's, found by the row's bits, and the two must agree."""
+    f = dev.f
+    xyz, perm = f.xyz, f.perm
+    off = np.concatenate([[0], np.cumsum(f.slot_sizes)]).astype(np.int64)
+    out = {}
+    for s_, p in enumerate(dev.poses):
+        mine = (perm >= off[s_]) & (perm < off[s_ + 1])
+        rows, index = xyz[mine], perm[mine] - off[s_]
+        if ident is not None:
+            orig, hsh = ident[p]
+            assert len(rows) == len(orig), (p, len(rows), len(orig))
+            order = np.argsort(hsh, kind="stable")
+            pos = np.minimum(np.searchsorted(hsh[order], S.row_hashes(rows)), max(len(hsh) - 1, 0))
+            assert np.array_equal(hsh[order][pos], S.row_hashes(rows)), f"pose {p} stores a row the model does not have"
+            assert np.array_equal(orig[order][pos], index), f"pose {p}: the rows' numbers are not the model's"
+            index = orig[order][pos]
+        a = np.argsort(index, kind="stable")
+        out[p] = (np.ascontiguousarray(rows[a]), index[a])
+    return out
+
+
+def _check_nearest(dev, got, Q, k, r, sel, ident, what):
+    """nearest_np over the stored rows, bit for bit; its indices mapped to rows of the clouds as first inserted (the
+    map is ascending, so the order (d2, slot, index) is the same in both numberings)."""
+    from octreelib_amd.query import nearest_np
+    from tests.test_gpu_nearest import _assert_equal
+
+    stored = _stored(dev, ident)
+    chosen = [p for p in dev.poses if sel is None or p in sel]
+    ref = nearest_np(Q, [(dev.name(p), stored[p][0]) for p in chosen], k, max_distance=r)
+    index = ref.index.copy()
+    for p in chosen:      # (pose numbers are distinct; an Octree has one cloud)
+        m = (ref.pose == dev.name(p)) & (ref.index >= 0)
+        index[m] = stored[p][1][ref.index[m]]
+    ref.index = index
+    _assert_equal(got, ref, what)
+
+
+def _check_raycast(dev, got, rays, sel, surface, mp, mv, planes, what):
+    """raycast_np over the leaves the tables downloaded now describe (tests/test_gpu_raycast._leaf_set) and, for the
+    plane form, the table the cast was made against, bit for bit."""
+    from octreelib_amd.query import normalize_directions, ray_inputs, raycast_np
+    from tests._raycast import assert_hits_equal
+    from tests.test_gpu_raycast import _leaf_set
+
+    slot_of = {p: s_ for s_, p in enumerate(dev.poses)}
+    cube, count = _leaf_set(dev.f, None if sel is None else [slot_of[p] for p in sel])
+    O, D, tmin, tmax = rays
+    o, dn, tmin, tmax = ray_inputs(O, normalize_directions(D), tmin, tmax)
+    ref = raycast_np(o, dn, tmax, *cube, t_min=tmin, count=count, planes=planes, surface=surface, min_points=mp,
+                     max_variance=mv)
+    assert_hits_equal(got, ref, what)
+
+
+def _check_pooled(dev, planes, sel, leaves, what):
+    """A pooled table against the leaves downloaded now (tests/test_gpu_query._check_planes)."""
+    from tests.test_gpu_query import _check_planes
+
+    chosen = dev.poses if sel is None else sel
+    slot_of = {p: s_ for s_, p in enumerate(dev.poses)}
+    pose_of = {s_: p for p, s_ in slot_of.items()}
+    if any(leaves[p] for p in chosen):
+        _check_planes(dev.o, dev.f, planes, sorted(slot_of[p] for p in chosen), lambda s_: leaves[pose_of[s_]], what)
+    else:
+        assert len(planes) == 0
+
+
+def _check_segments(dev, got, sel, gates, nodes, voxels, leaves, what):
+    from octreelib_amd.query import plane_segments_np
+    from tests.test_cpu_segments import table_error_over_bound
+    from tests.test_gpu_segments import _assert_equal
+
+    _check_pooled(dev, got.planes, sel, leaves, what)
+    ref = plane_segments_np(got.planes, nodes, voxels, dev.f.mode, dev.f._cube[1], gates["min_points"],
+                            gates["max_variance"], gates["max_angle"], gates["max_offset"])
+    _assert_equal(got, ref, what)
+    assert table_error_over_bound(got) <= 1.0, what
+
+
+def _check_registration(dev, scan, T, s, op, nodes, voxels, leaves, what):
+    from octreelib_amd.query import PointToPlane, locate_np
+    from octreelib_amd.registration import default_origin, transform_np
+    from tests.test_gpu_registration import _check_contract
+
+    _check_pooled(dev, s.planes, op["poses"], leaves, what)
+    moved = transform_np(T, scan)
+    node = locate_np(nodes, voxels, dev.f.mode, dev.f._cube[1], moved)
+    _check_point_to_plane(PointToPlane(s.node, s.row, s.residual, s.planes), s.planes, moved, node, op["min_points"],
+                          op["max_variance"])
+    assert np.array_equal(s.origin, default_origin(T, scan)), what
+    _check_contract(s, scan, T, s.origin, what, max_distance=op["max_distance"], huber_delta=op["huber_delta"])
+
+
+def _check_adjustment(dev, T, s, op, leaves, what):
+    """The block table is that of the leaves downloaded now - counts exactly, moments within the bound of
+    tests/test_gpu_adjustment.py::test_block_moments - and the sums are within _check_system's bound of the
+    definition on it."""
+    from octreelib_amd.adjustment import block_moments_np
+    from tests.test_gpu_adjustment import _check_system
+
+    LD = np.longdouble
+    chosen = [p for p in dev.poses if op["poses"] is None or p in op["poses"]]
+    assert list(s.pose_numbers) == chosen, (what, s.pose_numbers)
+    nd = dev.f.nodes
+    rows = [(v.node, k, nd["corner"][v.node] + nd["edge"][v.node] / 2.0, v.get_points())
+            for k, p in enumerate(chosen) for v in leaves[p]]
+    own = block_moments_np(rows, chosen, None, dtype=LD)
+    bm = s.blocks
+    assert np.array_equal(bm.node, own.node) and np.array_equal(bm.pose, own.pose) and np.array_equal(bm.count, own.count), what
+    assert np.array_equal(bm.anchor, own.anchor), what
+    points = {(int(n), int(k)): x for n, k, _, x in rows if len(x)}
+    for i in range(len(bm)):
+        d = points[(int(bm.node[i]), int(bm.pose[i]))].astype(LD) - bm.anchor[i].astype(LD)
+        n, R = len(d), float(np.abs(d).max())
+        gamma = (-(-n // 64) + -(-n // 4096) + 1 + 16) * EPS
+        assert np.all(np.abs(bm.s[i].astype(LD) - own.s[i]) <= 2 * gamma * R * n), (what, i)
+        assert np.all(np.abs(bm.M[i].astype(LD) - own.M[i]) <= 4 * gamma * R * R * n), (what, i)
+    gates = {"min_points": op["min_points"], "min_poses": op["min_poses"]}
+    if op["max_variance"] is not None:
+        gates["max_variance"] = op["max_variance"]
+    _check_system(s, T, s.origin, what, **gates)
+
+
 def _check_result(dev, seq, i, op, res, last_build):
     """What the log's own read-only operation returned - from whatever cache it answered - against tables that are
     downloaded now, with the same contracts as the battery below."""
@@ -272,8 +556,9 @@ def _check_result(dev, seq, i, op, res, last_build):
     from tests.test_gpu_query import _check_planes
 
     k, f = op["op"], dev.f
-    if k not in S.READ_ONLY:
+    if k not in S.ALL_READ_ONLY or (res is None and k in ("nearest", "raycast")):      # (refused: rows are displaced)
         return
+    what = f"operation {i} {k}"
     with dev.neutral():
         nodes, voxels = f.nodes, f.voxels
         leaves = {p: dev.leaves(p) for p in dev.poses}
@@ -295,6 +580,19 @@ def _check_result(dev, seq, i, op, res, last_build):
         elif k == "locate":
             Q, got = res
             assert got.dtype == np.int32 and np.array_equal(got, locate_np(nodes, voxels, f.mode, f._cube[1], Q))
+        elif k == "nearest":
+            _check_nearest(dev, res[1], res[0], op["k"], op["r"], op["poses"], seq.ident[i], what)
+        elif k == "raycast":
+            rays, hits, planes = res
+            if planes is not None:
+                _check_pooled(dev, planes, op["poses"], leaves, what)
+            _check_raycast(dev, hits, rays, op["poses"], op["surface"], op["min_points"], op["max_variance"], planes, what)
+        elif k == "plane_segments":
+            _check_segments(dev, res, op["poses"], op, nodes, voxels, leaves, what)
+        elif k == "registration_system":
+            _check_registration(dev, *res, op, nodes, voxels, leaves, what)
+        elif k == "adjustment_system":
+            _check_adjustment(dev, *res, op, leaves, what)
         else:
             Q, r = res if k == "point_to_plane" else (None, None)
             planes = r.planes if k == "point_to_plane" else res
@@ -311,13 +609,49 @@ def _check_result(dev, seq, i, op, res, last_build):
                                       op["max_variance"])
 
 
-def _check_queries(dev, rng, displaced):
+def _check_map_queries(dev, rng, displaced, sels, leaves, Q, ident):
+    """The battery's map queries: one nearest, one raycast per surface, one plane_segments per pose selection, each
+    against its definition on tables downloaded afterwards."""
+    e = S.cloud_edge(dev.c)
+    sel = sels[-1]
+    k, r = int(rng.choice([1, 3, 8])), float(rng.choice([0.05, 0.5, 2.0])) * e
+    rays = dev.rays(int(rng.integers(1 << 30)), 150, float(rng.uniform(0.5, 8.0)) * e, [0.0, 0.1 * e][int(rng.integers(0, 2))])
+    mp, mv = int(rng.choice([1, 8])), [None, 1e-3 * e ** 2][int(rng.integers(0, 2))]
+    gates = {"min_points": int(rng.choice([8, 16])), "max_variance": mv, "max_angle": float(rng.choice([0.1, 0.3])),
+             "max_offset": float(rng.choice([0.05, 0.02])) * e}
+    if displaced:      # (the two that must refuse; the error word moves with them, so the caller reads it afterwards)
+        with pytest.raises(RuntimeError):
+            dev.nearest(Q[-150:], k, r, sel)
+        for surface in ("cube", "plane"):
+            with pytest.raises(RuntimeError):
+                dev.raycast(rays, sel, surface, mp, mv)
+        return
+    near = dev.nearest(Q[-150:], k, r, sel)
+    hits = {}
+    for surface in ("cube", "plane"):
+        got = dev.raycast(rays, sel, surface, mp, mv)
+        hits[surface] = (got, dev.leaf_planes(sel) if surface == "plane" else None)
+    segments = [(x, dev.plane_segments(x, **gates)) for x in sels]
+    with dev.neutral():
+        nodes, voxels = dev.f.nodes, dev.f.voxels
+        _check_nearest(dev, near, Q[-150:], k, r, sel, ident, f"nearest {sel}")
+        for surface, (got, planes) in hits.items():
+            if planes is not None:
+                _check_pooled(dev, planes, sel, leaves, f"raycast {surface} {sel}")
+            _check_raycast(dev, got, rays, sel, surface, mp, mv, planes, f"raycast {surface} {sel}")
+        for x, got in segments:
+            _check_segments(dev, got, x, gates, nodes, voxels, leaves, f"plane_segments {x}")
+
+
+def _check_queries(dev, rng, displaced, ident=None):
     from octreelib_amd.query import locate_np
     from tests.test_gpu_leaf_stats import _assert_eigen, _assert_matches_leaves
     from tests.test_gpu_query import BAD, _check_planes
 
     f, o = dev.f, dev.o
     nodes, voxels, snap = dev.fresh()
+    if displaced:
+        _check_map_queries(dev, rng, True, [None], None, dev.queries(int(rng.integers(1 << 30)), 400), ident)
     err = f.lib.octl_last_error(f.ctx.handle)
     # locate: jittered stored points, points on splitting planes, the BAD rows
     Q = dev.queries(int(rng.integers(1 << 30)), 400)
@@ -357,6 +691,8 @@ def _check_queries(dev, rng, displaced):
         _assert_eigen(st.eigenvalues, st.eigenvectors, st.covariance)
     o.node_cubes()
     assert total == sum(dev.counters(p)[2] for p in dev.poses)
+    if not displaced:
+        _check_map_queries(dev, rng, False, sels, leaves, Q, ident)
     # read-only: nothing moved, the error word did not move
     assert dev.fresh()[2] == snap
     assert f.lib.octl_last_error(f.ctx.handle) == err
@@ -387,14 +723,14 @@ def _replay(seq, observe):
                 assert_same_leaves(got[p][0], want[p][0])
                 assert got[p][1] == want[p][1], (p, got[p][1], want[p][1])
             _check_stats_value(seq, i, last_build, dev.f.nodes, *dev.f.split_stats())
-            _check_queries(dev, rng, displaced)
+            _check_queries(dev, rng, displaced, None if seq.ident is None else seq.ident[i])
         except Exception as e:      # (a library error is the likeliest symptom of a stale cache: it carries the log too)
             raise AssertionError(f"operation {i} ({'observed' if observe else 'log-only'} object): "
                                  f"{type(e).__name__}: {e}\n{seq.printed(i)}") from e
     return dev
 
 
-@pytest.mark.parametrize("seed", S.SEEDS)
+@pytest.mark.parametrize("seed", S.SEEDS + S.SEEDS2)
 def test_random_operation_sequences_vs_model(seed):
     seq = S.generate(seed)
     a = _replay(seq, observe=True)
@@ -414,3 +750,6 @@ def test_random_operation_sequences_vs_model(seed):
         assert sa[key][0] == sc[key][0], f"history changes the points of a leaf\n{seq.printed()}"
         assert sa[key][1] == sc[key][1], f"history changes the statistics of pose {key[0]}'s leaf {key[1:]}\n{seq.printed()}"
     assert pa == pc, f"history changes the pooled planes\n{seq.printed()}"
+    ma, mc = a.map_by_cube(), c.map_by_cube()
+    for key in ma:
+        assert ma[key] == mc[key], f"history changes {key}\n{seq.printed()}"
