@@ -259,7 +259,8 @@ int octl_forest_leaf_stats(octl_forest* f, const int32_t* block_ids, int64_t nb,
  * every covariance entry within 4 g R^2 of the exact value; eigenvalues within 64 * 2^-53 * |C|_F of those of the
  * returned covariance.  A leaf's bits depend on its own points and on the selection only.  The table also stays on
  * the device for octl_forest_point_to_plane, until a call changes the forest's contents or scheme (build*, add_pose*,
- * extend_pose*, apply_mask*, apply_host_mask, filter_count, set_contents, set_scheme, clear).  Read-only otherwise.
+ * extend_pose*, apply_mask*, apply_host_mask, filter_count, carve*, set_contents, set_scheme, clear).  Read-only
+ * otherwise.
  * OCTL_E_STATE before the first build.  No reference counterpart (the reference has no per-leaf statistics).        */
 int octl_forest_pooled_leaf_stats(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int64_t cap, int32_t* node,
                                   int64_t* count, double* mean, double* cov6, double* eigval, double* eigvec,
@@ -353,6 +354,52 @@ int octl_forest_raycast_device(octl_forest* f, const double* origins_dev, const 
                                const double* t_min_dev, const double* t_max_dev, int64_t n, const uint8_t* slot_sel,
                                int32_t n_sel, int32_t surface, int32_t min_points, double max_variance,
                                int32_t* node_dev, double* t_dev, int32_t* row_dev);
+/* Ray evidence per leaf: how many of n rays END in each leaf of the scheme and how many only pass THROUGH it - the
+ * free-space evidence a map is kept clean with (octl_forest_carve).  Per ray o, d (taken as given), t_min, t_free, t_end
+ * ((n,3), (n,3), (n) f64): the free interval F = [t_min, t_free] (empty when t_free < t_min) and the end interval E =
+ * [e0, t_end] with e0 = max(t_min, t_free) (empty when t_end < e0); for a measured range r and a margin m a caller
+ * passes t_free = fl(r - m), t_end = fl(r + m).  octreelib_amd/query.py: ray_evidence_np is the same by brute force
+ * over the leaves, equal count for count; all arithmetic in f64, every product, sum and quotient rounded (no fma):
+ *   dead ray   any of o, d, t_min, t_free, t_end not finite; a component with |d| > 1; every component of d zero or with
+ *              a reciprocal that is not finite.  It adds nothing; never an error;
+ *   per leaf   near, far per axis and the pass test of an axis that bounds nothing as octl_forest_raycast's interval;
+ *              near = max over the bounding axes (-inf: none), far = min (+inf: none);
+ *              in_E iff every axis passes and max(near, e0) <= min(far, t_end);
+ *              in_F iff every axis passes and max(near, t_min) <= min(far, t_free)   (both ends inclusive);
+ *   answer     hits[v] = rays with in_E, through[v] = rays with in_F and not in_E, for every node v (row of
+ *              octl_forest_get_nodes), u32; inner nodes hold 0.
+ * A function of the scheme and the rays alone: no occupancy, no pose selection, so it also answers for a forest whose
+ * rows map_leaf_points moved outside their leaves.  *n_nodes = the scheme's node count; the counters are written only
+ * when cap_nodes >= *n_nodes (size query: cap_nodes = 0).  n = 0: zeros, no kernel.  A grid caps a ray whose t are
+ * finite at max(t_free, t_end) - t_min <= 256 voxel edges and |t_min|, |max(t_free, t_end)| <= 2^40 voxel edges, as
+ * octl_forest_raycast does: OCTL_E_INVALID above it.  OCTL_E_INVALID also: n < 0 or >= 2^31, a NULL array with n > 0.
+ * OCTL_E_STATE before the first build.  Five uploads, one fill of both counters, one kernel (each ray walks every leaf
+ * it crosses once and does one u32 atomic add there), two downloads, one wait.  Read-only.  No reference counterpart. */
+int octl_forest_ray_evidence(octl_forest* f, const double* origins, const double* directions, const double* t_min,
+                             const double* t_free, const double* t_end, int64_t n, int64_t cap_nodes, uint32_t* through,
+                             uint32_t* hits, int64_t* n_nodes);
+/* The same with pointers from octl_dev_alloc: one kernel that ADDS into the caller's through_dev / hits_dev of n_nodes
+ * u32 each (OCTL_E_INVALID unless n_nodes is the scheme's node count) - the caller zeroes them, and may accumulate
+ * several scans; a counter wraps at 2^32, which is the caller's concern.  Nothing is downloaded and the host does not
+ * wait.  The cap cannot be checked without reading the rays: a ray above it adds nothing.  No reference counterpart. */
+int octl_forest_ray_evidence_device(octl_forest* f, const double* origins_dev, const double* directions_dev,
+                                    const double* t_min_dev, const double* t_free_dev, const double* t_end_dev,
+                                    int64_t n, uint32_t* through_dev, uint32_t* hits_dev, int64_t n_nodes);
+/* Remove what rays saw through: every (leaf, pose) block of a pose with slot_sel[slot] != 0 (NULL: every pose; otherwise
+ * n_sel = number of poses) whose leaf has through[node] >= min_through and hits[node] <= max_hits loses all its points
+ * (octreelib_amd/query.py: carve_keep_np is the rule; through, hits: n_nodes u32 each, the counters of
+ * octl_forest_ray_evidence - evidence belongs to the scheme it was taken on).  The blocks are cleared in the mask and
+ * the mask is applied as octl_forest_filter_count applies its own: a pending RANSAC mask goes into the same ONE
+ * compaction.  The scheme stays; *n_alive (nullable) = points left in the leaf-ordered arrays.  OCTL_E_INVALID: n_nodes
+ * is not the scheme's node count, a NULL counter array, a selection of the wrong length, min_through < 1, max_hits < 0.
+ * OCTL_E_STATE before the first build.  Two uploads, one kernel, the compaction.  No reference counterpart.          */
+int octl_forest_carve(octl_forest* f, const uint32_t* through, const uint32_t* hits, int64_t n_nodes,
+                      const uint8_t* slot_sel, int32_t n_sel, int64_t min_through, int64_t max_hits, int64_t* n_alive);
+/* The same with the counters in device memory (pointers from octl_dev_alloc, as octl_forest_ray_evidence_device left
+ * them: nothing is downloaded).  No reference counterpart.                                                          */
+int octl_forest_carve_device(octl_forest* f, const uint32_t* through_dev, const uint32_t* hits_dev, int64_t n_nodes,
+                             const uint8_t* slot_sel, int32_t n_sel, int64_t min_through, int64_t max_hits,
+                             int64_t* n_alive);
 /* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
  * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
  * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in

@@ -742,6 +742,111 @@ class Forest:
                                                            t_max_dptr, int(n), nat.ptr(sel), n_sel, code, min_points, mv,
                                                            node_dptr, t_dptr, row_dptr))
 
+    def n_scheme_nodes(self) -> int:
+        """Rows of the node table (the length of a RayEvidence)."""
+        self.ensure_built()
+        n = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_ray_evidence(self.handle, None, None, None, None, None, 0, 0, None, None,
+                                                         C.byref(n)))
+        return n.value
+
+    def _evidence_args(self, origins, directions, ranges, margin, min_range, returned):
+        from octreelib_amd.query import check_evidence_cap, evidence_inputs
+
+        o, d, tmin, tfree, tend = evidence_inputs(origins, directions, ranges, margin, min_range, returned)
+        if self.mode == 0:
+            check_evidence_cap(tmin, tfree, tend, float(self._cube[1]))
+        return o, d, tmin, tfree, tend
+
+    def ray_evidence(self, origins, directions, ranges, margin, min_range=0.0, returned=None):
+        """Rays ending in / passing through every node (octl_forest_ray_evidence: one fill, one kernel, one host
+        wait): a query.RayEvidence as query.ray_evidence_np defines it on the inputs of query.evidence_inputs."""
+        from octreelib_amd.query import RayEvidence
+
+        o, d, tmin, tfree, tend = self._evidence_args(origins, directions, ranges, margin, min_range, returned)
+        N = self.n_scheme_nodes()
+        through, hits = np.zeros(N, dtype=np.uint32), np.zeros(N, dtype=np.uint32)
+        n = C.c_int64(0)
+        # (n = 0 still goes to the library: what it refuses whatever the rays is refused for no rays too)
+        self.ctx.check(self.lib.octl_forest_ray_evidence(self.handle, nat.ptr(o), nat.ptr(d), nat.ptr(tmin),
+                                                         nat.ptr(tfree), nat.ptr(tend), len(o), N, nat.ptr(through),
+                                                         nat.ptr(hits), C.byref(n)))
+        return RayEvidence(through, hits)
+
+    def ray_evidence_device(self, origins_dptr, directions_dptr, t_min_dptr, t_free_dptr, t_end_dptr, n: int,
+                            through_dptr, hits_dptr, n_nodes: int):
+        """ray_evidence for rays that are in device memory already (pointers from octl_dev_alloc; the directions as
+        the kernel is to see them, t_min, t_free, t_end one per ray): ADDS into the caller's n_nodes u32 counters;
+        enqueued on the context's stream, the host does not wait.  A ray above a grid's cap adds nothing."""
+        self.ensure_built()
+        self.ctx.check(self.lib.octl_forest_ray_evidence_device(self.handle, origins_dptr, directions_dptr, t_min_dptr,
+                                                                t_free_dptr, t_end_dptr, int(n), through_dptr,
+                                                                hits_dptr, int(n_nodes)))
+
+    def _carved(self, call, slots, min_through, max_hits) -> int:
+        """Run one of the two carve entries; the number of points removed."""
+        from octreelib_amd.query import check_carve_args
+
+        min_through, max_hits = check_carve_args(min_through, max_hits)
+        self.ensure_built()
+        before = self.n_ord
+        sel, n_sel, _ = self._adjust_selection(slots)
+        n = C.c_int64(0)
+        self.ctx.check(call(nat.ptr(sel), n_sel, min_through, max_hits, C.byref(n)))
+        self.n_ord = n.value
+        self._invalidate()
+        return before - n.value
+
+    def carve(self, evidence, min_through: int = 2, max_hits: int = 0, slots=None) -> int:
+        """Empty every (leaf, pose) block of `slots` (None: all) whose leaf at least min_through rays passed through
+        and at most max_hits ended in (octl_forest_carve: two uploads, one kernel, one compaction that also applies a
+        pending RANSAC mask); the scheme stays.  Returns the number of points removed."""
+        self.ensure_built()
+        N = self.n_scheme_nodes()
+        if len(evidence) != N:
+            raise ValueError(f"carve: evidence over {len(evidence)} nodes, the map has {N} (evidence belongs to the "
+                             f"scheme it was taken on)")
+        through = np.ascontiguousarray(evidence.through, dtype=np.uint32)
+        hits = np.ascontiguousarray(evidence.hits, dtype=np.uint32)
+        return self._carved(lambda *a: self.lib.octl_forest_carve(self.handle, nat.ptr(through), nat.ptr(hits), N, *a),
+                            slots, min_through, max_hits)
+
+    def carve_device(self, through_dptr, hits_dptr, n_nodes: int, min_through: int = 2, max_hits: int = 0,
+                     slots=None) -> int:
+        """carve with the counters where ray_evidence_device left them."""
+        return self._carved(lambda *a: self.lib.octl_forest_carve_device(self.handle, through_dptr, hits_dptr,
+                                                                         int(n_nodes), *a),
+                            slots, min_through, max_hits)
+
+    def carve_rays(self, origins, directions, ranges, margin, min_range=0.0, returned=None, min_through: int = 2,
+                   max_hits: int = 0, slots=None) -> int:
+        """ray_evidence + carve through the device forms: the rays are uploaded once, the counters never leave the
+        device.  Returns the number of points removed."""
+        from octreelib_amd.query import check_carve_args
+
+        check_carve_args(min_through, max_hits)
+        o, d, tmin, tfree, tend = self._evidence_args(origins, directions, ranges, margin, min_range, returned)
+        N, n = self.n_scheme_nodes(), len(o)
+        lib, h = self.lib, self.ctx.handle
+        rays = np.ascontiguousarray(np.concatenate([o.reshape(-1), d.reshape(-1), tmin, tfree, tend]))
+        buf, cnt = C.c_void_p(), C.c_void_p()
+        self.ctx.check(lib.octl_dev_alloc(h, max(rays.nbytes, 8), C.byref(buf)))
+        try:
+            self.ctx.check(lib.octl_dev_alloc(h, max(8 * N, 8), C.byref(cnt)))
+            zeros = np.zeros(2 * N, dtype=np.uint32)
+            if N:
+                self.ctx.check(lib.octl_dev_upload(h, cnt, nat.ptr(zeros), zeros.nbytes))
+            if n:
+                self.ctx.check(lib.octl_dev_upload(h, buf, nat.ptr(rays), rays.nbytes))
+            at = lambda k: C.c_void_p(buf.value + 8 * k)
+            through_d, hits_d = cnt, C.c_void_p(cnt.value + 4 * N)
+            self.ray_evidence_device(buf, at(3 * n), at(6 * n), at(7 * n), at(8 * n), n, through_d, hits_d, N)
+            return self.carve_device(through_d, hits_d, N, min_through, max_hits, slots)
+        finally:
+            lib.octl_dev_free(h, buf)
+            if cnt.value:
+                lib.octl_dev_free(h, cnt)
+
     def plane_segments(self, slots=None, min_points: int = 8, max_variance=None, max_angle: float = 0.1,
                        max_offset: float = 0.05):
         """The rows of leaf_planes(slots) merged across leaf faces into connected coplanar segments

@@ -96,6 +96,10 @@ SIGNATURES = {
     "octl_forest_nearest_device": (C.c_int, [_p, _p, _i64, _i32, _f64, _p, _i32, _p, _p, _p, _p]),
     "octl_forest_raycast": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i32, _i32, _i32, _f64, _p, _p, _p]),
     "octl_forest_raycast_device": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i32, _i32, _i32, _f64, _p, _p, _p]),
+    "octl_forest_ray_evidence": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _pi64]),
+    "octl_forest_ray_evidence_device": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64]),
+    "octl_forest_carve": (C.c_int, [_p, _p, _p, _i64, _p, _i32, _i64, _i64, _pi64]),
+    "octl_forest_carve_device": (C.c_int, [_p, _p, _p, _i64, _p, _i32, _i64, _i64, _pi64]),
     "octl_forest_plane_segments": (C.c_int, [_p, _p, _i32, _i32, _f64, _f64, _f64, _i64, _i64, _p, _p, _p, _p, _p, _p,
                                              _p, _p, _p, _pi64, _pi64]),
     "octl_forest_registration_system": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _p, _p]),

@@ -1,5 +1,5 @@
 // apply_mask: the stream compaction of the leaf-ordered arrays and of the block table by the RANSAC mask (or a
-// filter's / the caller's mask), its asynchronous form and the C entries around the mask.
+// filter's / carve's / the caller's mask), its asynchronous form and the C entries around the mask.
 #include "forest.h"
 #include "lookback.h"
 
@@ -297,6 +297,26 @@ __global__ __launch_bounds__(256) void k_filter_blocks(const uint32_t* __restric
   for (int64_t i = threadIdx.x & 63; i < n; i += 64) mask[s0 + i] = 0;
 }
 
+// octl_forest_carve: a (leaf, pose) block of a selected pose (slot_sel nullptr: every pose) whose leaf at least
+// min_through rays passed through and at most max_hits rays ended in (the counters of octl_forest_ray_evidence, one
+// pair per node) is emptied - query.py: carve_keep_np is the rule.  One wavefront per block clears its mask bytes.
+__global__ __launch_bounds__(256) void k_carve_blocks(const uint32_t* __restrict__ blk_start,
+                                                      const int32_t* __restrict__ blk_size,
+                                                      const int32_t* __restrict__ blk_slot,
+                                                      const int32_t* __restrict__ blk_node, int64_t nb,
+                                                      const uint8_t* __restrict__ slot_sel,
+                                                      const uint32_t* __restrict__ through,
+                                                      const uint32_t* __restrict__ hits, int64_t min_through,
+                                                      int64_t max_hits, uint8_t* __restrict__ mask) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= nb) return;
+  if (slot_sel && !slot_sel[blk_slot[b]]) return;
+  const int32_t node = blk_node[b];
+  if (!((int64_t)through[node] >= min_through && (int64_t)hits[node] <= max_hits)) return;
+  const int64_t n = blk_size[b], s0 = blk_start[b];
+  for (int64_t i = threadIdx.x & 63; i < n; i += 64) mask[s0 + i] = 0;
+}
+
 // The block table describes the leaf-ordered arrays exactly (every producer leaves it that way), so both
 // are compacted together: points tile-wise, blocks block-wise.  One synchronisation (kept points, blocks).
 // (async: return behind the last launch - forest_settle books the counts when somebody looks at the forest again)
@@ -396,6 +416,59 @@ int apply_device_mask(octl_forest* f, int64_t* n_alive_out, bool async = false) 
   return OCTL_OK;
 }
 
+// both forms of octl_forest_carve: the refusals, the counters (uploaded into f->q_stage by the host form), the blocks
+// cleared in the mask - a pending RANSAC mask stays in it, as with octl_forest_filter_count - and ONE compaction
+int forest_carve(octl_forest* f, const uint32_t* through, const uint32_t* hits, bool on_device, int64_t n_nodes,
+                 const uint8_t* slot_sel, int32_t n_sel, int64_t min_through, int64_t max_hits, int64_t* n_alive) {
+  OCTL_TRY(forest_settle(f));
+  octl_ctx* ctx = f->ctx;
+  if (!f->built) return octl_set_error(ctx, OCTL_E_STATE, "carve before build");
+  const int64_t N = f->nodes[f->cur].n;
+  if (n_nodes != N)
+    return octl_set_error(ctx, OCTL_E_INVALID,
+                          "carve: counters for %lld nodes, the scheme has %lld (evidence belongs to the scheme it "
+                          "was taken on)",
+                          (long long)n_nodes, (long long)N);
+  if (N > 0 && (!through || !hits)) return octl_set_error(ctx, OCTL_E_INVALID, "bad carve arguments");
+  if (min_through < 1)
+    return octl_set_error(ctx, OCTL_E_INVALID, "carve: min_through = %lld is below 1", (long long)min_through);
+  if (max_hits < 0)
+    return octl_set_error(ctx, OCTL_E_INVALID, "carve: max_hits = %lld is negative", (long long)max_hits);
+  std::vector<uint8_t> sel;
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (f->n_blocks > 0) {
+    // (every buffer first: a failed allocation leaves the mask as it was)
+    if (!on_device) OCTL_TRY(devbuf_reserve(ctx, f->q_stage, (size_t)N * 8));
+    if (!sel.empty()) OCTL_TRY(devbuf_reserve(ctx, f->scheme_dev, sel.size()));
+    OCTL_TRY(ensure_mask(f));
+    if (!on_device) {
+      uint32_t* c_d = f->q_stage.as<uint32_t>();
+      HIP_TRY(ctx, hipMemcpyAsync(c_d, through, (size_t)N * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(c_d + N, hits, (size_t)N * 4, hipMemcpyHostToDevice, st));
+      through = c_d;
+      hits = c_d + N;
+    } else {
+      OCTL_TRY(ctx_wait_uploads(ctx, through, (size_t)N * 4));
+      OCTL_TRY(ctx_wait_uploads(ctx, hits, (size_t)N * 4));
+    }
+    if (!sel.empty())
+      HIP_TRY(ctx, hipMemcpyAsync(f->scheme_dev.p, sel.data(), sel.size(), hipMemcpyHostToDevice, st));
+    if (!on_device || !sel.empty()) HIP_TRY(ctx, hipStreamSynchronize(st));  // (pageable sources)
+    KTimer t(ctx, "carve");
+    OCTL_LAUNCH(k_carve_blocks, dim3((unsigned)ceil_div(f->n_blocks, 4)), dim3(256), 0, st,
+                (const uint32_t*)f->blk_start.as<uint32_t>(), (const int32_t*)f->blk_size.as<int32_t>(),
+                (const int32_t*)f->blk_slot.as<int32_t>(), (const int32_t*)f->blk_node.as<int32_t>(), f->n_blocks,
+                sel.empty() ? (const uint8_t*)nullptr : (const uint8_t*)f->scheme_dev.as<uint8_t>(), through, hits,
+                min_through, max_hits, f->mask.as<uint8_t>());
+    HIP_TRY(ctx, hipGetLastError());
+  } else {
+    OCTL_TRY(ensure_mask(f));
+  }
+  return apply_device_mask(f, n_alive);
+}
+
 }  // namespace
 
 int forest_settle(octl_forest* f) {
@@ -492,6 +565,20 @@ int octl_forest_filter_count(octl_forest* f, const uint8_t* slot_sel, int32_t n_
     HIP_TRY(ctx, hipGetLastError());
   }
   return apply_device_mask(f, n_alive);
+}
+
+int octl_forest_carve(octl_forest* f, const uint32_t* through, const uint32_t* hits, int64_t n_nodes,
+                      const uint8_t* slot_sel, int32_t n_sel, int64_t min_through, int64_t max_hits,
+                      int64_t* n_alive) {
+  if (!f) return OCTL_E_INVALID;
+  return forest_carve(f, through, hits, false, n_nodes, slot_sel, n_sel, min_through, max_hits, n_alive);
+}
+
+int octl_forest_carve_device(octl_forest* f, const uint32_t* through_dev, const uint32_t* hits_dev, int64_t n_nodes,
+                             const uint8_t* slot_sel, int32_t n_sel, int64_t min_through, int64_t max_hits,
+                             int64_t* n_alive) {
+  if (!f) return OCTL_E_INVALID;
+  return forest_carve(f, through_dev, hits_dev, true, n_nodes, slot_sel, n_sel, min_through, max_hits, n_alive);
 }
 
 int octl_forest_apply_host_mask(octl_forest* f, const uint8_t* mask, int64_t n, int64_t* n_alive) {

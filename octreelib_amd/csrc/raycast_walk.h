@@ -1,6 +1,8 @@
 // One ray against the scheme: the traversal of octl_forest_raycast (raycast.hip states the definition, DESIGN.md 4.14
-// the argument).  __host__ __device__, so that a stand-alone host program can run the very code of the kernel over
-// tables it reads from a file (tests/host/raycast_host.cpp: a CPU build under the sanitizers, compared with raycast_np).
+// the argument) and, further down, that of octl_forest_ray_evidence (evidence.hip).  __host__
+// __device__, so that a stand-alone host program can run the very code of the kernel over tables it reads from a file
+// (tests/host/raycast_host.cpp, tests/host/evidence_host.cpp: CPU builds under the sanitizers, compared with raycast_np
+// and ray_evidence_np).
 #pragma once
 #include <cmath>
 
@@ -130,6 +132,20 @@ __host__ __device__ __forceinline__ void ray_walk(const RayTables& T, const Ray&
   }
 }
 
+// The voxels along an axis that can hold a crossed leaf while t runs over [ta, tb]: a crossed leaf has
+// near <= t_out <= tb and far >= t_in >= ta, which bounds its faces by the ray's positions at ta and tb up to a
+// few roundings of (|o| + |t d| + L) 2^-53 each - of the interval arithmetic, of the positions formed here, and
+// of the leaf's faces against its voxel's (ray_box); the range is taken 2^-45 of that wide, and the slack being
+// strictly larger than the error keeps the voxel below a face the ray only touches.  (Shared by the two marches below;
+// in scope where it is used: o3, d3 = the ray's origin and direction, L, wmin, wmax = the window of voxel indices.)
+#define RAY_RANGE(a, ta, tb, first, last)                                                 \
+  do {                                                                                    \
+    const double pa = o3[a] + (ta) * d3[a], pb = o3[a] + (tb) * d3[a];                    \
+    const double sg = 0x1p-45 * (((fabs(o3[a]) + fabs((ta) * d3[a])) + fabs((tb) * d3[a])) + L); \
+    first = fmax(floor_div_exact(fmin(pa, pb) - sg, L), wmin[a]);                         \
+    last = fmin(floor_div_exact(fmax(pa, pb) + sg, L), wmax[a]);                          \
+  } while (0)
+
 // what the ray o + t d, t_min <= t <= t_max hits first (node -1, t +inf, row -1: nothing, or a dead ray)
 template <bool PLANE>
 __host__ __device__ __forceinline__ RayBest ray_cast(const RayTables& T, const double* __restrict__ o,
@@ -170,18 +186,6 @@ __host__ __device__ __forceinline__ RayBest ray_cast(const RayTables& T, const d
       wmin[a] = fmax(-(double)OCTL_VOX_ABS_LIMIT + 1.0, (double)g3[a] - (double)OCTL_VOX_BIAS + 1.0);
       wmax[a] = fmin((double)OCTL_VOX_ABS_LIMIT - 1.0, (double)g3[a] + (double)OCTL_VOX_BIAS - 1.0);
     }
-    // The voxels along an axis that can hold a crossed leaf while t runs over [ta, tb]: a crossed leaf has
-    // near <= t_out <= tb and far >= t_in >= ta, which bounds its faces by the ray's positions at ta and tb up to a
-    // few roundings of (|o| + |t d| + L) 2^-53 each - of the interval arithmetic, of the positions formed here, and
-    // of the leaf's faces against its voxel's (ray_box); the range is taken 2^-45 of that wide, and the slack being
-    // strictly larger than the error keeps the voxel below a face the ray only touches.
-#define RAY_RANGE(a, ta, tb, first, last)                                                 \
-  do {                                                                                    \
-    const double pa = o3[a] + (ta) * d3[a], pb = o3[a] + (tb) * d3[a];                    \
-    const double sg = 0x1p-45 * (((fabs(o3[a]) + fabs((ta) * d3[a])) + fabs((tb) * d3[a])) + L); \
-    first = fmax(floor_div_exact(fmin(pa, pb) - sg, L), wmin[a]);                         \
-    last = fmin(floor_div_exact(fmax(pa, pb) + sg, L), wmax[a]);                          \
-  } while (0)
     double s_lo, s_hi;
     {
       double f0[3], f1[3];
@@ -227,7 +231,167 @@ __host__ __device__ __forceinline__ RayBest ray_cast(const RayTables& T, const d
         }
       }
     }
-#undef RAY_RANGE
   }
   return best;
 }
+
+// ---- every crossed leaf: the walk of octl_forest_ray_evidence (evidence.hip states the definition) ------------------
+// Its own march and descent.  They were first written as one template on a leaf visitor with ray_cast as a use; that
+// cost k_raycast<true> 16 VGPRs and a wave of occupancy, so ray_cast stays as it is and the two walks
+// share Ray, ray_axis, ray_box and RAY_RANGE.
+struct EvidenceTables {
+  QueryTables t;
+  const int32_t* parent;
+  int64_t max_steps;
+  uint32_t* through;  // [n_nodes] counters the walk adds into
+  uint32_t* hits;
+};
+
+// F = [t_min, t_free], E = [e0, t_end]; the walk's interval is [t_min, max(t_free, t_end)] (r.t_min, r.t_max)
+struct RayIntervals {
+  double e0, t_free, t_end;
+};
+
+// One ray adds 1 to hits[leaf] of every leaf with in_E, and to through[leaf] of every leaf with in_F and not in_E.  A
+// leaf comes here with t_in = max(near, t_min) and t_out = min(far, max(t_free, t_end)) (ray_box with w = 0), and as
+// t_min <= e0 and t_free, t_end <= the walk's end,
+//   max(near, e0) = max(t_in, e0),  min(far, t_end) = min(t_out, t_end),  min(far, t_free) = min(t_out, t_free):
+// the definition's two comparisons on the definition's bits.  An empty F or E fails its comparison by itself
+// (t_free < t_min <= max(..); t_end < e0 <= max(..)).
+__host__ __device__ __forceinline__ void evidence_leaf(const EvidenceTables& T, const RayIntervals& iv, int32_t node,
+                                                       double t_in, double t_out) {
+  const bool in_e = fmax(t_in, iv.e0) <= fmin(t_out, iv.t_end);
+  const bool in_f = t_in <= fmin(t_out, iv.t_free);
+  if (!(in_e || in_f)) return;
+  uint32_t* counter = (in_e ? T.hits : T.through) + node;
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(counter, 1u);  // (u32: the sums do not depend on the order of the rays)
+#else
+  ++*counter;
+#endif
+}
+
+// The tree under `root` in the order of ray_walk, nothing pruned by a best t: every leaf under `root` that the walk's
+// interval crosses is handed to evidence_leaf (a box that contains a crossed leaf is crossed: ray_box), and as the
+// order (child number XOR mask) is a permutation of the eight children and the walk only moves to the next sibling
+// or up, each at most once.
+__host__ __device__ __forceinline__ void evidence_walk(const EvidenceTables& T, const Ray& r, const RayIntervals& iv,
+                                                       int mask, int32_t root, int64_t& steps) {
+  const QueryTables& t = T.t;
+  int32_t node = root;
+  for (;;) {
+    if (++steps > T.max_steps) return;
+    const double cx = t.corner[3 * (int64_t)node + 0], cy = t.corner[3 * (int64_t)node + 1],
+                 cz = t.corner[3 * (int64_t)node + 2], e = t.edge[node];
+    const int32_t fc = t.first_child[node];
+    double t_in, t_out;
+    if (ray_box(r, cx, cy, cz, e, fc < 0, t_in, t_out)) {
+      if (fc >= 0) {
+        node = fc + mask;
+        continue;
+      }
+      evidence_leaf(T, iv, node, t_in, t_out);
+    }
+    for (;;) {
+      if (node == root) return;
+      const int32_t par = T.parent[node];
+      if (par < 0 || ++steps > T.max_steps) return;
+      const int32_t fcp = t.first_child[par];
+      const int rank = (node - fcp) ^ mask;
+      if (rank >= 0 && rank < 7) {
+        node = fcp + ((rank + 1) ^ mask);
+        break;
+      }
+      node = par;
+    }
+  }
+}
+
+// The evidence of one ray.  A dead ray (a value that is not finite, a component with |d| > 1, no axis that bounds
+// anything), one whose two intervals are both empty and - in grid mode - one above the cap add nothing.
+//
+// Every leaf at most ONCE per ray, or it would count double: the march is ray_cast's, and its slabs are one voxel
+// thick along the major axis m - lo[m] = hi[m] = sv, and sv differs from slab to slab - while the three loops of a
+// slab enumerate distinct (vx, vy, vz).  So no voxel is looked up twice, a voxel has one root (the keys are distinct),
+// and evidence_walk hands a leaf under a root over at most once.  (A leaf on a voxel wall that the ray runs along
+// belongs to ONE voxel, however many slabs and ranges the wall touches.)
+__host__ __device__ __forceinline__ void ray_evidence(const EvidenceTables& T, const double* __restrict__ o,
+                                                      const double* __restrict__ d, double t_min, double t_free,
+                                                      double t_end) {
+  const double INF = HUGE_VAL;
+  const QueryTables& t = T.t;
+  Ray r;
+  r.ox = o[0], r.oy = o[1], r.oz = o[2];
+  r.dx = d[0], r.dy = d[1], r.dz = d[2];
+  r.t_min = t_min, r.t_max = fmax(t_free, t_end);
+  r.ix = 1.0 / r.dx, r.iy = 1.0 / r.dy, r.iz = 1.0 / r.dz;
+  r.zx = r.dx == 0.0 || !(fabs(r.ix) < INF);
+  r.zy = r.dy == 0.0 || !(fabs(r.iy) < INF);
+  r.zz = r.dz == 0.0 || !(fabs(r.iz) < INF);
+  const RayIntervals iv = {fmax(t_min, t_free), t_free, t_end};
+  // (every comparison is false for NaN; fmax drops one, so t_free and t_end are tested one by one)
+  bool live = fabs(r.ox) < INF && fabs(r.oy) < INF && fabs(r.oz) < INF && fabs(r.dx) <= 1.0 && fabs(r.dy) <= 1.0 &&
+              fabs(r.dz) <= 1.0 && fabs(t_min) < INF && fabs(t_free) < INF && fabs(t_end) < INF &&
+              r.t_min <= r.t_max && !(r.zx && r.zy && r.zz) && t.V > 0;
+  const int mask = (r.dx < 0.0 ? 4 : 0) | (r.dy < 0.0 ? 2 : 0) | (r.dz < 0.0 ? 1 : 0);
+  int64_t steps = 0;
+  if (live && t.mode != 0) {
+    evidence_walk(T, r, iv, mask, 0, steps);
+  } else if (live && r.t_max - r.t_min <= RAY_CAP_EDGES * t.L && fabs(r.t_min) <= RAY_T_LIMIT * t.L &&
+             fabs(r.t_max) <= RAY_T_LIMIT * t.L) {
+    // (a ray above the cap is refused by the host form; here it adds nothing)
+    const double L = t.L;
+    const double adx = fabs(r.dx), ady = fabs(r.dy), adz = fabs(r.dz);
+    const int m = (adx >= ady && adx >= adz) ? 0 : (ady >= adz ? 1 : 2);
+    const double om = m == 0 ? r.ox : m == 1 ? r.oy : r.oz, dm = m == 0 ? r.dx : m == 1 ? r.dy : r.dz;
+    const double im = m == 0 ? r.ix : m == 1 ? r.iy : r.iz;
+    const double o3[3] = {r.ox, r.oy, r.oz}, d3[3] = {r.dx, r.dy, r.dz};
+    const int32_t g3[3] = {t.org.x, t.org.y, t.org.z};
+    double wmin[3], wmax[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      wmin[a] = fmax(-(double)OCTL_VOX_ABS_LIMIT + 1.0, (double)g3[a] - (double)OCTL_VOX_BIAS + 1.0);
+      wmax[a] = fmin((double)OCTL_VOX_ABS_LIMIT - 1.0, (double)g3[a] + (double)OCTL_VOX_BIAS - 1.0);
+    }
+    double s_lo, s_hi;
+    {
+      double f0[3], f1[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) RAY_RANGE(a, r.t_min, r.t_max, f0[a], f1[a]);
+      s_lo = m == 0 ? f0[0] : m == 1 ? f0[1] : f0[2];
+      s_hi = m == 0 ? f1[0] : m == 1 ? f1[1] : f1[2];
+    }
+    // (at most 256 + 3 slabs; the bound guards the loop whatever the arithmetic did)
+    const int64_t n_slabs = s_lo <= s_hi ? (int64_t)fmin(s_hi - s_lo + 1.0, RAY_CAP_EDGES + 8.0) : 0;
+    for (int64_t k = 0; k < n_slabs; ++k) {
+      const double sv = s_lo + (double)k;  // (any order: nothing ends the march early)
+      const double base = sv * L, dl = 0x1p-45 * (fabs(base) + L);
+      const double f_lo = base - dl, f_hi = (base + L) + dl;
+      const double te = ((dm > 0.0 ? f_lo : f_hi) - om) * im, tx = ((dm > 0.0 ? f_hi : f_lo) - om) * im;
+      const double ta = fmax(te, r.t_min), tb = fmin(tx, r.t_max);
+      if (!(ta <= tb)) continue;
+      double lo[3], hi[3];
+      bool any = true;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        RAY_RANGE(a, ta, tb, lo[a], hi[a]);
+        if (a == m) lo[a] = hi[a] = sv;
+        any = any && lo[a] <= hi[a];
+      }
+      if (!any) continue;
+      const int64_t x0 = (int64_t)lo[0], x1 = (int64_t)fmin(hi[0], lo[0] + 7.0);
+      const int64_t y0 = (int64_t)lo[1], y1 = (int64_t)fmin(hi[1], lo[1] + 7.0);
+      const int64_t z0 = (int64_t)lo[2], z1 = (int64_t)fmin(hi[2], lo[2] + 7.0);
+      for (int64_t vx = x0; vx <= x1; ++vx) {
+        for (int64_t vy = y0; vy <= y1; ++vy) {
+          const uint64_t code1 = vkey_pack(vx, vy, z1, t.org);
+          for (int64_t rr = lower_bound_u64(t.vcode, t.V, vkey_pack(vx, vy, z0, t.org)); rr < t.V; ++rr) {
+            if (t.vcode[rr] > code1) break;
+            evidence_walk(T, r, iv, mask, (int32_t)rr, steps);
+          }
+        }
+      }
+    }
+  }
+}
+#undef RAY_RANGE

@@ -18,7 +18,7 @@ from octreelib_amd.criteria import try_count_threshold, try_planar_threshold
 from octreelib_amd.grid.grid_base import GridBase, GridConfigBase, VisualizationConfig
 from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
-from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane, RayHits
+from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane, RayEvidence, RayHits
 from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
@@ -163,6 +163,49 @@ class Grid(GridBase):
             return self._host_map().raycast(origins, directions, max_range, min_range=min_range, pose_numbers=sel,
                                             surface=surface, min_points=min_points, max_variance=max_variance)
         return self._forest.raycast(origins, directions, max_range, min_range, sel, surface, min_points, max_variance)
+
+    def ray_evidence(self, origins, directions, ranges, margin, min_range=0.0, returned=None) -> RayEvidence:
+        """Free-space evidence of a scan: for n rays from `origins` (n, 3) along `directions` (n, 3; normalised here)
+        with measured `ranges` (scalar or (n,)), how many rays END in every leaf of the scheme and how many only pass
+        THROUGH it.  A ray is free over [min_range, range - margin] and ends in [range - margin, range + margin]
+        (margin finite and >= 0: the range noise plus what the surface may have moved); a leaf the end interval
+        crosses gets a hit, a leaf only the free interval crosses gets a through; rays with returned == False (no
+        echo) are free up to range - margin and end nowhere.  A RayEvidence (through, hits (n_nodes,) uint32 over the
+        rows of node_cubes(); `+` adds the evidence of two scans; .free(min_through, max_hits) the nodes carve would
+        empty).  The scheme and the rays alone decide - no occupancy, no pose selection; a dead ray (a value that is
+        not finite) adds nothing.  One kernel (octreelib_amd/query.py: ray_evidence_np is the definition, count for
+        count).  ValueError for shapes that do not fit, a bad margin, a ray that spans more than 256 voxel edges."""
+        if self._plug is not None:
+            return self._host_map().ray_evidence(origins, directions, ranges, margin, min_range, returned)
+        return self._forest.ray_evidence(origins, directions, ranges, margin, min_range, returned)
+
+    def carve(self, evidence: RayEvidence, min_through: int = 2, max_hits: int = 0,
+              pose_numbers: Optional[List[int]] = None) -> int:
+        """Remove what rays saw through: every leaf of the given poses (None: all) that at least min_through rays
+        passed through and at most max_hits rays ended in loses its points of those poses - things that have moved
+        away since the poses were taken.  Evidence belongs to the scheme it was taken on (ray_evidence of this map as
+        it is subdivided now; several scans summed with `+`).  The scheme stays, a pending RANSAC mask is applied in
+        the same compaction, every cached table is dropped.  Returns the number of points removed.  ValueError when
+        the evidence is not over this map's nodes, min_through < 1 or max_hits < 0; KeyError for an unknown pose;
+        NotImplementedError on the caller's own plug types."""
+        if self._plug is not None:
+            raise NotImplementedError(
+                "carve removes points of the device-resident map: a Grid on the caller's own plug types keeps its "
+                "points in those types on the host, and there is no host path for them")
+        sel = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+        return self._forest.carve(evidence, min_through, max_hits, sel)
+
+    def carve_rays(self, origins, directions, ranges, margin, min_range=0.0, returned=None, min_through: int = 2,
+                   max_hits: int = 0, pose_numbers: Optional[List[int]] = None) -> int:
+        """carve(ray_evidence(...)) in one go on the device: the counters are never downloaded.  Returns the number
+        of points removed."""
+        if self._plug is not None:
+            raise NotImplementedError(
+                "carve_rays removes points of the device-resident map: a Grid on the caller's own plug types keeps "
+                "its points in those types on the host, and there is no host path for them")
+        sel = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+        return self._forest.carve_rays(origins, directions, ranges, margin, min_range, returned, min_through,
+                                       max_hits, sel)
 
     def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
         """One least-squares plane per leaf over the given poses (None: all), all their points pooled: a LeafPlanes in

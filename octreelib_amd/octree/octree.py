@@ -115,6 +115,25 @@ class Octree(OctreeBase, Generic[T]):
         self._query_ready()
         return self._forest.raycast(origins, directions, max_range, min_range, None, surface, min_points, max_variance)
 
+    def ray_evidence(self, origins, directions, ranges, margin, min_range=0.0, returned=None):
+        """How many rays end in every leaf and how many only pass through it (a RayEvidence; Grid.ray_evidence
+        describes it).  One cube has no cap on the range."""
+        self._query_ready()
+        return self._forest.ray_evidence(origins, directions, ranges, margin, min_range, returned)
+
+    def carve(self, evidence, min_through: int = 2, max_hits: int = 0) -> int:
+        """Empty every leaf that at least min_through rays passed through and at most max_hits ended in (Grid.carve
+        describes it; evidence belongs to the scheme it was taken on).  Returns the number of points removed."""
+        self._query_ready()
+        return self._forest.carve(evidence, min_through, max_hits, None)
+
+    def carve_rays(self, origins, directions, ranges, margin, min_range=0.0, returned=None, min_through: int = 2,
+                   max_hits: int = 0) -> int:
+        """carve(ray_evidence(...)) in one go on the device.  Returns the number of points removed."""
+        self._query_ready()
+        return self._forest.carve_rays(origins, directions, ranges, margin, min_range, returned, min_through,
+                                       max_hits, None)
+
     def leaf_planes(self):
         """One least-squares plane per non-empty leaf, in ascending node id (a LeafPlanes)."""
         self._query_ready()

@@ -4,10 +4,12 @@ over a set of poses (leaf_planes) and the signed distance of a point to the plan
 the inner loop of scan-to-map registration and of every plane-factor residual.
 
 Further down: the stored points nearest to a point (nearest), the leaves merged into plane segments (plane_segments)
-and what a ray hits first (raycast).
+what a ray hits first (raycast), and the leaves rays end in or pass through (ray_evidence; carve removes what
+rays saw through).
 
 Grid / OctreeManager / Octree answer them on the device (octl_forest_locate, octl_forest_pooled_leaf_stats,
-octl_forest_point_to_plane, octl_forest_nearest, octl_forest_plane_segments, octl_forest_raycast).  The functions of this module are the same on the host in NumPy: they are the
+octl_forest_point_to_plane, octl_forest_nearest, octl_forest_plane_segments, octl_forest_raycast,
+octl_forest_ray_evidence, octl_forest_carve).  The functions of this module are the same on the host in NumPy: they are the
 specification, the higher-precision reference of the tests, and what the classes built on the caller's own plug types
 use, so that the whole feature also runs, slowly, without a GPU.
 """
@@ -24,7 +26,7 @@ from octreelib_amd.leaf_stats import LeafStatistics, cov6_to_full, leaf_statisti
 __all__ = ["LeafPlanes", "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np",
            "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K", "PlaneSegments",
            "SegmentTable", "plane_segments_np", "segment_probes_np", "RayHits", "raycast_np", "normalize_directions",
-           "RAY_CAP_EDGES"]
+           "RAY_CAP_EDGES", "RayEvidence", "ray_evidence_np", "carve_keep_np", "evidence_inputs"]
 
 VOX_ABS_LIMIT = 1 << 30   # absolute voxel indices travel as int32
 NN_MAX_K = 8              # OCTL_NN_MAX_K: the largest k of nearest()
@@ -422,6 +424,150 @@ def raycast_np(origins, directions, t_max, node, corner, edge, *, t_min=0.0, cou
 
 
 @dataclass
+class RayEvidence:
+    """Answer of ray_evidence: per node of the scheme (the rows of node_cubes()), how many rays ended in it and how
+    many only passed through it.  Inner nodes hold 0.  Evidence belongs to the scheme it was taken on."""
+
+    through: np.ndarray   # (n_nodes,) uint32 rays whose free interval crosses the leaf and whose end interval does not
+    hits: np.ndarray      # (n_nodes,) uint32 rays whose end interval crosses the leaf
+
+    def __len__(self):
+        return len(self.through)
+
+    def __add__(self, other: "RayEvidence") -> "RayEvidence":
+        """The evidence of both sets of rays (several scans over one scheme); a counter wraps at 2^32."""
+        if not isinstance(other, RayEvidence):
+            return NotImplemented
+        if len(other) != len(self):
+            raise ValueError(f"evidence over {len(self)} nodes + evidence over {len(other)} nodes")
+        return RayEvidence(self.through + other.through, self.hits + other.hits)
+
+    def free(self, min_through: int = 2, max_hits: int = 0) -> np.ndarray:
+        """(n_nodes,) bool: at least min_through rays passed through the node and at most max_hits ended in it - the
+        nodes carve empties."""
+        min_through, max_hits = check_carve_args(min_through, max_hits)
+        return (self.through.astype(np.int64) >= min_through) & (self.hits.astype(np.int64) <= max_hits)
+
+
+def check_carve_args(min_through, max_hits):
+    """(min_through, max_hits) as ints; ValueError for min_through < 1 or max_hits < 0."""
+    for name, v, least in (("min_through", min_through, 1), ("max_hits", max_hits, 0)):
+        if isinstance(v, bool) or int(v) != v or int(v) < least:
+            raise ValueError(f"carve: {name} = {v!r} is not an integer >= {least}")
+    return int(min_through), int(max_hits)
+
+
+def evidence_inputs(origins, directions, ranges, margin, min_range=0.0, returned=None):
+    """(origins, directions, t_min, t_free, t_end) as ray_evidence_np and the device take them, from what a scan gives:
+    the directions normalised (normalize_directions), t_min = min_range, t_free = ranges - margin and t_end = ranges +
+    margin, each rounded once (ranges, min_range: scalars or (n,)); a ray with returned == False (no echo: free up to
+    ranges - margin, ending nowhere) gets the empty end interval t_end = nextafter(max(t_min, t_free), -inf).
+    ValueError for shapes that do not fit or a margin that is not finite and >= 0."""
+    m = float(margin)
+    if not (np.isfinite(m) and m >= 0.0):
+        raise ValueError(f"ray_evidence: margin must be finite and not negative, got {margin!r}")
+    o, d, tmin, r = ray_inputs(origins, normalize_directions(directions), min_range, ranges)
+    with np.errstate(invalid="ignore", over="ignore"):
+        tfree, tend = r - m, r + m
+        if returned is not None:
+            ret = np.asarray(returned, dtype=bool)
+            if ret.shape != (len(o),):
+                raise ValueError(f"ray_evidence: returned must be of shape ({len(o)},), got {ret.shape}")
+            tend = np.where(ret, tend, np.nextafter(np.maximum(tmin, tfree), -np.inf))
+    return o, d, tmin, np.ascontiguousarray(tfree), np.ascontiguousarray(tend)
+
+
+def check_evidence_cap(t_min, t_free, t_end, edge: float):
+    """check_raycast_cap over the interval a ray of ray_evidence walks, [t_min, max(t_free, t_end)]."""
+    with np.errstate(invalid="ignore"):
+        # (np.maximum keeps a NaN: such a ray is dead and is not checked)
+        check_raycast_cap(t_min, np.maximum(t_free, t_end), edge)
+
+
+def ray_evidence_np(origins, directions, t_min, t_free, t_end, node, corner, edge, n_nodes: int,
+                    chunk: int = 128) -> RayEvidence:
+    """Which leaves every ray o + t d ends in and which it only passes through, by brute force over the leaves: the
+    definition of ray_evidence.  The directions are taken as given.  Leaves: node (m,) ids, corner (m, 3), edge (m,);
+    n_nodes: the length of the answer (ids index it).  All arithmetic in float64, every product, sum and quotient
+    rounded, in the order of raycast_np:
+
+    dead ray   any of o, d, t_min, t_free, t_end not finite; a component with |d| > 1; every component of d zero or
+               with a reciprocal that is not finite.  It contributes nothing;
+    intervals  free F = [t_min, t_free], empty when t_free < t_min; end E = [e0, t_end] with e0 = max(t_min, t_free),
+               empty when t_end < e0;
+    per leaf   lo = corner, hi = corner + edge; near / far per axis and the pass test of an axis that bounds nothing
+               as raycast_np's interval; near = max over the bounding axes (-inf: none), far = min (+inf: none);
+               in_E iff every axis passes, E is not empty and max(near, e0) <= min(far, t_end);
+               in_F iff every axis passes, F is not empty and max(near, t_min) <= min(far, t_free) (ends inclusive);
+    answer     hits[v] = number of rays with in_E, through[v] = number with in_F and not in_E; nodes that are not
+               among the leaves hold 0.  No occupancy and no pose selection enter."""
+    o, d = _as_queries(origins), _as_queries(directions)
+    n = len(o)
+    if len(d) != n:
+        raise ValueError(f"ray_evidence: {n} origins for {len(d)} directions")
+    ts = []
+    for name, v in (("t_min", t_min), ("t_free", t_free), ("t_end", t_end)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n, float(a))
+        elif a.shape != (n,):
+            raise ValueError(f"ray_evidence: {name} must be a scalar or of shape ({n},), got {a.shape}")
+        ts.append(a)
+    tmin, tfree, tend = ts
+    node = np.asarray(node, dtype=np.int64).reshape(-1)
+    lo = np.asarray(corner, dtype=np.float64).reshape(-1, 3)
+    e = np.asarray(edge, dtype=np.float64).reshape(-1)
+    if not len(node) == len(lo) == len(e):
+        raise ValueError("ray_evidence_np: node, corner and edge describe different numbers of leaves")
+    through, hits = np.zeros(int(n_nodes), dtype=np.int64), np.zeros(int(n_nodes), dtype=np.int64)
+    m = len(node)
+    if n and m:
+        hi = lo + e[:, None]
+        with np.errstate(all="ignore"):
+            inv = 1.0 / d
+            zero = (d == 0.0) | ~np.isfinite(inv)
+            dead = ~(np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1) & np.isfinite(tmin) & np.isfinite(tfree)
+                     & np.isfinite(tend))
+            dead |= zero.all(axis=1) | ~(np.abs(d) <= 1.0).all(axis=1)
+            for a0 in range(0, n, chunk):
+                live = np.nonzero(~dead[a0: a0 + chunk])[0] + a0
+                if len(live) == 0:
+                    continue
+                oc, ic, zc = o[live], inv[live], zero[live]
+                near = np.full((len(live), m), -np.inf)
+                far = np.full((len(live), m), np.inf)
+                ok = np.ones((len(live), m), dtype=bool)
+                for a in range(3):
+                    oa, ia, za = oc[:, a, None], np.where(zc[:, a], 1.0, ic[:, a])[:, None], zc[:, a, None]
+                    ta = (lo[None, :, a] - oa) * ia
+                    tb = (hi[None, :, a] - oa) * ia
+                    near = np.maximum(near, np.where(za, -np.inf, np.minimum(ta, tb)))
+                    far = np.minimum(far, np.where(za, np.inf, np.maximum(ta, tb)))
+                    ok &= ~za | ((lo[None, :, a] <= oa) & (oa <= hi[None, :, a]))
+                a_, f_, z_ = tmin[live][:, None], tfree[live][:, None], tend[live][:, None]
+                e0 = np.maximum(a_, f_)
+                in_e = ok & (e0 <= z_) & (np.maximum(near, e0) <= np.minimum(far, z_))
+                in_f = ok & (a_ <= f_) & (np.maximum(near, a_) <= np.minimum(far, f_))
+                hits[node] += in_e.sum(axis=0)
+                through[node] += (in_f & ~in_e).sum(axis=0)
+    return RayEvidence(through.astype(np.uint32), hits.astype(np.uint32))
+
+
+def carve_keep_np(blk_node, blk_slot, through, hits, slot_sel=None, min_through: int = 2,
+                  max_hits: int = 0) -> np.ndarray:
+    """The rule of carve: one bool per (leaf, pose) block of a block table (blk_node, blk_slot), False = the block is
+    emptied.  A block is emptied iff its slot is selected (slot_sel: one flag per slot, None: every slot) and
+    through[node] >= min_through and hits[node] <= max_hits."""
+    min_through, max_hits = check_carve_args(min_through, max_hits)
+    bn = np.asarray(blk_node, dtype=np.int64).reshape(-1)
+    bs = np.asarray(blk_slot, dtype=np.int64).reshape(-1)
+    chosen = np.ones(len(bs), dtype=bool) if slot_sel is None else np.asarray(slot_sel).astype(bool)[bs]
+    t = np.asarray(through).astype(np.int64)[bn]
+    h = np.asarray(hits).astype(np.int64)[bn]
+    return ~(chosen & (t >= min_through) & (h <= max_hits))
+
+
+@dataclass
 class SegmentTable(LeafStatistics):
     """LeafStatistics of the plane segments, merged from the moments of their leaves; row s describes segment s."""
 
@@ -708,6 +854,16 @@ class HostMap:
             planes = self.leaf_planes(pose_numbers)
         return raycast_np(o, d, tmax, leaf, corner, edge, t_min=tmin, count=count, planes=planes, surface=surface,
                           min_points=min_points, max_variance=max_variance)
+
+    def ray_evidence(self, origins, directions, ranges, margin, min_range=0.0, returned=None) -> RayEvidence:
+        """ray_evidence_np over the leaves of the node table: the inputs as evidence_inputs makes them, the grid's
+        cap checked."""
+        o, d, tmin, tfree, tend = evidence_inputs(origins, directions, ranges, margin, min_range, returned)
+        if self.mode == 0:
+            check_evidence_cap(tmin, tfree, tend, self.edge)
+        leaf = np.nonzero(np.asarray(self.nodes["first_child"]) < 0)[0]
+        return ray_evidence_np(o, d, tmin, tfree, tend, leaf, self.nodes["corner"][leaf], self.nodes["edge"][leaf],
+                               len(self.nodes["edge"]))
 
     def plane_segments(self, pose_numbers=None, min_points=8, max_variance=None, max_angle=0.1,
                        max_offset=0.05) -> PlaneSegments:
