@@ -264,7 +264,12 @@ __device__ __forceinline__ double plane_distance(double a, double b, double c, d
 }
 
 // launch shapes (A/B history of every number: HISTORY.md 4 and 8)
-constexpr int RS_MINWAVES = 4;         // waves per SIMD asked of the compiler
+// waves per SIMD asked of the compiler.  Five for the one-wave instances with a compile-time sample size: 96 VGPRs
+// (512 per lane and SIMD, allocated in eights) and 7 680 B of LDS - 21 workgroups per CU by the runtime's occupancy
+// query - which they reach without scratch (round 9: the next block's point parked in LDS, block-uniform vector
+// constants made where they are used, the survivor list in an idle s_loc buffer; HISTORY.md 12).  The generic-k
+// one-wave instance spills at 128 already and stays at four, like every instance of two and four waves.
+constexpr int rs_minwaves(int threads, int kt) { return threads == 64 && kt > 0 ? 5 : 4; }
 constexpr int RS_BIG_PER_CU = 16;      // workgroups per CU striding over the list of large blocks
 constexpr int RS_BIG_THREADS = 256;    // H > 256: lanes per workgroup of the instance for blocks of 128 .. 255 points
 constexpr int RS_BIG_HPL = 1024 / RS_BIG_THREADS;
@@ -498,14 +503,14 @@ __device__ __forceinline__ float wave_max_nonneg_f32(float m) {
 // block-local f32 coordinates of the point a lane is staging (relative to the block's first
 // point, loaded wave-uniformly by the caller well ahead of this call) and the per-wave maximum of their magnitudes
 template <int THREADS>
-__device__ __forceinline__ void stage_local(double ox, double oy, double oz, const BlockDesc& d,
+__device__ __forceinline__ void stage_local(unsigned tx, double ox, double oy, double oz, const BlockDesc& d,
                                             double px, double py, double pz, f4* loc,
                                             float* wext, uint32_t* wfast, float* ext_out = nullptr,
                                             uint32_t* fast_out = nullptr) {
   float m = 0.f;
-  if ((int)threadIdx.x < d.n) {
+  if ((int)tx < d.n) {
     const float u = (float)(px - ox), v = (float)(py - oy), w = (float)(pz - oz);
-    loc[threadIdx.x] = f4{u, v, w, 0.f};
+    loc[tx] = f4{u, v, w, 0.f};
     m = fmaxf(fabsf(u), fmaxf(fabsf(v), fabsf(w)));
     // a NaN coordinate would be dropped by fmaxf: force "everything is ambiguous" instead
     if (!(m == m) || u != u || v != v || w != w) m = __int_as_float(0x7f800000);
@@ -517,9 +522,9 @@ __device__ __forceinline__ void stage_local(double ox, double oy, double oz, con
   if (ext_out) {  // (one wave per block: the two words stay in the wave's registers)
     *ext_out = m;
     *fast_out = wave_fast ? 1u : 0u;
-  } else if ((threadIdx.x & 63) == 0) {
-    wext[threadIdx.x >> 6] = m;
-    wfast[threadIdx.x >> 6] = wave_fast ? 1u : 0u;
+  } else if ((tx & 63) == 0) {
+    wext[tx >> 6] = m;
+    wfast[tx >> 6] = wave_fast ? 1u : 0u;
   }
 }
 
@@ -705,11 +710,12 @@ __device__ unsigned long long g_rs_stamps[RS_NSTAMPS];
 
 // Persistent workgroups over the descriptors of all blocks with k <= n <= THREADS-1 points,
 // SORTED BY SIZE (largest first): workgroup w handles a contiguous chunk of the list
-//   * the grid is oversubscribed (64 ... 256 workgroups per CU, 4 ... 16 resident): the chunks with the largest
+//   * the grid is oversubscribed (64 ... 256 workgroups per CU, 4 ... 20 resident): the chunks with the largest
 //     blocks are dispatched first and the dispatcher evens out the rest (no tail);
 //   * while entry e is computed out of one LDS buffer the points of entry e+1 are already in
 //     flight into registers and the descriptor of entry e+2 is being fetched, so the per-block
-//     latency chain (descriptor -> points) is off the critical path;
+//     latency chain (descriptor -> points) is off the critical path (the one-wave prescreen instances issue the
+//     load behind the exact fit of group 0 and park the point in LDS behind the prescreen: PARK below);
 //   * the block's points are three f64 LDS arrays: the sampled points of a hypothesis are
 //     per-lane LDS gathers (conflict free up to 32 points), the scoring loop reads each point as
 //     a wave-uniform broadcast;
@@ -720,7 +726,7 @@ __device__ unsigned long long g_rs_stamps[RS_NSTAMPS];
 // PT: the sample positions - a function of (block size, hypothesis) alone, see sample_index_cached - come from the
 // launch's position table (pos_table_part: k <= 6); otherwise they are computed from the table row in front of a fit.
 template <int THREADS, int HPL, int KT, bool FULLH, bool PT>
-__global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
+__global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
     const double* __restrict__ xyz, const BlockDesc* __restrict__ sdesc,
     const uint32_t* __restrict__ lo_ptr, const uint32_t* __restrict__ hi_ptr, const double* __restrict__ hyp, int H,
     int k_rt, double thr, RansacOut out, const uint2* __restrict__ pos_tab, int no_prescreen) {
@@ -732,13 +738,23 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
   // every later one): no exchange between the waves before the block's one barrier.
   constexpr bool PRE = PT && KT >= 3 && HPL >= 2;
   constexpr int W = THREADS / 64;
+  constexpr bool PARK = PRE && W == 1;   // the next block's prefetched point is parked in LDS (see `park` below)
   constexpr int KS = KT > 0 ? KT : RS_KMAX;
   constexpr int GW = (KS + 3) / 4;  // packed sample positions: one byte each
   // survivors a wave can queue (more: every hypothesis takes the exact path); an entry is the hypothesis index, and
   // with one wave per block (under 64 points) its count bound above it
   constexpr int PRE_LIST = THREADS == 64 ? 512 : 256;
-  __shared__ uint16_t s_surv_all[PRE ? W : 1][PRE ? PRE_LIST : 1];
-  uint16_t* const s_surv = s_surv_all[PRE ? (threadIdx.x >> 6) : 0];
+  // (one wave per block: the list has no LDS of its own - it lies in the s_loc buffer of the NEXT block, idle until
+  //  that block is staged behind the last survivor, as the ring of the two-stage count lies in the idle s_pts buffers.
+  //  With it the one-wave instances are at 7 680 B.  Plain uint16_t on purpose: through a may_alias type the
+  //  compiler keeps the wave-uniform counters of the queues in scratch; a wavefront fence in front of the staging
+  //  orders the list's reads against the f4 stores instead.  The other end: s_loc[nbuf] of block t was `third` of
+  //  block t-1, read there as the f4 copy `ploc`; the block's barrier - __syncthreads, also with one wave - is what
+  //  keeps those reads in front of this block's 16-bit stores.  Whoever moves or drops it for W == 1 orders these too.
+  //  A full list ends on the buffer's last two bytes: `pos < PRE_LIST` guards the live buffers behind it)
+  constexpr bool OWN_LIST = PRE && W > 1;
+  __shared__ uint16_t s_surv_all[OWN_LIST ? W : 1][OWN_LIST ? PRE_LIST : 1];
+  uint16_t* const s_surv_own = s_surv_all[OWN_LIST ? (threadIdx.x >> 6) : 0];
   const int k = KT > 0 ? KT : k_rt;
   __shared__ double s_pts[3][3][THREADS];        // rotated: block t lives in buffer t % 3
   __shared__ uint32_t s_wbest[2][W];             // by block parity
@@ -746,6 +762,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
   // f32 screening of the scoring loop (see "screening" below): block-local f32 coordinates
   // relative to the block's first point and, per wave, the largest |coordinate|
   __shared__ f4 s_loc[3][THREADS];
+  static_assert(!(PRE && W == 1) || PRE_LIST * sizeof(uint16_t) <= sizeof(s_loc[0]), "the survivor list fits an s_loc buffer");
   __shared__ float s_wext[3][W];
   __shared__ uint32_t s_wfast[3][W];
   // this launch's part [lo, hi) of the size-sorted list (device-side counts; lo_ptr == nullptr: from the front)
@@ -774,7 +791,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
       s_pts[0][1][threadIdx.x] = py;
       s_pts[0][2][threadIdx.x] = pz;
     }
-    stage_local<THREADS>(xyz[3 * (int64_t)cur.pstart], xyz[3 * (int64_t)cur.pstart + 1],
+    stage_local<THREADS>(threadIdx.x, xyz[3 * (int64_t)cur.pstart], xyz[3 * (int64_t)cur.pstart + 1],
                          xyz[3 * (int64_t)cur.pstart + 2], cur, px, py, pz, s_loc[0], s_wext[0], s_wfast[0],
                          W == 1 ? &ext_carry : nullptr, W == 1 ? &fast_carry : nullptr);
   }
@@ -793,20 +810,43 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
     if (j + 2 < j_end) nxt2 = sdesc[j + 2];
     // points of the next block -> registers (in flight during the compute below)
     double rx = 0.0, ry = 0.0, rz = 0.0;
-    const bool pre = has_next && (int)tx <= nxt.n;
-    if (pre) {
-      const int64_t p = ((int)tx < nxt.n) ? (int64_t)nxt.pstart + tx : (int64_t)nxt.pspill;
-      rx = xyz[3 * p];
-      ry = xyz[3 * p + 1];
-      rz = xyz[3 * p + 2];
-    }
+    // (PARK: a lane mask held from here to the staging is two scalar registers more to spill; each use makes its own)
+    auto pre_here = [&]() {
+      unsigned t = tx;
+      if constexpr (PARK) asm volatile("" : "+v"(t));
+      return has_next && (int)t <= nxt.n;
+    };
+    const int nbuf = buf == 2 ? 0 : buf + 1;
+    uint16_t* const s_surv = PARK ? (uint16_t*)&s_loc[nbuf][0] : s_surv_own;
+    auto prefetch = [&]() {
+      if (pre_here()) {
+        const int64_t p = ((int)tx < nxt.n) ? (int64_t)nxt.pstart + tx : (int64_t)nxt.pspill;
+        rx = xyz[3 * p];
+        ry = xyz[3 * p + 1];
+        rz = xyz[3 * p + 2];
+      }
+    };
+    // PARK (the one-wave prescreen instances): six registers held from here to the end of the block are what keeps
+    // the instance from a fifth wave per SIMD.  The load is issued behind the exact fit of group 0 instead - the
+    // block's register peak - and the point leaves the registers for its place in s_pts[nbuf] as soon as the prescreen
+    // has drained its ring there, in front of the exact fits of the survivors; the staging reads it back.
+    auto park = [&]() {
+      if (pre_here()) {
+        s_pts[nbuf][0][tx] = rx;
+        s_pts[nbuf][1][tx] = ry;
+        s_pts[nbuf][2][tx] = rz;
+      }
+    };
     // ... and its first point, the origin of its block-local coordinates: a wave-uniform load whose latency
-    // used to sit in front of the staging at the END of the iteration
+    // used to sit in front of the staging at the END of the iteration (PARK: read back from s_pts[nbuf] there)
     double nox = 0.0, noy = 0.0, noz = 0.0;
-    if (has_next) {
-      nox = xyz[3 * (int64_t)nxt.pstart];
-      noy = xyz[3 * (int64_t)nxt.pstart + 1];
-      noz = xyz[3 * (int64_t)nxt.pstart + 2];
+    if constexpr (!PARK) {
+      prefetch();
+      if (has_next) {
+        nox = xyz[3 * (int64_t)nxt.pstart];
+        noy = xyz[3 * (int64_t)nxt.pstart + 1];
+        noz = xyz[3 * (int64_t)nxt.pstart + 2];
+      }
     }
     const int n = cur.n;
     const int be = (int)cur.pad[1];
@@ -839,7 +879,6 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
     // Early exit (exact).  The winner is the LOWEST index among the hypotheses with the maximal
     // count, and no count exceeds n.  Hypotheses 0 .. THREADS-1 (group 0) go first; when one of them holds
     // all n points, no later hypothesis can win - on the benchmark scene this is one leaf in five.
-    const double ox = lx[0], oy = ly[0], oz = lz[0];
     float extent = W == 1 ? ext_carry : s_wext[buf][0];
 #pragma unroll
     for (int w = 1; w < W; ++w) extent = fmaxf(extent, s_wext[buf][w]);
@@ -851,17 +890,40 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
     const bool blk_fast = __builtin_amdgcn_readfirstlane((int)fastw) != 0;
     // block-uniform parts of the bound.  Thresholds or extents outside the sane range (nobody's
     // plane tolerance) are always recounted exactly.
-    const double delta_blk = fma(0x1p-23 * 9.0, (double)extent,
-                                 0x1p-49 * (fabs(ox) + fabs(oy) + fabs(oz) + (double)extent + 1.0));
-    const double dprime_thr = 0x1p-21 * (thr * thr);
     const bool blk_sane = thr >= 0x1p-40 && thr <= 0x1p40 && extent < 0x1p60f;
-    const float nthr2 = -(float)(thr * thr);
-    const f4* __restrict__ loc = s_loc[buf];
-    // f32 forms of the bound's block-uniform parts, rounded up
     const bool fast_screen = blk_fast && thr >= 0x1p-40 && thr <= 0x1p40;
-    const float delta_blk_f = (float)delta_blk * 0x1.0002p0f;
-    const float thr2_f = (float)(thr + thr) * 0x1.0002p0f;
-    const float dprime_thr_f = (float)dprime_thr * 0x1.0002p0f;
+    const f4* __restrict__ loc = s_loc[buf];
+    struct BlkConst {
+      double ox, oy, oz;     // the block's first point
+      double delta_blk, dprime_thr, thr2;
+      float nthr2;
+      float delta_blk_f, thr2_f, dprime_thr_f;   // f32 forms of the bound's block-uniform parts, rounded up
+    };
+    // PARK: these are wave-uniform values in VECTOR registers (f64 and conversions have no scalar form), a dozen of
+    // them, and left alone they live through the prescreen - or, the threshold's, hoisted out of the block loop, through
+    // the kernel.  They are cheap: every fit and every count makes its own from an opaque copy of the threshold and a
+    // fresh broadcast read of the first point (a dozen instructions in front of a fit of two hundred and fifty).
+    auto blk_consts = [&]() {
+      double th = thr;
+      if constexpr (PARK) asm volatile("" : "+s"(th));
+      BlkConst c;
+      c.ox = lx[0]; c.oy = ly[0]; c.oz = lz[0];
+      c.delta_blk = fma(0x1p-23 * 9.0, (double)extent,
+                        0x1p-49 * (fabs(c.ox) + fabs(c.oy) + fabs(c.oz) + (double)extent + 1.0));
+      c.dprime_thr = 0x1p-21 * (th * th);
+      c.thr2 = th + th;
+      c.nthr2 = -(float)(th * th);
+      c.delta_blk_f = (float)c.delta_blk * 0x1.0002p0f;
+      c.thr2_f = (float)(th + th) * 0x1.0002p0f;
+      c.dprime_thr_f = (float)c.dprime_thr * 0x1.0002p0f;
+      return c;
+    };
+    const BlkConst bc0 = blk_consts();
+    auto consts_here = [&]() {
+      if constexpr (PARK) return blk_consts();
+      else return bc0;
+    };
+    const double ox = bc0.ox, oy = bc0.oy, oz = bc0.oz;
 
     // ---- one hypothesis per lane, exactly: positions, plane fit, count --------------------------------------------
     uint32_t gpk[GW], rk = 0;     // packed sample positions of the lane's hypothesis and their risky-draw bits
@@ -895,6 +957,9 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
       cnt = 0;
       fa = fb = fc = fd = sto = sdl = 0.f;
       if (FULLH || act) {
+        const BlkConst bc = consts_here();
+        const double ox = bc.ox, oy = bc.oy, oz = bc.oz, delta_blk = bc.delta_blk, dprime_thr = bc.dprime_thr;
+        const float delta_blk_f = bc.delta_blk_f, thr2_f = bc.thr2_f, dprime_thr_f = bc.dprime_thr_f;
         double sx[KS], sy[KS], sz[KS];
         // does any lane of this wave hold a draw that needs the block's start (probability 2^-20
         // per draw)?  Otherwise the gathers skip the per-sample check.
@@ -937,7 +1002,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
           sdl = fma32(dl, thr2_f + dl, dprime_thr_f) * 0x1.0002p0f;
         } else {
           const double delta = fma(0x1p-21, fabs(to), fma(0x1p-49, fabs(D), delta_blk));
-          const double dprime = fma(delta, thr + thr + delta, dprime_thr) * 1.000001;
+          const double dprime = fma(delta, bc.thr2 + delta, dprime_thr) * 1.000001;
           const bool sane = blk_sane && (fabs(to) < 0x1p60);  // false for NaN
           sdl = sane ? (float)dprime : __int_as_float(0x7f800000);
         }
@@ -949,7 +1014,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
       int c1[1] = {0};
       RS_COUNT(14, 1);
       RS_COUNT(15, n);
-      screen_group<1>(loc, n, &fa, &fb, &fc, &sto, nthr2, c1, margin);
+      screen_group<1>(loc, n, &fa, &fb, &fc, &sto, consts_here().nthr2, c1, margin);
       cnt = c1[0];
       // a hypothesis whose smallest |e| does not clear its bound is recounted exactly, by the whole wavefront
       // for one flagged lane at a time (almost always exactly one): its plane is broadcast, every lane tests one
@@ -994,6 +1059,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
       const bool act = FULLH || t < H;
       load_pos(t, act);
       fit(t, act);
+      if constexpr (PARK) prefetch();
       score(act);
       take(t, act);
     }
@@ -1051,7 +1117,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
                 const bool mine = (int)tx < n;
                 const f4 Lp = loc[mine ? tx : 0];
                 const float sv = fma32(A, Lp.x, fma32(B, Lp.y, fma32(Cc, Lp.z, To)));
-                const bool far = mine && !(fma32(sv, sv, nthr2) < 0.f);
+                const bool far = mine && !(fma32(sv, sv, consts_here().nthr2) < 0.f);
                 const unsigned long long mf = __ballot(far), mn = __ballot(mine && !far);
                 const unsigned long long mm = far ? mf : mn;
                 const int pos = (far ? 0 : __popcll(mf)) +
@@ -1222,6 +1288,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         }
+        if constexpr (PARK) park();
         // ---- the survivors (in index order) - or, without a prescreen, groups 1 .. HPL-1 - exactly ------------------
         const int nbatch = use_list ? ((S + 63) >> 6) : HPL - 1;
 #pragma unroll 1
@@ -1250,6 +1317,7 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
         }
       } else {
         RS_COUNT(9, 1);
+        if constexpr (PARK) park();
       }
     }
     const uint32_t wbest = wave_max_u32(best);
@@ -1278,14 +1346,24 @@ __global__ __launch_bounds__(THREADS, RS_MINWAVES) void k_ransac(
     // stage the next block.  Its buffer, (t+1) % 3, was last read for block t-2: every wave has
     // passed the barrier of block t-1 since.  The reduction slots alternate by parity for the
     // same reason, so ONE barrier per block publishes both the reduction and the staged points.
-    const int nbuf = buf == 2 ? 0 : buf + 1;
-    if (pre) {
-      s_pts[nbuf][0][tx] = rx;
-      s_pts[nbuf][1][tx] = ry;
-      s_pts[nbuf][2][tx] = rz;
+    if constexpr (PARK) {
+      // (the survivor list in s_loc[nbuf] has been read as 16-bit words: nothing of the staging moves in front of that)
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (pre_here()) {
+        rx = s_pts[nbuf][0][tx];
+        ry = s_pts[nbuf][1][tx];
+        rz = s_pts[nbuf][2][tx];
+      }
+      if (has_next) {   // (k >= 1: lane 0 parked the block's first point)
+        nox = s_pts[nbuf][0][0];
+        noy = s_pts[nbuf][1][0];
+        noz = s_pts[nbuf][2][0];
+      }
+    } else {
+      park();
     }
     if (has_next)
-      stage_local<THREADS>(nox, noy, noz, nxt, rx, ry, rz, s_loc[nbuf], s_wext[nbuf], s_wfast[nbuf],
+      stage_local<THREADS>(tx, nox, noy, noz, nxt, rx, ry, rz, s_loc[nbuf], s_wext[nbuf], s_wfast[nbuf],
                            W == 1 ? &ext_carry : nullptr, W == 1 ? &fast_carry : nullptr);
     __syncthreads();
     if constexpr (W > 1) {

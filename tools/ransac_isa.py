@@ -62,7 +62,7 @@ L = {
     "screen_group": line_of(r"^__device__ __forceinline__ void screen_group"),
     "prescreen_const": line_of(r"^struct PreConst"),
     "screen_ub": line_of(r"^__device__ __forceinline__ void screen_ub"),
-    "kernel": line_of(r"^__global__ __launch_bounds__\(THREADS, RS_MINWAVES\) void k_ransac"),
+    "kernel": line_of(r"^__global__ __launch_bounds__\(THREADS, (RS_MINWAVES|rs_minwaves\(THREADS, KT\))\) void k_ransac"),
 }
 L["shared_begin"] = line_of(r"^typedef float f4 ")
 L["stage_local"] = line_of(r"^__device__ __forceinline__ void stage_local")
