@@ -34,6 +34,7 @@
 
 #include "forest.h"
 #include "lookback.h"
+#include "plane_cert.h"
 #include "wave_utils.h"
 
 namespace {
@@ -500,9 +501,29 @@ __device__ __forceinline__ float wave_max_nonneg_f32(float m) {
   return __uint_as_float(wave_max_u32(__float_as_uint(m)));
 }
 
+// Sum of an f64 over the wavefront, the same six DPP steps (a lane the row mask leaves out adds +0.0); a tree, so six
+// roundings per sum.  Wave-uniform result.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_f64_or_zero(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  v += dpp_f64_or_zero<0xB1, 0xF>(v);
+  v += dpp_f64_or_zero<0x4E, 0xF>(v);
+  v += dpp_f64_or_zero<0x141, 0xF>(v);
+  v += dpp_f64_or_zero<0x140, 0xF>(v);
+  v += dpp_f64_or_zero<0x142, 0xA>(v);
+  v += dpp_f64_or_zero<0x143, 0xC>(v);
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
+                          __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+
 // block-local f32 coordinates of the point a lane is staging (relative to the block's first
 // point, loaded wave-uniformly by the caller well ahead of this call) and the per-wave maximum of their magnitudes
-template <int THREADS>
+// (SFAST: the one-wave prescreen instances, at their register limit, keep the carried range word in a scalar register)
+template <int THREADS, bool SFAST = false>
 __device__ __forceinline__ void stage_local(unsigned tx, double ox, double oy, double oz, const BlockDesc& d,
                                             double px, double py, double pz, f4* loc,
                                             float* wext, uint32_t* wfast, float* ext_out = nullptr,
@@ -521,7 +542,7 @@ __device__ __forceinline__ void stage_local(unsigned tx, double ox, double oy, d
   const bool wave_fast = __all(inr);
   if (ext_out) {  // (one wave per block: the two words stay in the wave's registers)
     *ext_out = m;
-    *fast_out = wave_fast ? 1u : 0u;
+    *fast_out = SFAST ? (uint32_t)__builtin_amdgcn_readfirstlane(wave_fast ? 1 : 0) : (wave_fast ? 1u : 0u);
   } else if ((tx & 63) == 0) {
     wext[tx >> 6] = m;
     wfast[tx >> 6] = wave_fast ? 1u : 0u;
@@ -685,11 +706,14 @@ __device__ __forceinline__ void screen_ub(const f4* __restrict__ loc, int n, con
 //   [16] (point, hypothesis) pairs of stage 1   [17] pairs of stage 2 (lanes without a queued hypothesis included)
 //   [18] hypotheses queued for stage 2   [19] prescreened blocks that took the single-stage count
 //   [20] pairs of the single-stage count   [21] stage-2 passes   [22] pairs a single-stage count of every block takes
+//   the certified exit (see "the certified exit" below):
+//   [24] blocks tested at n - L = 1   [25] ... at n - L = 2   [26] blocks certified at n - L = 1   [27] ... at n - L = 2
+//   [28] later hypotheses of certified blocks that the cross-product test sent to the exact queue
 #ifdef RS_COUNTS
-constexpr int RS_NSTAMPS = 24;
+constexpr int RS_NSTAMPS = 32;
 __device__ unsigned long long g_rs_stamps[RS_NSTAMPS];
 #define RS_COUNT_INIT unsigned long long _rs_acc[RS_NSTAMPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,  \
-                                                                0, 0, 0, 0, 0, 0, 0, 0};                             \
+                                                                0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     \
                       const unsigned long long _rs_m0 = __builtin_amdgcn_s_memtime(),                      \
                                                _rs_r0 = __builtin_amdgcn_s_memrealtime()
 #define RS_COUNT(k, v) _rs_acc[k] += (unsigned long long)(v)
@@ -707,6 +731,36 @@ __device__ unsigned long long g_rs_stamps[RS_NSTAMPS];
 #define RS_COUNT(k, v) do {} while (0)
 #define RS_COUNT_FLUSH do {} while (0)
 #endif
+
+// ---- the certified exit (round 10; one wave per block) -------------------------------------------------------
+// A block ends behind group 0 when a hypothesis of group 0 holds all n points.  It may end there just as well when
+// the best count L of group 0 is n - 1 or n - 2 and NO plane holds more than L of the block's points: a later
+// hypothesis wins only with a count above L (a tie goes to the lower index).  plane_cert.h decides that from the
+// scatter matrix of the block's points - nine f64 sums over the wave - for every plane whose normal has a length of
+// at least 1 - 2^-22, with t = PreConst::thrblk: the reference's test fl(|a x + b y + c z + d|) < thr on the
+// f32 plane and the global coordinates (util.py:22-24) puts the point within thr + 2^-49 G < thrblk of that plane.
+// Which hypotheses have such a normal?  The reference normalises a row of cofactors in f64 and rounds it to f32
+// (util.py:63-84, cuda_ransac.py:110-113): the length is 1 - 2^-24 - 2^-50 at least, UNLESS the row's norm is zero
+// (util.py:77-78: the zero plane, which counts every point; samples of one or two distinct points, duplicates,
+// exact cancellation - real on the benchmark scene) or so small that its square loses bits.  The row holds the
+// largest of the three diagonal cofactors as the reference computes them, so that cofactor bounds the norm from
+// below.  For k samples with residuals r_i against their centroid the three diagonal cofactors of sum r r^T add up
+// to (Lagrange; centred data)
+//      sum_{i<j} |r_i x r_j|^2 = (1 / k) sum_{i<j<l} |(p_j - p_i) x (p_l - p_i)|^2,
+// so for ANY three of the samples the largest diagonal cofactor is at least |(p1 - p0) x (p2 - p0)|^2 / (3 k),
+// 1 / 18 of it for k <= 6.  The reference's f64 arithmetic on global coordinates (T <= 72 E^2 the trace of the sums,
+// centroid off by 2^-49 G per coordinate: the sums about a centre off by d gain 6 d d^T):
+//      each covariance sum   |err| <= 9 x 2^-53 T + 6 x 2^-98 G^2         <= 2^-43 E^2 + 2^-95 G^2
+//      each cofactor         |err| <= 4 T (that) + 2^-51 T^2 (+ squares)  <= 2^-34 E^4 + 2^-86 G^2 E^2
+// The kernel forms the cross product of three sample positions in f32 on the block's local coordinates (each
+// difference good to 2^-22 E, each component of the product to 2^-18 E^2, its length to 2^-17 E^2) and vouches
+// for the hypothesis when the squared length exceeds 2^-24 E^4 + 2^-74 G^2 E^2: then the length is above 2^-12 E^2,
+// the ideal one at least (1 - 2^-5) of it, the largest ideal cofactor at least 2^-28.3 E^4 + 2^-78.3 G^2 E^2 - 50
+// times the reference's error and more - and the norm the reference divides by is above 2^-29 E^4 >= 2^-57: no
+// zero plane, no lost bits.  Everything else - fewer than three distinct positions, duplicates, nearly collinear
+// samples, a risky draw (the position table's bits 16..21) - joins the exact queue like a hypothesis the
+// prescreen does not vouch for, in index order.  A certified block builds no partition, fits no approximate plane
+// and counts nothing: tools/cert_exit_sim.py has the shares (one block in five on the benchmark scene).
 
 // Persistent workgroups over the descriptors of all blocks with k <= n <= THREADS-1 points,
 // SORTED BY SIZE (largest first): workgroup w handles a contiguous chunk of the list
@@ -791,7 +845,7 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
       s_pts[0][1][threadIdx.x] = py;
       s_pts[0][2][threadIdx.x] = pz;
     }
-    stage_local<THREADS>(threadIdx.x, xyz[3 * (int64_t)cur.pstart], xyz[3 * (int64_t)cur.pstart + 1],
+    stage_local<THREADS, PARK>(threadIdx.x, xyz[3 * (int64_t)cur.pstart], xyz[3 * (int64_t)cur.pstart + 1],
                          xyz[3 * (int64_t)cur.pstart + 2], cur, px, py, pz, s_loc[0], s_wext[0], s_wfast[0],
                          W == 1 ? &ext_carry : nullptr, W == 1 ? &fast_carry : nullptr);
   }
@@ -803,7 +857,14 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
     // threadIdx.x directly the compiler hoists them out of this loop and then SPILLS them (48 B of
     // scratch per lane, written by every workgroup: 200 MB of HBM writes per launch - measured).
     // An opaque copy of the lane index per iteration keeps them in-loop.
+    // (PARK - one wave per block, at the register limit of five waves per SIMD: the lane index is counted afresh from an
+    //  opaque zero, three instructions per block, instead of living in a register - or in scratch - through the loop)
     unsigned tx = threadIdx.x;
+    if constexpr (PARK) {
+      unsigned z = 0;
+      asm volatile("" : "+v"(z));
+      tx = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+    }
     asm volatile("" : "+v"(tx));
     const bool has_next = j + 1 < j_end;
     BlockDesc nxt2 = nxt;
@@ -1094,13 +1155,40 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
             constexpr bool TWO = THREADS == 64;
             typedef uint32_t __attribute__((may_alias)) u32a;
             const int budget = n - Lcur;
+            // ---- the certified exit (one wave per block; see "the certified exit" above k_ransac) -------------------
+            bool certified = false;
+            if constexpr (TWO) {
+              if (budget <= 2) {   // (wave-uniform; budget >= 1 here)
+                RS_COUNT(budget == 1 ? 24 : 25, 1);
+                const bool mine = (int)tx < n;
+                // the lane's point relative to the block's first (lanes without a point: the first point itself, 0);
+                // read again wherever it is needed, and one reduction after the other: nine interleaved chains and
+                // three coordinates held across them are what would raise the instance's register peak
+                auto rel = [&](const double* __restrict__ l) { return l[mine ? tx : 0u] - l[0]; };
+                double sum[9];
+#pragma unroll
+                for (int q = 0; q < 9; ++q) {
+                  // q: x y z xx xy xz yy yz zz
+                  const double* __restrict__ la = q < 3 ? (q == 0 ? lx : q == 1 ? ly : lz) : (q < 6 ? lx : q < 8 ? ly : lz);
+                  const double* __restrict__ lb = (q == 3) ? lx : (q == 4 || q == 6) ? ly : lz;
+                  sum[q] = wave_sum_f64(q < 3 ? rel(la) : rel(la) * rel(lb));
+                  __builtin_amdgcn_sched_barrier(0);
+                }
+                const plane_cert::Scatter sc = plane_cert::scatter_from_sums(n, sum[0], sum[1], sum[2], sum[3], sum[4],
+                                                                             sum[5], sum[6], sum[7], sum[8]);
+                const double t = (double)pc.thrblk;
+                if (budget == 1) certified = plane_cert::no_plane_holds_all(sc, n, t);
+                else certified = __all(!mine || plane_cert::no_plane_holds_others(sc, n, rel(lx), rel(ly), rel(lz), t));
+                if (certified) RS_COUNT(budget == 1 ? 26 : 27, 1);
+              }
+            }
             int m1 = n, qhead = 0, qtail = 0;
             bool two_stage = false;
             f4* ploc = nullptr;
             u32a *qlo = nullptr, *qhi = nullptr;
             if constexpr (TWO) {
               m1 = min(n, (budget + RS_STAGE1_SLACK + 3) & ~3);
-              two_stage = n - m1 >= RS_STAGE2_MIN;
+              two_stage = !certified && n - m1 >= RS_STAGE2_MIN;   // (certified: no widened count at all)
               if (two_stage) {
                 const int third = buf == 0 ? 2 : buf - 1;
                 ploc = s_loc[third];
@@ -1124,7 +1212,7 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
                                 (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
                 if (mine) ploc[pos] = Lp;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-              } else {
+              } else if (!certified) {
                 RS_COUNT(19, 1);
               }
             }
@@ -1276,9 +1364,42 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
             };
             constexpr int PNH = 3;   // (four or five at a time: within the box-to-box noise, HISTORY 9)
             constexpr int TRIOS = (HPL - 1) / PNH, REST = (HPL - 1) % PNH;
+            if (TWO && certified) {
+              // no proper plane can beat Lcur: a later hypothesis is only fitted when its plane may be the zero plane
+              const float E = extent;
+              const float G = ((float)(fabs(lx[0]) + fabs(ly[0]) + fabs(lz[0])) + E) * 0x1.0002p0f;
+              const float E2 = E * E;
+              const float floor2 = fma32(0x1p-74f * (G * G), E2, 0x1p-24f * (E2 * E2)) * 0x1.0002p0f;
 #pragma unroll 1
-            for (int i = 0; i < TRIOS; ++i) prescreen(std::integral_constant<int, PNH>{}, 1 + PNH * i);
-            if constexpr (REST > 0) prescreen(std::integral_constant<int, (REST > 0 ? REST : 1)>{}, 1 + PNH * TRIOS);
+              for (int g = 1; g < HPL; ++g) {
+                const int t = (int)tx + g * THREADS;
+                const bool real = FULLH || t < H;
+                const uint2 e = pos_tab[(size_t)n * (size_t)H + (size_t)(real ? t : 0)];
+                uint32_t p[KS];
+#pragma unroll
+                for (int i = 0; i < KS; ++i) p[i] = ((i < 4 ? e.x : e.y) >> (8 * (i & 3))) & 0xFFu;
+                // three distinct positions among the samples, if there are three (otherwise two of these coincide)
+                uint32_t p1 = p[KS - 1], p2 = p[KS - 1];
+#pragma unroll
+                for (int i = KS - 2; i >= 1; --i) p1 = p[i] != p[0] ? p[i] : p1;
+#pragma unroll
+                for (int i = KS - 2; i >= 2; --i) p2 = (p[i] != p[0] && p[i] != p1) ? p[i] : p2;
+                // (a position n - the spill point, outside loc - comes with its risk bit: gathered from slot 0 instead)
+                const bool risky = (e.y >> 16) != 0u;
+                const f4 P0 = loc[risky ? 0u : p[0]], P1 = loc[risky ? 0u : p1], P2 = loc[risky ? 0u : p2];
+                const float ux = P1.x - P0.x, uy = P1.y - P0.y, uz = P1.z - P0.z;
+                const float vx = P2.x - P0.x, vy = P2.y - P0.y, vz = P2.z - P0.z;
+                const float cx = fma32(uy, vz, -(uz * vy)), cy = fma32(uz, vx, -(ux * vz)), cz = fma32(ux, vy, -(uy * vx));
+                const float c2 = fma32(cz, cz, fma32(cy, cy, cx * cx));
+                const bool vouched = !risky && c2 > floor2;   // (false for NaN)
+                RS_COUNT(28, __popcll(__ballot(real && !vouched)));
+                survive(real && !vouched, 63u, t);
+              }
+            } else {
+#pragma unroll 1
+              for (int i = 0; i < TRIOS; ++i) prescreen(std::integral_constant<int, PNH>{}, 1 + PNH * i);
+              if constexpr (REST > 0) prescreen(std::integral_constant<int, (REST > 0 ? REST : 1)>{}, 1 + PNH * TRIOS);
+            }
             if constexpr (TWO) {
               if (qtail != qhead) stage2(qtail - qhead);
             }
@@ -1363,7 +1484,7 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
       park();
     }
     if (has_next)
-      stage_local<THREADS>(tx, nox, noy, noz, nxt, rx, ry, rz, s_loc[nbuf], s_wext[nbuf], s_wfast[nbuf],
+      stage_local<THREADS, PARK>(tx, nox, noy, noz, nxt, rx, ry, rz, s_loc[nbuf], s_wext[nbuf], s_wfast[nbuf],
                            W == 1 ? &ext_carry : nullptr, W == 1 ? &fast_carry : nullptr);
     __syncthreads();
     if constexpr (W > 1) {

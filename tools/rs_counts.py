@@ -17,7 +17,7 @@ lib.octl_debug_rs_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 wl = bench.Workload(ctx, ctx, 0, 1, 10_000_000, (32, 32, 32), "planar", 64, False, False, n_clouds=3)
 for _ in range(3):
     wl.step()
-NW = 24   # RS_NSTAMPS of csrc/ransac.hip
+NW = 32   # RS_NSTAMPS of csrc/ransac.hip
 out = (C.c_ulonglong * NW)()
 ctx.check(lib.octl_debug_rs_stamps(ctx.handle, out, 1))
 reps = 6
@@ -58,6 +58,13 @@ res = {
     "widened_count_pairs_fraction_of_single_stage": (v[16] + v[17] + v[20]) / max(v[22], 1),
     "hypotheses_queued_for_stage_2": v[18], "fraction_prescreened_queued_for_stage_2": v[18] / max(a_groups * LANES, 1),
     "stage_2_passes": v[21], "stage_2_passes_per_two_stage_block": v[21] / max(eligible - v[19], 1),
+    # the certified exit (tools/cert_exit_sim.py predicts the same shares of the leaves of 6..63 points)
+    "cert_blocks_tested_b1": v[24], "cert_blocks_tested_b2": v[25],
+    "cert_blocks_certified_b1": v[26], "cert_blocks_certified_b2": v[27],
+    "fraction_blocks_tested_b1": v[24] / blocks, "fraction_blocks_tested_b2": v[25] / blocks,
+    "fraction_blocks_certified_b1": v[26] / blocks, "fraction_blocks_certified_b2": v[27] / blocks,
+    "cert_hypotheses_sent_to_exact_queue": v[28],
+    "cert_hypotheses_sent_to_exact_queue_per_certified_block": v[28] / max(v[26] + v[27], 1),
     "note": "average per launch over %d steps of the rotating headline workload; the instance runs one wave per block" % reps,
 }
 print(json.dumps(res, indent=1))
