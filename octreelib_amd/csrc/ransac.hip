@@ -761,6 +761,15 @@ __device__ unsigned long long g_rs_stamps[RS_NSTAMPS];
 // samples, a risky draw (the position table's bits 16..21) - joins the exact queue like a hypothesis the
 // prescreen does not vouch for, in index order.  A certified block builds no partition, fits no approximate plane
 // and counts nothing: tools/cert_exit_sim.py has the shares (one block in five on the benchmark scene).
+// Which three positions the cross product takes is a function of (block size, hypothesis) alone, like the positions
+// themselves: pos_table_entry works them out once per launch, for the sizes of the one-wave instance, into a second
+// table of one word per (size, hypothesis) behind the position table's 256 sizes - three byte offsets into the
+// block's f4 points, 10 bits each, and TRIO_FLAG where the hypothesis cannot be vouched for whatever the points are.
+constexpr uint32_t TRIO_FLAG = 0x80000000u;
+// (the entry's index in the position table seen as 32-bit words: 512 H words of positions in front, 32 bits are enough)
+__device__ __forceinline__ uint32_t trio_word(int n, int H, int t) {
+  return (512u + (uint32_t)n) * (uint32_t)H + (uint32_t)t;
+}
 
 // Persistent workgroups over the descriptors of all blocks with k <= n <= THREADS-1 points,
 // SORTED BY SIZE (largest first): workgroup w handles a contiguous chunk of the list
@@ -1370,28 +1379,27 @@ __global__ __launch_bounds__(THREADS, rs_minwaves(THREADS, KT)) void k_ransac(
               const float G = ((float)(fabs(lx[0]) + fabs(ly[0]) + fabs(lz[0])) + E) * 0x1.0002p0f;
               const float E2 = E * E;
               const float floor2 = fma32(0x1p-74f * (G * G), E2, 0x1p-24f * (E2 * E2)) * 0x1.0002p0f;
+              // three distinct sample positions of the lane's hypothesis, as byte offsets into loc: the entry at trio_word,
+              // read one group ahead (a flagged entry - a risky draw, fewer than three distinct positions - has offsets 0)
+              const uint32_t* __restrict__ trio = reinterpret_cast<const uint32_t*>(pos_tab) + trio_word(n, H, 0);
+              auto trio_of = [&](int g) {
+                const int t = (int)tx + g * THREADS;
+                return trio[(FULLH || t < H) ? t : 0];
+              };
+              auto at = [&](uint32_t off) { return *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(loc) + off); };
+              uint32_t e_next = trio_of(1);
 #pragma unroll 1
               for (int g = 1; g < HPL; ++g) {
                 const int t = (int)tx + g * THREADS;
                 const bool real = FULLH || t < H;
-                const uint2 e = pos_tab[(size_t)n * (size_t)H + (size_t)(real ? t : 0)];
-                uint32_t p[KS];
-#pragma unroll
-                for (int i = 0; i < KS; ++i) p[i] = ((i < 4 ? e.x : e.y) >> (8 * (i & 3))) & 0xFFu;
-                // three distinct positions among the samples, if there are three (otherwise two of these coincide)
-                uint32_t p1 = p[KS - 1], p2 = p[KS - 1];
-#pragma unroll
-                for (int i = KS - 2; i >= 1; --i) p1 = p[i] != p[0] ? p[i] : p1;
-#pragma unroll
-                for (int i = KS - 2; i >= 2; --i) p2 = (p[i] != p[0] && p[i] != p1) ? p[i] : p2;
-                // (a position n - the spill point, outside loc - comes with its risk bit: gathered from slot 0 instead)
-                const bool risky = (e.y >> 16) != 0u;
-                const f4 P0 = loc[risky ? 0u : p[0]], P1 = loc[risky ? 0u : p1], P2 = loc[risky ? 0u : p2];
+                const uint32_t e = e_next;
+                e_next = trio_of(g + 1 < HPL ? g + 1 : g);   // (the last group once more: no branch)
+                const f4 P0 = at(e & 0x3F0u), P1 = at((e >> 10) & 0x3F0u), P2 = at((e >> 20) & 0x3F0u);
                 const float ux = P1.x - P0.x, uy = P1.y - P0.y, uz = P1.z - P0.z;
                 const float vx = P2.x - P0.x, vy = P2.y - P0.y, vz = P2.z - P0.z;
                 const float cx = fma32(uy, vz, -(uz * vy)), cy = fma32(uz, vx, -(ux * vz)), cz = fma32(ux, vy, -(uy * vx));
                 const float c2 = fma32(cz, cz, fma32(cy, cy, cx * cx));
-                const bool vouched = !risky && c2 > floor2;   // (false for NaN)
+                const bool vouched = !(e & TRIO_FLAG) && c2 > floor2;   // (false for NaN)
                 RS_COUNT(28, __popcll(__ballot(real && !vouched)));
                 survive(real && !vouched, 63u, t);
               }
@@ -1896,6 +1904,18 @@ __device__ __forceinline__ void pos_table_entry(const double* __restrict__ hyp, 
     y |= (risky || g == (uint32_t)n) ? (0x10000u << i) : 0u;
   }
   tab[(size_t)n * (size_t)H + t] = uint2{x, y};
+  if (n < RS_TINY_THREADS && k >= 3) {
+    // the certified exit's entry (trio_word): the first three distinct positions among the samples - p[0], the first of
+    // p[1 .. k-2] that differs from it (else p[k-1]), the first of p[2 .. k-2] that differs from both (else p[k-1]) - as
+    // byte offsets into the block's f4 points; flagged: a risky draw, or fewer than three distinct positions
+    auto p = [&](int i) { return ((i < 4 ? x : y) >> (8 * (i & 3))) & 0xFFu; };
+    const uint32_t p0 = p(0);
+    uint32_t p1 = p(k - 1), p2 = p(k - 1);
+    for (int i = k - 2; i >= 1; --i) p1 = p(i) != p0 ? p(i) : p1;
+    for (int i = k - 2; i >= 2; --i) p2 = (p(i) != p0 && p(i) != p1) ? p(i) : p2;
+    const bool flagged = (y >> 16) != 0u || p1 == p0 || p2 == p0 || p2 == p1;
+    reinterpret_cast<uint32_t*>(tab)[trio_word(n, H, t)] = flagged ? TRIO_FLAG : (p0 << 4) | (p1 << 14) | (p2 << 24);
+  }
 }
 __device__ __forceinline__ void pos_table_part(const double* __restrict__ hyp, int H, int k,
                                                const uint32_t* __restrict__ counters, uint2* __restrict__ tab,
@@ -2134,10 +2154,12 @@ int ransac_launch(octl_ctx* ctx, const double* xyz_dev, int64_t n_points,
   const size_t off_s = off_d + (size_t)nb * sizeof(BlockDesc);
   const size_t off_b = off_s + (size_t)nb * sizeof(BlockDesc);
   const size_t off_c = (off_b + (size_t)nb * 4 + 31) & ~(size_t)31;
-  // (position table of the instances with compile-time k = 3 .. 6: 256 sizes x H entries of 8 bytes)
+  // (position table of the instances with compile-time k = 3 .. 6: 256 sizes x H entries of 8 bytes; behind it the
+  //  certified exit's entries, trio_word: RS_TINY_THREADS sizes x H entries of 4 bytes)
   const bool use_tab = !any_k && k >= 3 && k <= 6 && (H > 256 || k == 6);
   const size_t off_t = (off_c + RC_WORDS * 4 + 31) & ~(size_t)31;
-  OCTL_TRY(devbuf_reserve(ctx, scratch, off_t + (use_tab ? (size_t)256 * (size_t)H * sizeof(uint2) : 0)));
+  const size_t tab_bytes = (size_t)256 * (size_t)H * sizeof(uint2) + (size_t)RS_TINY_THREADS * (size_t)H * sizeof(uint32_t);
+  OCTL_TRY(devbuf_reserve(ctx, scratch, off_t + (use_tab ? tab_bytes : 0)));
   char* base = static_cast<char*>(scratch.p);
   uint32_t* tmp = scratch.as<uint32_t>();
   BlockDesc* desc = reinterpret_cast<BlockDesc*>(base + off_d);

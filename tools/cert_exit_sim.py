@@ -8,7 +8,8 @@ NumPy oracle, the benchmark's hypothesis table.  Per leaf: the reference's plane
 hypotheses (oracle/ransac_np.py), L = the best of the first 64, b = n - L, the certificate (tools/plane_cert_model.py, the
 float64 port of the header with the kernel's t = PreConst::thrblk) and the cross-product test of the 960 later ones.
 It also checks what the exit rests on: in a certified leaf every later hypothesis that beats L is one the test does
-NOT vouch for (the reference's zero plane).  The counting build's shares (tools/rs_counts.py, slots 24..28) are set
+NOT vouch for (the reference's zero plane).  Forecast of a filter in front of the certificate (two f32 wave sums of the
+residuals against the winner of group 0 instead of nine f64 sums; not built): the refused tests it would spare.  The counting build's shares (tools/rs_counts.py, slots 24..28) are set
 beside these in profiles/r10_ransac_counts.json.
 No GPU, no reference checkout."""
 import os
@@ -34,7 +35,7 @@ def leaves_of(cloud):
 
 def run(name, cloud, table):
     t = dict(leaves=0, b0=0, b1=0, b2=0, b1_quiet=0, b2_quiet=0, c1=0, c2=0, later=0, queued=0, all_vouched=0,
-             winners=0, zero_winners=0, slipped=0, inelig=0)
+             winners=0, zero_winners=0, slipped=0, inelig=0, r1=0, r2=0, f1=0, f2=0, lost=0)
     for pts in leaves_of(cloud):
         n = len(pts)
         idx = np.minimum((table * n).astype(np.int32), n - 1)
@@ -55,8 +56,15 @@ def run(name, cloud, table):
         cert = pcm.certified(pts, THR, L)
         if cert is None:
             t['inelig'] += 1
+        # a filter in front of the certificate, from the residuals against the winner of group 0 (pcm.filter_skips)
+        skip = cert is not None and pcm.filter_skips(pts, plane[int(np.argmax(cnt[:LANES] == L))],
+                                                     pcm.block_constants(pts, THR)[1], b)
+        if cert is False:
+            t[f'r{b}'] += 1
+            t[f'f{b}'] += int(skip)
         if not cert:
             continue
+        t['lost'] += int(skip)
         t[f'c{b}'] += 1
         ok = pcm.vouched(pts, idx[LANES:])
         t['later'] += H - LANES
@@ -79,6 +87,9 @@ def run(name, cloud, table):
     print(f"  certified leaves: {t['queued'] / c:.2f} of 960 later hypotheses not vouched for on average, none in "
           f"{100 * t['all_vouched'] / c:.0f} % of them; a later hypothesis wins in {t['winners']} "
           f"({t['zero_winners']} by the zero plane); vouched-for hypotheses that beat L: {t['slipped']}")
+    print(f"  a filter on the residuals against the winner of group 0 would spare {t['f1']} of {t['r1']} refused tests at "
+          f"b = 1 ({100 * t['f1'] / max(t['r1'], 1):.0f} %), {t['f2']} of {t['r2']} at b = 2 "
+          f"({100 * t['f2'] / max(t['r2'], 1):.0f} %), and skip {t['lost']} of {t['c1'] + t['c2']} certifiable leaves")
     return t
 
 

@@ -110,3 +110,20 @@ def vouched(pts, idx):
     return (c * c).sum(1) > cross_floor(E, G)
 
 
+# ---- a filter in front of the certificate (forecast only: the kernel has none yet) -------------------------------------
+def filter_skips(pts, plane, t, b):
+    """Whether the certificate of a block with n - L = b (1 or 2) cannot succeed, judged from the residuals r of the
+    points against one plane (a, b, c, d) alone - the winner of group 0: with V = sum (r - mean r)^2 / |a|^2,
+    lambda_min(S) <= V, and without point i lambda_min(S_i) <= V - n / (n - 1) (r_i - mean r)^2 / |a|^2; the header's
+    test asks for 4 det / tr^2 <= lambda_min above m t^2 (1 + 2^-10).  Two wave sums instead of nine."""
+    n = len(pts)
+    nn = float((plane[:3] ** 2).sum())
+    if nn == 0.0:
+        return False
+    r = ((plane[0] * pts[:, 0] + plane[1] * pts[:, 1]) + plane[2] * pts[:, 2]) + plane[3]
+    d = r - r.mean()
+    V = float((d * d).sum()) / nn
+    if b == 1:
+        return V <= n * t * t * UP
+    return V - n / (n - 1.0) * float((d * d).max()) / nn <= (n - 1) * t * t * UP
+
