@@ -148,6 +148,34 @@ int octl_forest_extend_pose_f32(octl_forest* f, int32_t slot, const float* xyz, 
 /* The same from a device pointer: octl_forest_extend_pose_device.                                              */
 int octl_forest_extend_pose_device_f32(octl_forest* f, int32_t slot, const float* xyz_dev, int64_t n);
 
+/* Clouds inserted UNDER A TRANSFORM: row i of the cloud is stored as ((R_i0 x + R_i1 y) + R_i2 z) + t_i of its own
+ * 3x4 - every product and sum rounded to f64, no fused multiply-add (registration.py: transform_rows_np; an f32 row is
+ * widened first) - so the forest holds exactly what the entry without a transform leaves for the cloud that was
+ * transformed on the host: store, voxel box, domain flag, and with them every table and error of a later call.  A row
+ * moved outside the domain fails at the build (OCTL_E_DOMAIN), as its host-transformed twin does, not here.
+ *   flags         OCTL_XF_F32: xyz is (n,3) float; OCTL_XF_DEVICE: xyz is a device pointer (consumed in stream order,
+ *                 ordered behind an octl_dev_upload_async into it, never read in place; 8-byte aligned for f64, 4-byte
+ *                 for f32 is enough)
+ *   transforms    HOST, n_transforms x 12 doubles: the rows (R_i0 R_i1 R_i2 t_i) of each 3x4.  Rigidity is not checked.
+ *   segment       HOST uint16[n], or NULL with n_transforms == 1: the transform of every row ("piecewise rigid": the
+ *                 firing columns of a sweep, each with its pose).  The caller has validated segment[i] < n_transforms;
+ *                 the kernel clamps a larger index to n_transforms - 1 so that no read leaves the table.
+ * All host buffers are the caller's again when the call returns.  OCTL_E_INVALID: n_transforms < 1 or
+ * > OCTL_XF_MAX_SEGMENTS, n_transforms > 1 without a segment, a null buffer with n > 0, a transform that is not finite.
+ * n == 0 launches nothing and still creates the pose.  One kernel whatever n; a host cloud costs one host wait, a
+ * device cloud none.                                                                                              */
+#define OCTL_XF_MAX_SEGMENTS 1024
+enum { OCTL_XF_F32 = 1, OCTL_XF_DEVICE = 2 };
+/* Grid.insert_points (grid/grid.py:58-109), OctreeManager.insert_points (octree_manager.py:161-171) and
+ * Octree.insert_points (octree/octree.py:235-239, OctreeNode.insert_points octree/octree.py:67-100) of the transformed
+ * cloud: octl_forest_add_pose.                                                                                   */
+int octl_forest_add_pose_xf(octl_forest* f, const void* xyz, int64_t n, uint32_t flags, const double* transforms,
+                            int32_t n_transforms, const uint16_t* segment, int32_t* slot);
+/* OctreeManager.insert_points on an existing pose and Octree.insert_points (grid/grid.py:58-109 reaches them per
+ * voxel; octree/octree.py:67-100) of the transformed cloud: octl_forest_extend_pose.                             */
+int octl_forest_extend_pose_xf(octl_forest* f, int32_t slot, const void* xyz, int64_t n, uint32_t flags,
+                               const double* transforms, int32_t n_transforms, const uint16_t* segment);
+
 typedef struct octl_build_info {
   int64_t n_points;     /* alive points that were placed                                   */
   int64_t n_voxels;     /* top-level voxels (roots)                                        */

@@ -78,9 +78,37 @@ class Forest:
         self._pooled = None      # (pose selection, LeafPlanes) of the pooled table the device holds
 
     # -- points -----------------------------------------------------------------------------
-    def add_pose(self, points) -> int:
+    def _xf_source(self, points, transform, segment):
+        """(pointer, n, flags, table, n_transforms, segment pointer, keep-alive objects) of a cloud that goes in under
+        a transform (octl_forest_*_pose_xf; registration.transform_rows_np defines what is stored)."""
+        from octreelib_amd.feed import DeviceCloud
+        from octreelib_amd.registration import as_transform_rows
+
+        if isinstance(points, DeviceCloud):
+            src, n, flags, cloud = points.ptr, points.n, 2 | (1 if points.dtype == np.float32 else 0), points
+        else:
+            pts = nat.as_points_native(points)   # (f32 stays f32: widened on the device)
+            src, n, flags, cloud = nat.ptr(pts), len(pts), (1 if pts.dtype == np.float32 else 0), pts
+        table, seg = as_transform_rows(transform, segment, n)
+        return src, n, flags, table, len(table), seg, cloud
+
+    def add_pose(self, points, transform=None, segment=None) -> int:
         from octreelib_amd.feed import DeviceCloud
 
+        if transform is None and segment is not None:
+            raise ValueError("segment is given without transforms")
+        if transform is not None:
+            # moved by the ingest kernel on its way into the store; a device cloud is read in stream order, never in
+            # place, and kept alive until the copy has been consumed (the next synchronising call)
+            src, n, flags, table, m, seg, cloud = self._xf_source(points, transform, segment)
+            slot = C.c_int32(-1)
+            self.ctx.check(self.lib.octl_forest_add_pose_xf(self.handle, src, n, flags, nat.ptr(table), m, nat.ptr(seg),
+                                                            C.byref(slot)))
+            if flags & 2:
+                self._device_clouds.append(cloud)
+            self._in_place = None
+            self._register_slot(n)
+            return slot.value
         if isinstance(points, DeviceCloud) and points.dtype == np.float32:
             # an f32 cloud on the device: widened into the store by the library, never read in place; kept alive
             # until the copy has been consumed (the next synchronising call)
@@ -135,10 +163,18 @@ class Forest:
         self._dirty = True
         self._invalidate()
 
-    def extend_pose(self, slot: int, points):
+    def extend_pose(self, slot: int, points, transform=None, segment=None):
         from octreelib_amd.feed import DeviceCloud
 
-        if isinstance(points, DeviceCloud):
+        if transform is None and segment is not None:
+            raise ValueError("segment is given without transforms")
+        if transform is not None:
+            src, n_new, flags, table, m, seg, cloud = self._xf_source(points, transform, segment)
+            self.ctx.check(self.lib.octl_forest_extend_pose_xf(self.handle, slot, src, n_new, flags, nat.ptr(table), m,
+                                                               nat.ptr(seg)))
+            if flags & 2:
+                self._device_clouds.append(cloud)
+        elif isinstance(points, DeviceCloud):
             # appended device-to-device behind the pose's points (the library orders the copy behind the upload)
             fn = (self.lib.octl_forest_extend_pose_device_f32 if points.dtype == np.float32
                   else self.lib.octl_forest_extend_pose_device)

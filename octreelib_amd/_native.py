@@ -73,6 +73,8 @@ SIGNATURES = {
     "octl_forest_add_pose_device_f32": (C.c_int, [_p, _p, _i64, _pi32]),
     "octl_forest_extend_pose_f32": (C.c_int, [_p, _i32, _p, _i64]),
     "octl_forest_extend_pose_device_f32": (C.c_int, [_p, _i32, _p, _i64]),
+    "octl_forest_add_pose_xf": (C.c_int, [_p, _p, _i64, C.c_uint32, _p, _i32, _p, _pi32]),
+    "octl_forest_extend_pose_xf": (C.c_int, [_p, _i32, _p, _i64, C.c_uint32, _p, _i32, _p]),
     "octl_forest_build": (C.c_int, [_p, _i64, _p, _i32, _i32, _i32, C.POINTER(BuildInfo)]),
     "octl_forest_build_planar": (C.c_int, [_p, _i64, _f64, _i32, _i32, _p, _i32, _i32, C.POINTER(BuildInfo)]),
     "octl_forest_get_split_stats": (C.c_int, [_p, _i64, _p, _p, _pi64]),

@@ -164,6 +164,13 @@ struct octl_ctx {
   // device staging of host float32 clouds (octl_forest_add_pose_f32 / _extend_pose_f32): the upload lands here and
   // the ingest kernel widens it into the forest's f64 store; kept between calls so that a scan loop does no hipMalloc
   DevBuf f32_stage;
+  // clouds inserted under a transform (octl_forest_*_pose_xf): device staging of the transform table and the segment
+  // indices; for a DEVICE cloud, whose call does not wait, they are uploaded from xf_host - the library's copy of the
+  // caller's arrays - and xf_event, recorded behind that upload, is waited for before xf_host is written again
+  DevBuf xf_stage;
+  std::vector<char> xf_host;
+  hipEvent_t xf_event = nullptr;
+  bool xf_inflight = false;
   // octl_forest_leaf_stats / octl_debug_sym3_eigen (leaf_stats.hip): block ids, outputs, claim words, chunk work
   // items and chunk partials of one call; kept between calls
   DevBuf ls_buf;

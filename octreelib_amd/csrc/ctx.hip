@@ -407,6 +407,8 @@ void octl_ctx_destroy(octl_ctx* ctx) {
   for (auto& b : ctx->scan_tmp) devbuf_free(b);
   devbuf_free(ctx->hyp_dev);
   devbuf_free(ctx->f32_stage);
+  devbuf_free(ctx->xf_stage);
+  if (ctx->xf_event) (void)hipEventDestroy(ctx->xf_event);
   devbuf_free(ctx->ls_buf);
   devbuf_free(ctx->rs_counters);
   devbuf_free(ctx->scan_status);

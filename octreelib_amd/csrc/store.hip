@@ -1,7 +1,8 @@
-// The point store of a forest: the ingest kernels that copy (or widen) a pose into it, mark its points alive and
-// fold their voxel box, the kernel that moves the stored rows of poses by a rigid transform each, and the C entries
-// that add, extend or move poses.
+// The point store of a forest: the ingest kernels that copy (or widen, or move by a transform) a pose into it, mark its
+// points alive and fold their voxel box, the kernel that moves the stored rows of poses by a rigid transform each, and
+// the C entries that add, extend or move poses.
 #include "forest.h"
+#include "ingest_xf.h"
 #include "ref_arith.h"
 
 namespace {
@@ -209,6 +210,45 @@ __global__ __launch_bounds__(256) void k_ingest_f32(const float* __restrict__ sr
   if (mode != 0 && (u0 < n_units || (u0 == 0 && n_flat > 0))) box.zero();
   ingest_alive(alive, n);
   vox_fold_publish(box, bbox);
+}
+
+// ---- ingest under a transform ------------------------------------------------------------------------------------
+// The same pass for a cloud that is inserted under one 3x4 (SEG = false: the matrix is a kernel argument, uniform) or
+// under a table of up to OCTL_XF_MAX_SEGMENTS of them with one uint16 index per row (SEG = true: "piecewise rigid").
+// The store, the alive flags and the box folded from the MOVED values are those of the cloud's host-transformed twin
+// (registration.py: transform_rows_np).  A lane needs the three coordinates of a row, so the cloud is read in row
+// groups (ingest_xf.h has the thread's body, which the host test compiles too); src == dst for an f64 host cloud, which
+// is uploaded into the store and moved in place (hence no __restrict__ on the two).  The table stays in global memory:
+// 96 KB at most, L2-resident, read through scalar loads where a wave agrees on its index (sweep order) and gathered per
+// lane elsewhere; no LDS copy (a workgroup of 1024 rows would stage up to 96 KB to use a few rows of it).
+struct IxfFold {
+  VoxFold box;
+  int mode;
+  double L;
+  bool any = false;
+  __device__ __forceinline__ void row(double x, double y, double z) {
+    any = true;
+    if (mode == 0) {
+      box.add(x, 0, L);
+      box.add(y, 1, L);
+      box.add(z, 2, L);
+    }
+  }
+};
+
+template <bool F32, bool SEG, bool SRC16, bool DST16>
+__global__ __launch_bounds__(256) void k_ingest_xf(const void* src, double* dst, uint8_t* __restrict__ alive, int64_t n,
+                                                   const IxfMat one, const IxfMat* __restrict__ table, int n_tab,
+                                                   const uint16_t* __restrict__ seg, int mode, double L,
+                                                   int32_t* __restrict__ bbox) {
+  IxfFold fold;
+  fold.mode = mode;
+  fold.L = L;
+  const int64_t g0 = (int64_t)blockIdx.x * (256 * IXF_GROUPS) + threadIdx.x;
+  ingest_xf_thread<F32, SEG, SRC16, DST16>(src, dst, seg, one, table, n_tab, n, g0, fold);
+  if (mode != 0 && fold.any) fold.box.zero();
+  ingest_alive(alive, n);
+  vox_fold_publish(fold.box, bbox);
 }
 
 // ---- transform_poses: the stored rows of the selected poses moved by one rigid transform each --------------------
@@ -465,6 +505,109 @@ int store_append_f32(octl_forest* f, const float* xyz, int64_t n, bool from_devi
   return OCTL_OK;
 }
 
+// The arguments of a cloud under a transform (octl_forest_add_pose_xf / _extend_pose_xf), checked
+struct XfArgs {
+  uint32_t flags;
+  const double* transforms;
+  int32_t n_transforms;
+  const uint16_t* segment;
+  bool f32() const { return (flags & OCTL_XF_F32) != 0; }
+  bool device() const { return (flags & OCTL_XF_DEVICE) != 0; }
+};
+
+int xf_args_check(octl_ctx* ctx, const XfArgs& a, const void* xyz, int64_t n) {
+  const int M = a.n_transforms;
+  if (M < 1 || M > OCTL_XF_MAX_SEGMENTS)
+    return octl_set_error(ctx, OCTL_E_INVALID, "ingest under a transform: %d transforms (1..%d)", M, OCTL_XF_MAX_SEGMENTS);
+  if (!a.transforms) return octl_set_error(ctx, OCTL_E_INVALID, "ingest under a transform: null transforms");
+  if (a.flags & ~(uint32_t)(OCTL_XF_F32 | OCTL_XF_DEVICE))
+    return octl_set_error(ctx, OCTL_E_INVALID, "ingest under a transform: unknown flags");
+  if (M > 1 && !a.segment)
+    return octl_set_error(ctx, OCTL_E_INVALID, "ingest under a transform: %d transforms without a segment array", M);
+  if (n < 0 || (n > 0 && !xyz)) return octl_set_error(ctx, OCTL_E_INVALID, "bad point buffer");
+  for (int k = 0; k < 12 * M; ++k)
+    if (!std::isfinite(a.transforms[k]))
+      return octl_set_error(ctx, OCTL_E_INVALID, "ingest under a transform: transform %d is not finite", k / 12);
+  return OCTL_OK;
+}
+
+// store_append / store_append_f32 with the rows moved on their way into the store (k_ingest_xf).  One launch whatever
+// n and whatever the store's parity.  An f64 host cloud is uploaded into the store itself and moved in place; an f32
+// host cloud goes through the context's f32 staging buffer; a device cloud is read where it lies.  With a segment
+// array the table and the indices (2 B per row) are uploaded by the same call.
+int store_append_xf(octl_forest* f, const void* xyz, int64_t n, const XfArgs& a) {
+  octl_ctx* ctx = f->ctx;
+  double* dst = nullptr;
+  uint8_t* alive = nullptr;
+  OCTL_TRY(store_prepare_append(f, xyz, n, &dst, &alive));
+  if (n == 0) return OCTL_OK;
+  hipStream_t st = ctx->stream;
+  const bool f32 = a.f32(), dev = a.device(), seg = a.segment != nullptr;
+  const int M = a.n_transforms;
+  IxfMat one;
+  std::memcpy(one.m, a.transforms, sizeof one.m);  // (SEG: unused by the kernel)
+  // table | indices, each from a 256-byte boundary
+  const size_t tab_bytes = align256((size_t)M * sizeof(IxfMat)), seg_bytes = (size_t)n * 2;
+  if (seg) OCTL_TRY(devbuf_reserve(ctx, ctx->xf_stage, tab_bytes + seg_bytes + 16));
+  if (f32 && !dev) OCTL_TRY(devbuf_reserve(ctx, ctx->f32_stage, (size_t)n * 12 + 16));
+  const char* up_tab = reinterpret_cast<const char*>(a.transforms);
+  const char* up_seg = reinterpret_cast<const char*>(a.segment);
+  if (seg && dev) {
+    // no host wait in this call: the uploads read the library's copy of the two arrays
+    if (!ctx->xf_event) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->xf_event, hipEventDisableTiming));
+    if (ctx->xf_inflight && hipEventQuery(ctx->xf_event) != hipSuccess) {
+      (void)hipGetLastError();                           // (hipErrorNotReady is not an error here)
+      HIP_TRY(ctx, hipEventSynchronize(ctx->xf_event));  // (the previous call's upload is still reading the copy)
+    }
+    ctx->xf_inflight = false;
+    ctx->xf_host.resize(tab_bytes + seg_bytes);
+    std::memcpy(ctx->xf_host.data(), a.transforms, (size_t)M * sizeof(IxfMat));
+    std::memcpy(ctx->xf_host.data() + tab_bytes, a.segment, seg_bytes);
+    up_tab = ctx->xf_host.data();
+    up_seg = ctx->xf_host.data() + tab_bytes;
+  }
+  const IxfMat* table_d = nullptr;
+  const uint16_t* seg_d = nullptr;
+  if (seg) {
+    char* base = static_cast<char*>(ctx->xf_stage.p);
+    HIP_TRY(ctx, hipMemcpyAsync(base, up_tab, (size_t)M * sizeof(IxfMat), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base + tab_bytes, up_seg, seg_bytes, hipMemcpyHostToDevice, st));
+    if (dev) {
+      HIP_TRY(ctx, hipEventRecord(ctx->xf_event, st));
+      ctx->xf_inflight = true;
+    }
+    table_d = reinterpret_cast<const IxfMat*>(base);
+    seg_d = reinterpret_cast<const uint16_t*>(base + tab_bytes);
+  }
+  const void* src = xyz;
+  if (!dev) {
+    void* up = f32 ? ctx->f32_stage.p : static_cast<void*>(dst);
+    HIP_TRY(ctx, hipMemcpyAsync(up, xyz, (size_t)n * (f32 ? 12 : 24), hipMemcpyHostToDevice, st));
+    src = up;
+  }
+  const unsigned grid = (unsigned)ceil_div(n, f32 ? ixf_rows_per_wg<true>() : ixf_rows_per_wg<false>());
+  int32_t* bbox = f->bbox_dev.as<int32_t>();
+  // (a device cloud handed over through the ABI may be 8-byte (f64) / 4-byte (f32) aligned only; a pose behind an odd
+  //  number of stored rows starts 8 bytes off: element-wise accesses on that side then, 16-byte ones on the other)
+  const int src16 = (reinterpret_cast<uintptr_t>(src) & 15) == 0, dst16 = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+#define IXF_CASE(F32, SEG, S16, D16)                                                                              \
+  case ((F32) << 3 | (SEG) << 2 | (S16) << 1 | (D16)):                                                            \
+    OCTL_LAUNCH((k_ingest_xf<F32, SEG, S16, D16>), dim3(grid), dim3(256), 0, st, src, dst, alive, n, one, table_d, \
+                M, seg_d, f->mode, f->edge, bbox);                                                                \
+    break;
+  {
+    KTimer t(ctx, f32 ? "ingest_xf_f32" : "ingest_xf");  // (the kernel alone: the uploads are in front of it)
+    switch ((int)f32 << 3 | (int)seg << 2 | src16 << 1 | dst16) {
+      IXF_CASE(0, 0, 0, 0) IXF_CASE(0, 0, 0, 1) IXF_CASE(0, 0, 1, 0) IXF_CASE(0, 0, 1, 1)
+      IXF_CASE(0, 1, 0, 0) IXF_CASE(0, 1, 0, 1) IXF_CASE(0, 1, 1, 0) IXF_CASE(0, 1, 1, 1)
+      IXF_CASE(1, 0, 0, 0) IXF_CASE(1, 0, 0, 1) IXF_CASE(1, 0, 1, 0) IXF_CASE(1, 0, 1, 1)
+      IXF_CASE(1, 1, 0, 0) IXF_CASE(1, 1, 0, 1) IXF_CASE(1, 1, 1, 0) IXF_CASE(1, 1, 1, 1)
+    }
+  }
+#undef IXF_CASE
+  return store_append_done(ctx, dev);
+}
+
 // An EMPTY forest takes the n points that f->xyz already holds (a swapped-in routed buffer, a borrowed
 // caller buffer) as its first pose without touching them: alive flags by memset, the voxel box left to the
 // build (bbox_pending).
@@ -561,17 +704,20 @@ static int commit_new_pose(octl_forest* f, int64_t n, int32_t* slot) {
 }
 
 static int extend_pose_impl(octl_forest* f, int32_t slot, const void* xyz, int64_t n, bool from_device,
-                            bool f32 = false) {
+                            bool f32 = false, const XfArgs* xf = nullptr) {
   if (!f) return OCTL_E_INVALID;
   OCTL_TRY(forest_settle(f));
   octl_ctx* ctx = f->ctx;
+  if (xf) OCTL_TRY(xf_args_check(ctx, *xf, xyz, n));
   const int n_poses = (int)f->pose_off.size() - 1;
   if (slot < 0 || slot >= n_poses) return octl_set_error(ctx, OCTL_E_INVALID, "bad pose slot");
   const int64_t tail = f->n_store - f->pose_off[slot + 1];  // points of the later poses
   // (a device cloud may be the target of an octl_dev_upload_async that is still in flight)
   if (from_device && n > 0) OCTL_TRY(ctx_wait_uploads(ctx, xyz, (size_t)n * (f32 ? 12 : 24)));
   // lands behind everything (bounding box, alive flags)
-  if (f32) {
+  if (xf) {
+    OCTL_TRY(store_append_xf(f, xyz, n, *xf));
+  } else if (f32) {
     OCTL_TRY(store_append_f32(f, static_cast<const float*>(xyz), n, from_device));
   } else {
     OCTL_TRY(store_append(f, static_cast<const double*>(xyz), n, from_device));
@@ -636,6 +782,18 @@ int octl_forest_add_pose_device_f32(octl_forest* f, const float* xyz_dev, int64_
   // (the cloud may be the target of an octl_dev_upload_async that is still in flight)
   if (n > 0) OCTL_TRY(ctx_wait_uploads(f->ctx, xyz_dev, (size_t)n * 12));
   OCTL_TRY(store_append_f32(f, xyz_dev, n, true));
+  return commit_new_pose(f, n, slot);
+}
+
+int octl_forest_add_pose_xf(octl_forest* f, const void* xyz, int64_t n, uint32_t flags, const double* transforms,
+                            int32_t n_transforms, const uint16_t* segment, int32_t* slot) {
+  if (!f) return OCTL_E_INVALID;
+  OCTL_TRY(forest_settle(f));
+  const XfArgs a{flags, transforms, n_transforms, segment};
+  OCTL_TRY(xf_args_check(f->ctx, a, xyz, n));
+  // (the cloud may be the target of an octl_dev_upload_async that is still in flight)
+  if (a.device() && n > 0) OCTL_TRY(ctx_wait_uploads(f->ctx, xyz, (size_t)n * (a.f32() ? 12 : 24)));
+  OCTL_TRY(store_append_xf(f, xyz, n, a));
   return commit_new_pose(f, n, slot);
 }
 
@@ -753,6 +911,12 @@ int octl_forest_extend_pose_f32(octl_forest* f, int32_t slot, const float* xyz, 
 
 int octl_forest_extend_pose_device_f32(octl_forest* f, int32_t slot, const float* xyz_dev, int64_t n) {
   return extend_pose_impl(f, slot, xyz_dev, n, true, true);
+}
+
+int octl_forest_extend_pose_xf(octl_forest* f, int32_t slot, const void* xyz, int64_t n, uint32_t flags,
+                               const double* transforms, int32_t n_transforms, const uint16_t* segment) {
+  const XfArgs a{flags, transforms, n_transforms, segment};
+  return extend_pose_impl(f, slot, xyz, n, a.device(), a.f32(), &a);
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@ from octreelib_amd.internal.voxel import Voxel
 from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane, RayEvidence, RayHits
 from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
-from octreelib_amd.registration import Alignment, RegistrationSystem
+from octreelib_amd.registration import Alignment, RegistrationSystem, host_transformed as _host_transformed
 
 __all__ = ["Grid", "GridConfig"]
 
@@ -68,12 +68,19 @@ class Grid(GridBase):
             self._forest = Forest(0, corner, float(L))
 
     # grid.py:58-109
-    def insert_points(self, pose_number: int, points):
+    def insert_points(self, pose_number: int, points, *, transform=None, segment=None):
+        """transform (no reference counterpart): a 3x4 or 4x4 - Alignment.transform goes straight in - under which
+        the cloud is stored, moved by the ingest kernel on its way into the map: exactly what
+        insert_points(pose_number, transform_rows_np(transform, points, segment)) leaves, without the host pass.  A
+        stack (M, 3, 4) or (M, 4, 4), M <= 1024, with segment (n,), the index of every row's transform, deskews a
+        sweep in the same pass.  points may be a host array (f64 or f32) or a DeviceCloud."""
         if self._plug is not None:
+            if transform is not None or segment is not None:
+                points = _host_transformed(points, transform, segment)
             return self._plug.insert_points(pose_number, points)
         if pose_number in self._slots:
             raise ValueError(f"Cannot insert points to existing pose {pose_number}")
-        self._slots[pose_number] = self._forest.add_pose(points)
+        self._slots[pose_number] = self._forest.add_pose(points, transform, segment)
 
     # grid.py:244-258
     def subdivide(self, subdivision_criteria: List[Callable], pose_numbers: Optional[List[int]] = None):

@@ -35,13 +35,14 @@ class Octree(OctreeBase, Generic[T]):
         self._slot = None
 
     # -- construction -------------------------------------------------------------------
-    def insert_points(self, points):
+    def insert_points(self, points, *, transform=None, segment=None):
         """octree.py:235-239.  Points added to an already subdivided tree descend the existing
-        structure (octree.py:67-98) without triggering new splits."""
+        structure (octree.py:67-98) without triggering new splits.  transform / segment (no reference counterpart):
+        the cloud is stored under the transform(s), as Grid.insert_points describes."""
         if self._slot is None:
-            self._slot = self._forest.add_pose(points)
+            self._slot = self._forest.add_pose(points, transform, segment)
         else:
-            self._forest.extend_pose(self._slot, points)
+            self._forest.extend_pose(self._slot, points, transform, segment)
 
     def subdivide(self, subdivision_criteria: List[Callable]):
         """octree.py:214-220 / 20-32.  A root that is already split holds no points itself, so

@@ -16,7 +16,7 @@ from octreelib_amd.leaf_stats import LeafStatistics, leaf_statistics_of_leaves
 from octreelib_amd.octree.octree_base import OctreeBase, OctreeConfigBase
 from octreelib_amd.query import HostMap, LeafPlanes, Neighbours, PlaneSegments, PointToPlane, RayEvidence, RayHits
 from octreelib_amd.adjustment import Adjustment, AdjustmentSystem
-from octreelib_amd.registration import Alignment, RegistrationSystem
+from octreelib_amd.registration import Alignment, RegistrationSystem, host_transformed as _host_transformed
 
 __all__ = ["OctreeManager"]
 
@@ -47,13 +47,17 @@ class OctreeManager(VoxelBase):
             self._forest = Forest(1, np.asarray(corner_min, dtype=np.float64), float(edge_length))
 
     # octree_manager.py:161-171
-    def insert_points(self, pose_number: int, points):
+    def insert_points(self, pose_number: int, points, *, transform=None, segment=None):
+        """transform / segment (no reference counterpart): the cloud is stored under the transform(s), as
+        Grid.insert_points describes; a second call on a pose extends it."""
         if self._plug is not None:
+            if transform is not None or segment is not None:
+                points = _host_transformed(points, transform, segment)
             return self._plug.insert_points(pose_number, points)
         if pose_number not in self._slots:
-            self._slots[pose_number] = self._forest.add_pose(points)
+            self._slots[pose_number] = self._forest.add_pose(points, transform, segment)
         else:
-            self._forest.extend_pose(self._slots[pose_number], points)
+            self._forest.extend_pose(self._slots[pose_number], points, transform, segment)
 
     # octree_manager.py:36-66
     def subdivide(self, subdivision_criteria: List[Callable], pose_numbers: Optional[List[int]] = None):

@@ -24,7 +24,8 @@ import numpy as np
 
 from octreelib_amd.query import LeafPlanes, _as_queries, point_to_plane_np
 
-__all__ = ["RegistrationSystem", "Alignment", "as_transform", "transform_np", "default_origin", "se3_exp",
+__all__ = ["RegistrationSystem", "Alignment", "as_transform", "transform_np", "transform_rows_np",
+           "as_transform_rows", "default_origin", "se3_exp",
            "system_from_sums", "registration_system_np", "align_np"]
 
 _TRIU = np.triu_indices(6)
@@ -103,6 +104,66 @@ def transform_np(transform, points) -> np.ndarray:
     with np.errstate(invalid="ignore", over="ignore"):
         cols = [((R[i, 0] * q[:, 0] + R[i, 1] * q[:, 1]) + R[i, 2] * q[:, 2]) + t[i] for i in range(3)]
     return np.ascontiguousarray(np.stack(cols, axis=1)) if len(q) else np.empty((0, 3))
+
+
+XF_MAX_SEGMENTS = 1024   # OCTL_XF_MAX_SEGMENTS (include/octreelib_hip.h)
+
+
+def as_transform_rows(transforms, segment, n: int):
+    """(table (M, 12) f64 - the rows (R_i0 R_i1 R_i2 t_i) of every 3x4 -, segment uint16 (n,) or None) of the
+    arguments of transform_rows_np, validated; ValueError otherwise."""
+    a = np.asarray(transforms, dtype=np.float64)
+    if a.ndim == 2:
+        if segment is not None:
+            raise ValueError("segment is given with a single transform: pass transforms of shape (M, 3, 4) or "
+                             "(M, 4, 4)")
+        R, t = as_transform(a)
+        return np.ascontiguousarray(np.concatenate([R, t[:, None]], axis=1).reshape(1, 12)), None
+    if a.ndim != 3:
+        raise ValueError(f"expected a 4x4 or 3x4 transform or a stack of them, got shape {a.shape}")
+    if segment is None:
+        raise ValueError("a stack of transforms needs segment, the index of every row's transform")
+    M = a.shape[0]
+    if not 1 <= M <= XF_MAX_SEGMENTS:
+        raise ValueError(f"{M} transforms: between 1 and {XF_MAX_SEGMENTS} are supported")
+    table = np.empty((M, 12))
+    for k in range(M):
+        R, t = as_transform(a[k])
+        table[k] = np.concatenate([R, t[:, None]], axis=1).reshape(12)
+    s = np.asarray(segment)
+    if not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"segment must have an integer dtype, got {s.dtype}")
+    if s.shape != (n,):
+        raise ValueError(f"segment must have shape ({n},), one index per point, got {s.shape}")
+    if n and (int(s.min()) < 0 or int(s.max()) >= M):
+        raise ValueError(f"segment entries must lie in [0, {M})")
+    return table, np.ascontiguousarray(s, dtype=np.uint16)
+
+
+def transform_rows_np(transforms, points, segment=None) -> np.ndarray:
+    """transform_np with a transform per row ("piecewise rigid": the firing columns of a sweep, each with its pose).
+    transforms (3, 4) or (4, 4) and segment None: transform_np(transforms, points).  transforms (M, 3, 4) or (M, 4, 4),
+    1 <= M <= 1024, and segment (n,) of an integer dtype with entries in [0, M): row i is
+    transform_np(transforms[segment[i]], points[i:i+1]) - the same formula, every product and sum rounded.  f32 points
+    are widened first.  What insert_points(points, transform=transforms, segment=segment) stores."""
+    q = points.astype(np.float64) if isinstance(points, np.ndarray) and points.dtype == np.float32 else points
+    q = _as_queries(q)
+    table, seg = as_transform_rows(transforms, segment, len(q))
+    if seg is None:
+        return transform_np(table.reshape(3, 4), q)
+    m = table[seg]           # (n, 12)
+    with np.errstate(invalid="ignore", over="ignore"):
+        cols = [((m[:, 4 * i] * q[:, 0] + m[:, 4 * i + 1] * q[:, 1]) + m[:, 4 * i + 2] * q[:, 2]) + m[:, 4 * i + 3]
+                for i in range(3)]
+    return np.ascontiguousarray(np.stack(cols, axis=1)) if len(q) else np.empty((0, 3))
+
+
+def host_transformed(points, transform, segment):
+    """The cloud the caller's own plug types are fed for insert_points(points, transform=..., segment=...): moved on the
+    host (transform_rows_np) before the plug sees it."""
+    if transform is None:
+        raise ValueError("segment is given without transforms")
+    return transform_rows_np(transform, points, segment)
 
 
 def default_origin(transform, points) -> np.ndarray:
