@@ -546,6 +546,31 @@ int octl_forest_adjustment_tables(octl_forest* f, int64_t cap_leaves, int32_t* n
  * a successful no-op that changes no state.  OCTL_E_INVALID: n_sel is not the number of poses, NULL transforms with
  * S > 0, a non-finite transform entry (checked before anything runs).  No reference counterpart.                    */
 int octl_forest_transform_poses(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, const double* transforms);
+/* Let go of poses: the selected poses (slot_sel / n_sel as above; NULL: every pose) leave the map, on the device, and
+ * their rows leave the point store.  Afterwards the forest is the forest as it was with those poses absent:
+ *  - the scheme stays (node table, voxels, voxel origin, epochs), as after octl_forest_carve: voxels and leaves that
+ *    only a removed pose populated stay, empty; ray evidence taken on the scheme is still valid;
+ *  - the poses that stay are renumbered densely in ascending order - new_slot (n_sel int32, may be NULL) receives the
+ *    new slot of every old one, -1 for a removed pose - and keep every row, alive or dead, at its index within the
+ *    pose (octl_forest_get_perm minus the pose's offset, octl_forest_nearest's index), bit for bit;
+ *  - every map query over "every pose" answers what it answered over the selection of the remaining poses before;
+ *  - the store holds the remaining poses' rows alone (octl_forest_store_size), and the voxel box on the device is
+ *    folded again from the alive rows that stay: the next fresh build forms its key geometry from that box.
+ * *n_removed (may be NULL): the alive rows of the removed poses.  A built forest loses the removed poses' (leaf, pose)
+ * blocks in ONE compaction, which also applies a pending RANSAC mask (as octl_forest_carve and
+ * octl_forest_filter_count do); a forest without tables (never built, or reset by octl_forest_transform_poses) takes
+ * the store pass alone.  The store pass is out of place, into the block octl_forest_transform_poses writes; a caller's
+ * buffer the store reads in place (octl_forest_add_pose_adopt) is never written, and the store is the forest's own
+ * afterwards.  Every buffer is reserved before anything changes: OCTL_E_NOMEM leaves the forest as it was.
+ * Launches and host waits do not depend on the number of points (the compaction in its fused form): a built forest
+ * 4 launches and 2 host waits, a forest without tables 2 launches and 1 host wait; with no pose left the store pass is
+ * not launched.  Nothing selected: a successful no-op, no launch, no state change (new_slot: the identity).  Every pose
+ * selected: an empty store, the scheme standing.  OCTL_E_INVALID: n_sel is not the number of poses.  OCTL_E_STATE: a
+ * built forest to which points were added since (build first).  No reference counterpart.                          */
+int octl_forest_remove_poses(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int32_t* new_slot,
+                             int64_t* n_removed);
+/* Rows the point store holds (alive or not), alive rows among them, poses.  Any output may be NULL. */
+int octl_forest_store_size(octl_forest* f, int64_t* n_store, int64_t* n_alive, int32_t* n_poses);
 /* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
 int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 

@@ -1110,6 +1110,45 @@ class Forest:
         self._in_place = None   # (the moved store is the forest's own)
         self._invalidate()
 
+    def remove_slots(self, slots):
+        """Let go of the poses of `slots` (octl_forest_remove_poses): their blocks leave the leaf-ordered arrays in
+        one compaction - a pending RANSAC mask with them - and their rows leave the store; the scheme, the voxels and
+        their creation order stay.  Returns (new slot of every old slot, -1 for a removed one; alive points that
+        left).  The slots that stay are renumbered densely in ascending order."""
+        chosen = sorted(set(int(s) for s in slots))
+        # (a forest that has been built - with a scheme or, by a read, without - and has grown since: the library
+        #  would refuse; one that was never built stays unbuilt and takes the store pass alone)
+        if self.has_scheme or self.info is not None:
+            self.ensure_built()
+        self._resolve_membership()   # (pending captures name slots as they are numbered now: behind the last build)
+        new_slot = np.arange(self.n_slots, dtype=np.int32)
+        if not chosen:
+            return new_slot, 0
+        sel = np.zeros(self.n_slots, dtype=np.uint8)
+        sel[chosen] = 1
+        removed = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_remove_poses(self.handle, nat.ptr(sel), self.n_slots, nat.ptr(new_slot),
+                                                         C.byref(removed)))
+        keep = [s for s in range(self.n_slots) if not sel[s]]
+        self.slot_sizes = [self.slot_sizes[s] for s in keep]
+        self.slot_epoch = [self.slot_epoch[s] for s in keep]
+        self.slot_voxel_keys = [self.slot_voxel_keys[s] for s in keep]
+        self._member_next -= sum(1 for s in chosen if s < self._member_next)
+        self.n_slots = len(keep)
+        self._in_place = None        # (the squeezed store is the forest's own)
+        if self.info is not None:
+            n = C.c_int64(0)
+            self.ctx.check(self.lib.octl_forest_settle(self.handle, C.byref(n)))
+            self.n_ord = n.value
+        self._invalidate()
+        return new_slot, removed.value
+
+    def store_size(self):
+        """(rows the store holds, alive rows among them, poses) as the library counts them."""
+        a, b, p = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self.ctx.check(self.lib.octl_forest_store_size(self.handle, C.byref(a), C.byref(b), C.byref(p)))
+        return a.value, b.value, p.value
+
     @property
     def perm(self) -> np.ndarray:
         """perm[i] = index (in the concatenation of all pose clouds, slot order) of the point at

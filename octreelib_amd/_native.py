@@ -110,6 +110,8 @@ SIGNATURES = {
     "octl_forest_adjustment_system": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _i32, _f64, _p, _p, _p]),
     "octl_forest_adjustment_tables": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _pi64, _i64, _p, _p, _p, _pi64]),
     "octl_forest_transform_poses": (C.c_int, [_p, _p, _i32, _p]),
+    "octl_forest_remove_poses": (C.c_int, [_p, _p, _i32, _p, _pi64]),
+    "octl_forest_store_size": (C.c_int, [_p, _pi64, _pi64, _pi32]),
     "octl_forest_ransac": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, _f64, _p, _p, _p]),
     "octl_forest_reference_order": (C.c_int, [_p, _p, _i32, _i64, _p, _pi64]),
     "octl_forest_ransac_all": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _f64]),

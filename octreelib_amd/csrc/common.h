@@ -376,6 +376,10 @@ int octl_exclusive_scan_u32(octl_ctx* ctx, const uint32_t* in, uint32_t* out, in
                             uint32_t* total_dev);
 // status words + a fresh epoch for one look-back chain of up to `tiles` workgroups (lookback.h)
 int octl_scan_status_acquire(octl_ctx* ctx, int64_t tiles, uint64_t** status, uint32_t* epoch);
+// the allocations of a following octl_scan_status_acquire(tiles) / octl_exclusive_scan_u32(n) made now, so that neither
+// can fail for memory (a transaction reserves before it changes anything)
+int octl_scan_status_reserve(octl_ctx* ctx, int64_t tiles);
+int octl_exclusive_scan_reserve(octl_ctx* ctx, int64_t n);
 // stable LSD radix sort of (key u64, value u32) pairs on bits [0, key_bits).  keys[0]/vals[0]
 // hold the input; keys[1]/vals[1] are ping-pong space of the same size.  *result (0 or 1)
 // tells which pair of buffers holds the sorted output.

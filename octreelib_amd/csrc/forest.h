@@ -53,6 +53,7 @@ struct octl_forest {
   // point store: all poses concatenated in slot order (pose-major), insertion order inside
   DevBuf xyz;     // f64 [n_store][3]
   DevBuf alive;   // u8  [n_store]
+  DevBuf alive2;  // octl_forest_remove_poses: the flags of the squeezed store are written here, then the two swap
   // octl_forest_add_pose_adopt: xyz.p is the CALLER's device buffer (read in place, never written, never
   // freed here); the forest's own block waits in xyz_own and the store is copied into it (store_materialize)
   // before anything appends to or reorders the store
@@ -84,7 +85,7 @@ struct octl_forest {
   // (alive_ensure: a second pose, a re-placement; apply_mask fills them in its first kernel): every point is alive
   bool alive_stale = false;
   // octl_forest_transform_poses (store.hip): the table one call uploads - the fresh box, the poses' end offsets, a
-  // 3x4 and a selected flag per pose
+  // 3x4 and a selected flag per pose; octl_forest_remove_poses: its table (RetireLayout)
   DevBuf xf_tab;
 
   // scheme of the last build
@@ -306,3 +307,9 @@ int forest_settle(octl_forest* f);
 void forest_forget_pending(octl_forest* f);
 // mask.hip: the RANSAC mask is allocated and, when it is not valid, all ones (every point kept)
 int ensure_mask(octl_forest* f);
+// mask.hip, for octl_forest_remove_poses (store.hip, store_retire.h).  mask_retire_reserve: every buffer the two calls
+// below grow, grown - nothing the forest reads has changed when it fails.  mask_retire_slots: the blocks of the poses
+// with sel_dev[slot] != 0 are cleared in the mask (a pending RANSAC mask stays in it; without one every other byte
+// becomes 1), their sizes are added to *removed_dev, and the ONE compaction runs (the host waits for its counts).
+int mask_retire_reserve(octl_forest* f);
+int mask_retire_slots(octl_forest* f, const uint8_t* sel_dev, unsigned long long* removed_dev);

@@ -317,6 +317,36 @@ __global__ __launch_bounds__(256) void k_carve_blocks(const uint32_t* __restrict
   for (int64_t i = threadIdx.x & 63; i < n; i += 64) mask[s0 + i] = 0;
 }
 
+// octl_forest_remove_poses (store_retire.h): a (leaf, pose) block of a pose that leaves is emptied and its size
+// counted; fill: no mask is pending, so the bytes of every other block become 1 here - the blocks cover the ordered
+// points exactly - instead of in a fill launch.  One wavefront per block, over a grid that stops growing at 2048
+// workgroups: the sizes are summed per workgroup and added to *removed with ONE atomic each (same-address atomics
+// serialise; one per block of a removed pose would be tens of thousands).
+__global__ __launch_bounds__(256) void k_retire_mask(const uint32_t* __restrict__ blk_start,
+                                                     const int32_t* __restrict__ blk_size,
+                                                     const int32_t* __restrict__ blk_slot, int64_t nb,
+                                                     const uint8_t* __restrict__ slot_sel, int fill,
+                                                     uint8_t* __restrict__ mask,
+                                                     unsigned long long* __restrict__ removed) {
+  __shared__ unsigned long long s_gone[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned long long gone = 0;   // (wave-uniform)
+  for (int64_t b = (int64_t)blockIdx.x * 4 + wave; b < nb; b += (int64_t)gridDim.x * 4) {
+    const bool leaves = slot_sel[blk_slot[b]] != 0;
+    if (!leaves && !fill) continue;
+    const int64_t n = blk_size[b], s0 = blk_start[b];
+    const uint8_t v = leaves ? 0 : 1;
+    for (int64_t i = lane; i < n; i += 64) mask[s0 + i] = v;
+    if (leaves) gone += (unsigned long long)n;
+  }
+  if (lane == 0) s_gone[wave] = gone;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long all = s_gone[0] + s_gone[1] + s_gone[2] + s_gone[3];
+    if (all) atomicAdd(removed, all);
+  }
+}
+
 // The block table describes the leaf-ordered arrays exactly (every producer leaves it that way), so both
 // are compacted together: points tile-wise, blocks block-wise.  One synchronisation (kept points, blocks).
 // (async: return behind the last launch - forest_settle books the counts when somebody looks at the forest again)
@@ -470,6 +500,42 @@ int forest_carve(octl_forest* f, const uint32_t* through, const uint32_t* hits, 
 }
 
 }  // namespace
+
+// (the sizes apply_device_mask asks for, in its order: what is reserved here it does not grow)
+int mask_retire_reserve(octl_forest* f) {
+  octl_ctx* ctx = f->ctx;
+  const int64_t n = f->n_ord, nb = f->n_blocks;
+  OCTL_TRY(devbuf_reserve(ctx, f->mask, (size_t)std::max<int64_t>(n, 1), f->mask_valid ? 1 : 0));
+  if (n <= 0 || nb <= 0) return OCTL_OK;
+  const int64_t nt = ceil_div(n, 2048), n_all = nt + 2 * nb;
+  const size_t o_out = (((size_t)n_all + 8) * 4 + 15) & ~(size_t)15;
+  OCTL_TRY(devbuf_reserve(ctx, f->flags, 2 * o_out));
+  if (!ctx->opt.no_fused_tables && nt + 2 * ceil_div(nb, 256) <= 1024)
+    OCTL_TRY(octl_scan_status_reserve(ctx, nt + 2 * ceil_div(nb, 256)));
+  else
+    OCTL_TRY(octl_exclusive_scan_reserve(ctx, n_all));
+  OCTL_TRY(devbuf_reserve(ctx, f->ord_idx2, (size_t)n * 4));
+  OCTL_TRY(devbuf_reserve(ctx, f->xyz_ord2, (size_t)n * 24));
+  OCTL_TRY(devbuf_reserve(ctx, f->blk_node2, (size_t)n * 4));
+  OCTL_TRY(devbuf_reserve(ctx, f->blk_slot2, (size_t)n * 4));
+  OCTL_TRY(devbuf_reserve(ctx, f->blk_start2, (size_t)n * 4));
+  OCTL_TRY(devbuf_reserve(ctx, f->blk_size2, (size_t)n * 4));
+  return OCTL_OK;
+}
+
+int mask_retire_slots(octl_forest* f, const uint8_t* sel_dev, unsigned long long* removed_dev) {
+  octl_ctx* ctx = f->ctx;
+  if (f->n_ord > 0 && f->n_blocks > 0) {
+    KTimer t(ctx, "remove_poses");
+    OCTL_LAUNCH(k_retire_mask, dim3((unsigned)std::min<int64_t>(ceil_div(f->n_blocks, 4), 2048)), dim3(256), 0, ctx->stream,
+                (const uint32_t*)f->blk_start.as<uint32_t>(), (const int32_t*)f->blk_size.as<int32_t>(),
+                (const int32_t*)f->blk_slot.as<int32_t>(), f->n_blocks, sel_dev, f->mask_valid ? 0 : 1,
+                f->mask.as<uint8_t>(), removed_dev);
+    HIP_TRY(ctx, hipGetLastError());
+    f->mask_valid = true;
+  }
+  return apply_device_mask(f, nullptr);
+}
 
 int forest_settle(octl_forest* f) {
   if (!f->totals_pending) return OCTL_OK;

@@ -203,6 +203,16 @@ int octl_scan_status_acquire(octl_ctx* ctx, int64_t tiles, uint64_t** status, ui
   return OCTL_OK;
 }
 
+// ... and only the growth of it: a following acquire of up to `tiles` tiles allocates nothing
+int octl_scan_status_reserve(octl_ctx* ctx, int64_t tiles) {
+  const size_t need = (size_t)std::max<int64_t>(tiles, 1) * 8;
+  if (ctx->scan_status.cap >= need) return OCTL_OK;
+  OCTL_TRY(devbuf_reserve(ctx, ctx->scan_status, need + need / 2));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->scan_status.p, 0, ctx->scan_status.cap, ctx->stream));
+  ctx->scan_epoch = 0;
+  return OCTL_OK;
+}
+
 int octl_exclusive_scan_u32(octl_ctx* ctx, const uint32_t* in, uint32_t* out, int64_t n,
                             uint32_t* total_dev) {
   if (n <= 0) {
@@ -220,4 +230,18 @@ int octl_exclusive_scan_u32(octl_ctx* ctx, const uint32_t* in, uint32_t* out, in
   const bool single = ctx->opt.scan_mode ? ctx->opt.scan_mode == 1 : ceil_div(n, SCAN_TILE) <= 1024;
   if (!single) return scan_rec(ctx, in, out, n, total_dev, 0);
   return scan_single_pass(ctx, in, out, n, total_dev);
+}
+
+// Every buffer a following octl_exclusive_scan_u32 of n items grows, grown now: a caller that must not fail behind
+// its first change (octl_forest_remove_poses) asks before it changes anything.
+int octl_exclusive_scan_reserve(octl_ctx* ctx, int64_t n) {
+  if (n <= 0) return OCTL_OK;
+  const bool single = ctx->opt.scan_mode ? ctx->opt.scan_mode == 1 : ceil_div(n, SCAN_TILE) <= 1024;
+  if (single) return octl_scan_status_reserve(ctx, ceil_div(n, SCAN_TILE));
+  int64_t m = n;
+  for (int level = 0; level < 3 && ceil_div(m, SCAN_TILE) > 1; ++level) {
+    m = ceil_div(m, SCAN_TILE);
+    OCTL_TRY(devbuf_reserve(ctx, ctx->scan_tmp[level], (size_t)m * sizeof(uint32_t)));
+  }
+  return OCTL_OK;
 }

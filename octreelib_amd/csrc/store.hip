@@ -4,6 +4,7 @@
 #include "forest.h"
 #include "ingest_xf.h"
 #include "ref_arith.h"
+#include "store_retire.h"
 
 namespace {
 
@@ -400,6 +401,178 @@ __global__ __launch_bounds__(256) void k_transform_poses(const double* __restric
   }
   if (mode != 0 && any_alive) box.zero();
   vox_fold_publish(box, bbox);
+}
+
+// ---- remove_poses: the store squeezed, the rows of the removed poses gone (store_retire.h) --------
+// One pass over the NEW store, out of place: later poses move DOWN past the removed ones, so a copy in place would
+// race between workgroups.  The copy is flat, like k_ingest's: a lane owns whole 16-byte units of the DESTINATION
+// (two doubles) and stores them with one instruction each whatever the shift.  The source of a unit lies
+// 3 * shift doubles further up: 16-byte aligned too when the shift is even (one 16-byte load); 8 bytes off when it is
+// odd - a removed pose with an odd number of rows in front, 24 mod 16 = 8 - and then the two doubles are loaded one
+// by one (the store stays wide).  The unit where two poses of different shifts meet takes each double by its own.
+// All twelve row loads of a thread are issued first.  Behind them the alive flags of the workgroup's 2048 rows are
+// gathered (8 per thread, one 8-byte store) and kept in LDS; behind a barrier they tell the fold which of the loaded
+// doubles count: VoxFold / vox_fold_publish over the alive rows that stay, into a fresh box.
+// (No counter of the alive rows in this kernel: one same-address atomicAdd per workgroup - 3 256 of them for 6.7 M
+// rows - took it from 96 to 166 us; a forest without tables counts the new flags in k_alive_count.)
+constexpr int RT_UNITS = 12;                                // 16-byte units per thread
+constexpr int RT_ROWS_PER_WG = 256 * RT_UNITS * 2 / 3;      // 2048
+
+// the table one call uploads: the fresh box with the call's two counters {rows of removed poses the compaction took
+// out, alive rows that stay} behind it, the poses' old end offsets, their shifts, new slots and the selection
+struct RetireLayout {
+  Carve plan;
+  Carve::Part<int32_t> box = plan.add<int32_t>(12);  // (words 8..11: the two u64 counters)
+  Carve::Part<int64_t> end, shift;
+  Carve::Part<int32_t> new_slot;
+  Carve::Part<uint8_t> sel;
+  explicit RetireLayout(int n_poses)
+      : end(plan.add<int64_t>((size_t)n_poses)), shift(plan.add<int64_t>((size_t)n_poses + 1)),
+        new_slot(plan.add<int32_t>((size_t)n_poses)), sel(plan.add<uint8_t>((size_t)n_poses)) {}
+};
+
+__global__ __launch_bounds__(256) void k_retire_poses(const double* __restrict__ src, double* __restrict__ dst,
+                                                      const uint8_t* __restrict__ alive /* nullptr: all alive */,
+                                                      uint8_t* __restrict__ alive_out, int64_t n_new,
+                                                      const int64_t* __restrict__ end,
+                                                      const int64_t* __restrict__ shift, int n_poses, int mode,
+                                                      double L, int32_t* __restrict__ bbox) {
+  __shared__ __align__(8) uint8_t s_alive[RT_ROWS_PER_WG];
+  const RetireMap m{end, shift, n_poses};
+  const int t = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * RT_ROWS_PER_WG;  // (< n_new: the grid is ceil(n_new / 2048))
+  // the poses of the workgroup's first and last row bracket those of every row between them; as a rule they are one
+  // pose, and the whole workgroup moves by one shift
+  const int64_t r_last = min(row0 + RT_ROWS_PER_WG, n_new) - 1;
+  const int s_lo = retire_pose_of_new(m, 0, n_poses - 1, row0);
+  const int s_hi = retire_new_end(m, s_lo) > r_last ? s_lo : retire_pose_of_new(m, s_lo, n_poses - 1, r_last);
+  const bool one = s_lo == s_hi;
+  const int64_t sh = shift[s_lo];
+  // ---- the rows: units u0 + 256 k of the new store, doubles 2 u and 2 u + 1; every load is issued before the flags
+  const int64_t n_flat = 3 * n_new, n_units = n_flat / 2;
+  const int64_t u0 = (int64_t)blockIdx.x * (256 * RT_UNITS) + t;   // (row0 * 3 / 2 = blockIdx * 3072)
+  double2 v[RT_UNITS];
+#pragma unroll
+  for (int k = 0; k < RT_UNITS; ++k) {
+    const int64_t u = u0 + k * 256;
+    v[k] = make_double2(0.0, 0.0);
+    if (u < n_units) {
+      if (one && (sh & 1) == 0) {
+        v[k] = *reinterpret_cast<const double2*>(src + 2 * u + 3 * sh);   // (the store starts 16-byte aligned)
+      } else if (one) {
+        v[k].x = src[2 * u + 3 * sh];
+        v[k].y = src[2 * u + 3 * sh + 1];
+      } else {
+        const int64_t a = retire_src_double(m, s_lo, s_hi, 2 * u), b = retire_src_double(m, s_lo, s_hi, 2 * u + 1);
+        if (b == a + 1 && (a & 1) == 0) {
+          v[k] = *reinterpret_cast<const double2*>(src + a);
+        } else {
+          v[k].x = src[a];
+          v[k].y = src[b];
+        }
+      }
+    }
+  }
+  // ---- alive flags: rows row0 + 8 t .. + 7, normalised to 0 / 1
+  {
+    const int64_t r = row0 + 8 * t;
+    uint64_t w = 0;
+    if (!alive) {
+      for (int j = 0; j < 8 && r + j < n_new; ++j) w |= (uint64_t)1 << (8 * j);
+    } else if (one && r + 8 <= n_new && ((r + sh) & ~(int64_t)7) + 16 <= n_new + shift[n_poses]) {
+      // one shift: the eight flags from the two aligned 8-byte words that hold them (both inside the old flags)
+      const int64_t q = (r + sh) & ~(int64_t)7;
+      const int o = (int)((r + sh) & 7);
+      const uint64_t lo = *reinterpret_cast<const uint64_t*>(alive + q);
+      const uint64_t hi = *reinterpret_cast<const uint64_t*>(alive + q + 8);
+      const uint64_t x = o ? (lo >> (8 * o)) | (hi << (64 - 8 * o)) : lo;
+      w = ((((x & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | x) >> 7) & 0x0101010101010101ull;
+    } else {
+      for (int j = 0; j < 8 && r + j < n_new; ++j) {
+        const int p = one ? s_lo : retire_pose_of_new(m, s_lo, s_hi, r + j);
+        w |= (uint64_t)(alive[r + j + shift[p]] ? 1 : 0) << (8 * j);
+      }
+    }
+    *reinterpret_cast<uint64_t*>(s_alive + 8 * t) = w;
+    if (alive_out) {
+      if (r + 8 <= n_new) {
+        *reinterpret_cast<uint64_t*>(alive_out + r) = w;   // (the flags' block is 16-byte aligned, r a multiple of 8)
+      } else {
+        for (int j = 0; j < 8 && r + j < n_new; ++j) alive_out[r + j] = (uint8_t)(w >> (8 * j));
+      }
+    }
+  }
+  __syncthreads();
+  VoxFold box;
+  bool any_alive = false;
+#pragma unroll
+  for (int k = 0; k < RT_UNITS; ++k) {
+    const int64_t u = u0 + k * 256;
+    if (u < n_units) {
+      reinterpret_cast<double2*>(dst)[u] = v[k];
+      const int ld = 2 * (t + k * 256);                      // double within the workgroup: row ld / 3, axis ld % 3
+      const int r0 = ld / 3, a0 = ld - 3 * r0, r1 = (ld + 1) / 3, a1 = ld + 1 - 3 * r1;
+      const bool l0 = s_alive[r0] != 0, l1 = s_alive[r1] != 0;
+      any_alive |= l0 | l1;
+      if (mode == 0) {
+        if (l0) box.add(v[k].x, a0, L);
+        if (l1) box.add(v[k].y, a1, L);
+      }
+    }
+  }
+  if ((n_flat & 1) && u0 == 0) {  // the last double of an odd number of rows: the z of row n_new - 1
+    const int p = retire_pose_of_new(m, 0, n_poses - 1, n_new - 1);
+    const double z = src[n_flat - 1 + 3 * shift[p]];
+    dst[n_flat - 1] = z;
+    const bool l = alive ? alive[n_new - 1 + shift[p]] != 0 : true;
+    any_alive |= l;
+    if (mode == 0 && l) box.add(z, 2, L);
+  }
+  if (mode != 0 && any_alive) box.zero();
+  vox_fold_publish(box, bbox);
+}
+
+// the alive rows of a squeezed store that has no block table to say so (a forest without tables): flags are 0 / 1, 16
+// per lane and step, one atomic per workgroup of a grid that does not grow with the store
+__global__ __launch_bounds__(256) void k_alive_count(const uint8_t* __restrict__ alive, int64_t n,
+                                                     unsigned long long* __restrict__ out) {
+  __shared__ uint32_t s_w[4];
+  uint32_t c = 0;
+  const int64_t n16 = n / 16;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
+    const uint4 w = reinterpret_cast<const uint4*>(alive)[i];
+    c += __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < n - 16 * n16) c += alive[16 * n16 + threadIdx.x];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0 && s_w[0] + s_w[1] + s_w[2] + s_w[3])
+    atomicAdd(out, (unsigned long long)(s_w[0] + s_w[1] + s_w[2] + s_w[3]));
+}
+
+// the blocks that stay, in the COMPACTED block table: their points are named by their new store rows, their pose by
+// its new slot.  One wavefront per block; lane 0 alone touches the block's slot word.
+__global__ __launch_bounds__(256) void k_retire_blocks(const uint32_t* __restrict__ blk_start,
+                                                       const int32_t* __restrict__ blk_size,
+                                                       int32_t* __restrict__ blk_slot, int64_t nb,
+                                                       const int64_t* __restrict__ shift,
+                                                       const int32_t* __restrict__ new_slot,
+                                                       uint32_t* __restrict__ ord_idx) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= nb) return;
+  const int lane = threadIdx.x & 63;
+  int s = 0;
+  if (lane == 0) {
+    s = blk_slot[b];
+    blk_slot[b] = new_slot[s];
+  }
+  s = __shfl(s, 0);
+  const uint32_t sh = (uint32_t)shift[s];
+  const int64_t n = blk_size[b], s0 = blk_start[b];
+  if (sh)
+    for (int64_t i = lane; i < n; i += 64) ord_idx[s0 + i] -= sh;
 }
 
 __global__ void k_bbox_reset(int32_t* __restrict__ bbox) {
@@ -894,6 +1067,148 @@ int octl_forest_transform_poses(octl_forest* f, const uint8_t* slot_sel, int32_t
   }
   f->bbox_stale = f->bbox_pending = false;
   forest_reset_scheme(f);
+  return OCTL_OK;
+}
+
+int octl_forest_remove_poses(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int32_t* new_slot,
+                             int64_t* n_removed) {
+  if (!f) return OCTL_E_INVALID;
+  OCTL_TRY(forest_settle(f));
+  octl_ctx* ctx = f->ctx;
+  std::vector<uint8_t> sel;
+  OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
+  const int n_poses = (int)f->pose_off.size() - 1;
+  // shifts, new slots (dense, ascending) and new offsets
+  std::vector<int64_t> shift((size_t)n_poses + 1, 0), off_new(1, 0);
+  std::vector<int32_t> slot_new((size_t)std::max(n_poses, 1), -1);
+  int S = 0;
+  for (int s = 0; s < n_poses; ++s) {
+    const bool leaves = sel.empty() || sel[s];
+    const int64_t size = f->pose_off[s + 1] - f->pose_off[s];
+    shift[s + 1] = shift[s] + (leaves ? size : 0);
+    if (leaves) {
+      ++S;
+    } else {
+      slot_new[s] = (int32_t)off_new.size() - 1;
+      off_new.push_back(off_new.back() + size);
+    }
+  }
+  if (S == 0) {  // (nothing leaves: no launch, no state change)
+    if (n_removed) *n_removed = 0;
+    if (new_slot)
+      for (int s = 0; s < n_poses; ++s) new_slot[s] = s;
+    return OCTL_OK;
+  }
+  if (f->built && f->store_dirty)
+    return octl_set_error(ctx, OCTL_E_STATE,
+                          "remove_poses: points were added since the forest was built (bring it up to date first)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t n_old = f->n_store, n_new = n_old - shift[n_poses];
+  const bool tables = f->built && !f->store_dirty;
+  // ---- every buffer before anything the forest reads is changed: a failed allocation leaves it as it was ---------
+  DevBuf& target = f->store_borrowed ? f->xyz_own : f->part_xyz[0];
+  if (n_new > 0) {
+    OCTL_TRY(devbuf_reserve(ctx, target, (size_t)n_new * 24 + 16));
+    OCTL_TRY(devbuf_reserve(ctx, f->alive2, (size_t)n_new + 2));
+  }
+  const RetireLayout lay(n_poses);
+  OCTL_TRY(devbuf_reserve(ctx, f->xf_tab, lay.plan.total));
+  OCTL_TRY(devbuf_reserve(ctx, f->bbox_dev, 32));
+  if (tables) OCTL_TRY(mask_retire_reserve(f));
+  std::vector<char> host(lay.plan.total, 0);
+  {
+    int32_t* box = reinterpret_cast<int32_t*>(host.data() + lay.box.off);
+    for (int a = 0; a < 8; ++a) box[a] = a < 3 ? (1 << 30) : (a < 6 ? -(1 << 30) : 0);
+    std::memcpy(host.data() + lay.end.off, f->pose_off.data() + 1, (size_t)n_poses * 8);
+    std::memcpy(host.data() + lay.shift.off, shift.data(), ((size_t)n_poses + 1) * 8);
+    std::memcpy(host.data() + lay.new_slot.off, slot_new.data(), (size_t)n_poses * 4);
+    uint8_t* sel_h = reinterpret_cast<uint8_t*>(host.data() + lay.sel.off);
+    for (int s = 0; s < n_poses; ++s) sel_h[s] = (sel.empty() || sel[s]) ? 1 : 0;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(f->xf_tab.p, host.data(), host.size(), hipMemcpyHostToDevice, st));
+  int32_t* box_d = Carve::at(f->xf_tab, lay.box);
+  unsigned long long* cnt_d = reinterpret_cast<unsigned long long*>(box_d + 8);
+  const int64_t* shift_d = Carve::at(f->xf_tab, lay.shift);
+  const int64_t alive_before = f->n_alive;
+  // the removed poses' blocks leave the leaf-ordered arrays and the block table (with a pending RANSAC mask, in the
+  // same compaction); the alive flags are cleared by OLD store index: before the store pass
+  if (tables) OCTL_TRY(mask_retire_slots(f, Carve::at(f->xf_tab, lay.sel), cnt_d));
+  {
+    KTimer t(ctx, "remove_poses");  // (with k_retire_mask's: the compaction between them keeps its own label)
+    if (tables) {
+      if (f->n_blocks > 0) {
+        OCTL_LAUNCH(k_retire_blocks, dim3((unsigned)ceil_div(f->n_blocks, 4)), dim3(256), 0, st,
+                    (const uint32_t*)f->blk_start.as<uint32_t>(), (const int32_t*)f->blk_size.as<int32_t>(),
+                    f->blk_slot.as<int32_t>(), f->n_blocks, shift_d, (const int32_t*)Carve::at(f->xf_tab, lay.new_slot),
+                    f->ord_idx.as<uint32_t>());
+        HIP_TRY(ctx, hipGetLastError());
+      }
+    }
+    if (n_new > 0) {
+      const bool flags = !f->alive_stale;
+      OCTL_LAUNCH(k_retire_poses, dim3((unsigned)ceil_div(n_new, RT_ROWS_PER_WG)), dim3(256), 0, st,
+                  (const double*)f->xyz.as<double>(), target.as<double>(),
+                  flags ? (const uint8_t*)f->alive.as<uint8_t>() : (const uint8_t*)nullptr,
+                  flags ? f->alive2.as<uint8_t>() : (uint8_t*)nullptr, n_new,
+                  (const int64_t*)Carve::at(f->xf_tab, lay.end), shift_d, n_poses, f->mode, f->edge, box_d);
+      HIP_TRY(ctx, hipGetLastError());
+      // (with tables the compaction has booked the rows that left; without, the flags just written are counted)
+      if (!tables && flags) {
+        OCTL_LAUNCH(k_alive_count, dim3((unsigned)std::min<int64_t>(ceil_div(n_new, 256 * 16 * 8), 256)), dim3(256), 0,
+                    st, (const uint8_t*)f->alive2.as<uint8_t>(), n_new, cnt_d + 1);
+        HIP_TRY(ctx, hipGetLastError());
+      }
+    }
+  }
+  // the call's own host wait: its two counters through the context's mirror (also: `host` is ours again)
+  unsigned long long cnt[2];
+  {
+    char* mirror = static_cast<char*>(ctx->small_host) + MIRROR_BBOX_WORD * 4;
+    HIP_TRY(ctx, hipMemcpyAsync(mirror, cnt_d, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(cnt, mirror, sizeof cnt);
+  }
+  // ---- commit: the squeezed store with its flags, the box just folded, the poses renumbered ----------------------
+  HIP_TRY(ctx, hipMemcpyAsync(f->bbox_dev.p, box_d, 32, hipMemcpyDeviceToDevice, st));
+  if (f->store_borrowed) {  // (the caller's buffer was only read; with no pose left nothing was written at all)
+    f->xyz = f->xyz_own;
+    f->xyz_own = DevBuf{};
+    f->store_borrowed = false;
+  } else if (n_new > 0) {
+    std::swap(f->xyz, f->part_xyz[0]);
+  }
+  if (n_new > 0 && !f->alive_stale) std::swap(f->alive, f->alive2);
+  if (n_new == 0) f->alive_stale = false;
+  f->bbox_stale = f->bbox_pending = false;
+  f->pose_off = off_new;
+  f->pose_off_uploaded.clear();
+  f->n_store = n_new;
+  if (!tables) f->n_alive = f->alive_stale ? n_new : (int64_t)cnt[1];  // (flags never written: every row alive)
+  if (n_removed) *n_removed = tables ? (int64_t)cnt[0] : alive_before - f->n_alive;
+  f->built_store = tables ? n_new : 0;
+  f->built_poses = tables ? (int)off_new.size() - 1 : 0;
+  f->fast_order_valid = false;
+  // (the selections the derived tables were made for count poses that are gone)
+  f->pl_stamp = f->adj_stamp = f->nn_stamp = f->seg_stamp = 0;
+  f->pl_sel.clear();
+  f->adj_sel.clear();
+  f->adj_slots.clear();
+  f->adj_chunk_off.clear();
+  f->adj_called = false;
+  f->nn_sel.clear();
+  f->seg_sel.clear();
+  forest_contents_changed(f);
+  if (new_slot) std::memcpy(new_slot, slot_new.data(), (size_t)n_poses * 4);
+  return OCTL_OK;
+}
+
+int octl_forest_store_size(octl_forest* f, int64_t* n_store, int64_t* n_alive, int32_t* n_poses) {
+  if (!f) return OCTL_E_INVALID;
+  OCTL_TRY(forest_settle(f));
+  if (n_store) *n_store = f->n_store;
+  if (n_alive) *n_alive = f->n_alive;
+  if (n_poses) *n_poses = (int32_t)f->pose_off.size() - 1;
   return OCTL_OK;
 }
 

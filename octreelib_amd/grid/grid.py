@@ -334,6 +334,28 @@ class Grid(GridBase):
         sel = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
         self._forest.transform_poses(transforms, sel)
 
+    def remove_poses(self, pose_numbers: List[int]) -> int:
+        """Let go of poses: afterwards the map is the map as it was with those poses absent.  The subdivision, the
+        voxels and their creation order stay, as after carve (voxels and leaves only a removed pose populated stay,
+        empty; ray evidence stays valid); every remaining pose reads back the same bits from get_points,
+        get_leaf_points, leaf_statistics and the counters, and its rows keep their Neighbours.index; a query over
+        every pose answers what it answered over the remaining poses before.  The pose numbers are free again -
+        insert_points with one of them adds a new pose, which inherits the subdivision as any late pose does - and
+        the point store on the device shrinks to the remaining poses' rows with its voxel box folded again, so a
+        sliding window holds bounded memory and does not carry the box of everywhere it has been.  A pending RANSAC
+        mask is applied in the same compaction; every cached table is dropped.  Launches and host waits do not depend
+        on the number of points (octl_forest_remove_poses).  Returns the number of stored points that left.  KeyError
+        for an unknown pose; ValueError on the caller's own plug types."""
+        if self._plug is not None:
+            raise ValueError(
+                "remove_poses removes points of the device-resident map: a Grid on the caller's own plug types keeps "
+                "its points in those types on the host, and there is no host path for them")
+        slots = [self._slots[p] for p in pose_numbers]   # KeyError for an unknown pose, before anything changes
+        gone = set(pose_numbers)
+        new_slot, removed = self._forest.remove_slots(slots)
+        self._slots = {p: int(new_slot[s]) for p, s in self._slots.items() if p not in gone}
+        return removed
+
     def _adjust_names(self, pose_numbers):
         """The selected pose numbers in ascending slot order: the order of the transforms and of every result row."""
         chosen = self._slots if pose_numbers is None else set(pose_numbers)
