@@ -19,6 +19,15 @@ project states elsewhere (no tolerance is introduced here):
     within the bound of tests/test_gpu_adjustment.py::test_block_moments), the sums under _check_system;
   * transform_poses_refused raises DomainError and changes nothing; after rows were displaced nearest and raycast raise
     RuntimeError;
+  * the third generation (SEEDS3): ray_evidence == ray_evidence_np count for count on the node table downloaded now
+    (tests/test_gpu_evidence.py) and is read-only; carve - carve_rays or carve(ray_evidence(...)), or carve with the
+    evidence an earlier operation of the log returned - and remove_poses return the number of rows the model lost, and
+    the tables afterwards are the model's; directly before and after a remove_poses every remaining pose reads back
+    the same bytes (get_points, leaf list, leaf_statistics, counters) and leaf_planes / nearest / raycast over the
+    remaining poses before equal the calls over every pose after; store_size is (rows the remaining poses were
+    given, alive rows, poses); remove_poses_refused raises KeyError and changes nothing; what insert_moved /
+    extend_moved store is transform_rows_np of the cloud as given - a host array of any form or a DeviceCloud - bit
+    for bit, and Neighbours.index names the rows of that cloud;
   * the queries are read-only (tables, permutation, coordinates, counters, the error word);
   * at the C ABI octl_forest_point_to_plane answers OCTL_E_STATE exactly when the model says something mutating has
     happened since the last pooled table.
@@ -67,6 +76,8 @@ class Device:
         self.poses = []
         self.displaced = False
         self.replaced = False      # a map function replaced the contents: the store is numbered anew, in block order
+        self.n_applied = 0         # the index of the next operation: a carve names the ray_evidence it takes by it
+        self.evidence = {}
 
     def leaves(self, p):
         if self.kind == "grid":
@@ -154,11 +165,44 @@ class Device:
 
     def apply(self, op):
         o, k = self.o, op["op"]
-        if k in ("insert", "extend"):
+        index, self.n_applied = self.n_applied, self.n_applied + 1
+        if k in ("insert", "extend") + S.MOVED:
             cloud = S.make_cloud(op["cloud"])
-            o.insert_points(cloud) if self.kind == "octree" else o.insert_points(op["pose"], cloud)
-            if k == "insert":
+            how = {}
+            if k in S.MOVED:
+                how["transform"], how["segment"] = S.moved_args(op, len(cloud))
+            if op["cloud"]["form"].startswith("device"):
+                from octreelib_amd.feed import DeviceCloud
+
+                cloud = DeviceCloud(cloud)
+            o.insert_points(cloud, **how) if self.kind == "octree" else o.insert_points(op["pose"], cloud, **how)
+            if k in ("insert", "insert_moved"):
                 self.poses.append(op["pose"])
+        elif k in ("ray_evidence", "carve"):
+            from octreelib_amd.query import RayEvidence
+
+            sel = {} if self.kind == "octree" else {"pose_numbers": op.get("poses")}
+            if op.get("evidence_from") is not None:      # what that operation of the log returned
+                return o.carve(self.evidence[op["evidence_from"]], op["min_through"], op["max_hits"], **sel)
+            O, D, r, returned = S.evidence_rays(op, S.stored_rows(self.f.xyz), float(S.cloud_edge(self.c)))
+            args = (O, D, r, op["margin"], op["min_range"], returned)
+            if k == "ray_evidence":
+                ev = o.ray_evidence(*args)
+                self.evidence[index] = RayEvidence(ev.through.copy(), ev.hits.copy())
+                return args, ev
+            if op["fused"]:
+                return o.carve_rays(*args, op["min_through"], op["max_hits"], **sel)
+            return o.carve(o.ray_evidence(*args), op["min_through"], op["max_hits"], **sel)
+        elif k == "remove_poses":
+            left = o.remove_poses(op["poses"])
+            for p in set(op["poses"]):
+                self.poses.remove(p)      # (the others keep their order: slots are renumbered densely, ascending)
+            return left
+        elif k == "remove_poses_refused":
+            with pytest.raises(KeyError):
+                o.remove_poses(op["poses"])
+        elif k == "store_size":
+            return self.f.store_size()
         elif k in S.SUBDIVIDES:
             crit = S.build_criteria(op["crit"])
             o.subdivide(crit) if self.kind == "octree" else o.subdivide(crit, op["poses"])
@@ -556,6 +600,9 @@ def _check_result(dev, seq, i, op, res, last_build):
     from tests.test_gpu_query import _check_planes
 
     k, f = op["op"], dev.f
+    if k in ("carve", "remove_poses", "store_size"):      # the rows that left / the library's own count, by the model's book
+        assert res == seq.meta[i]["returns"], (k, res, seq.meta[i]["returns"])
+        return
     if k not in S.ALL_READ_ONLY or (res is None and k in ("nearest", "raycast")):      # (refused: rows are displaced)
         return
     what = f"operation {i} {k}"
@@ -580,6 +627,11 @@ def _check_result(dev, seq, i, op, res, last_build):
         elif k == "locate":
             Q, got = res
             assert got.dtype == np.int32 and np.array_equal(got, locate_np(nodes, voxels, f.mode, f._cube[1], Q))
+        elif k == "ray_evidence":
+            from octreelib_amd.query import evidence_inputs
+            from tests._evidence import assert_evidence_equal, evidence_of_nodes
+
+            assert_evidence_equal(res[1], evidence_of_nodes(nodes, *evidence_inputs(*res[0])), what)
         elif k == "nearest":
             _check_nearest(dev, res[1], res[0], op["k"], op["r"], op["poses"], seq.ident[i], what)
         elif k == "raycast":
@@ -698,6 +750,53 @@ def _check_queries(dev, rng, displaced, ident=None):
     assert f.lib.octl_last_error(f.ctx.handle) == err
 
 
+def _read_back(dev, poses, sel, Q, rays):
+    """Everything the given poses read back, and what the map answers over the selection `sel`, as bytes."""
+    from tests.test_gpu_leaf_stats import _stats_bytes
+
+    def attempt(fn):      # (the answer or the kind of refusal: the same before and after)
+        try:
+            return fn()
+        except Exception as e:   # noqa: BLE001
+            return type(e).__name__
+
+    out = []
+    for p in poses:
+        lv = dev.leaves(p)
+        out.append((dev.o.get_points(p).tobytes(), dev.counters(p), attempt(lambda: _stats_bytes(dev.leaf_statistics(p))),
+                    [(np.asarray(v.corner_min, dtype=np.float64).tobytes(), np.float64(v.edge_length).tobytes(), v.node,
+                      v.get_points().tobytes()) for v in lv]))
+
+    def planes():
+        pl = dev.leaf_planes(sel)
+        return _stats_bytes(pl) + (pl.node.tobytes(),)
+
+    def near():
+        nn = dev.nearest(Q, 4, 0.5 * S.cloud_edge(dev.c), sel)
+        return tuple(a.tobytes() for a in (nn.index, nn.pose, nn.distance2, nn.count))
+
+    def cast():
+        h = dev.raycast(rays, sel, "cube", None, None)
+        return tuple(a.tobytes() for a in (h.node, h.t, h.row))
+
+    return out + [attempt(planes), attempt(near), attempt(cast)]
+
+
+def _check_moved(dev, op):
+    """What an insert under a transform stored is transform_rows_np of the cloud as given, bit for bit, whatever form
+    the cloud was given in (the order is the leaves'; the rows of a pose are distinct)."""
+    from octreelib_amd.registration import transform_rows_np
+
+    cloud = S.make_cloud(op["cloud"])
+    T, segment = S.moved_args(op, len(cloud))
+    want = sorted(map(bytes, transform_rows_np(T, cloud, segment)))
+    got = sorted(map(bytes, dev.o.get_points() if dev.kind == "octree" else dev.o.get_points(op["pose"])))
+    if op["op"] == "insert_moved":
+        assert got == want, "the stored rows are not transform_rows_np of the cloud"
+    else:
+        assert set(want) <= set(got), "the appended rows are not transform_rows_np of the cloud"
+
+
 def _replay(seq, observe):
     from octreelib_amd import _native as nat
 
@@ -707,7 +806,26 @@ def _replay(seq, observe):
     last_build = None
     for i, op in enumerate(seq.log):
         try:
+            before = None
+            if observe and op["op"] == "remove_poses":
+                # the commit's own contract on a drawn state: what the remaining poses read back, and a query over
+                # them, directly before ...
+                stay = [p for p in dev.poses if p not in op["poses"]]
+                Q = dev.queries(int(rng.integers(1 << 30)), 200)
+                rays = dev.rays(int(rng.integers(1 << 30)), 150, 6.0 * S.cloud_edge(dev.c), 0.0)
+                before = _read_back(dev, stay, stay, Q, rays)
+            if observe and op["op"] in S.GEN3_READ_ONLY:
+                before = (dev.fresh()[2], dev.f.lib.octl_last_error(dev.f.ctx.handle))
             res = dev.apply(op)
+            if observe and op["op"] == "remove_poses":      # ... and the same calls over every pose directly after
+                assert dev.poses == stay
+                after = _read_back(dev, stay, None, Q, rays)
+                for n, (x, y) in enumerate(zip(before, after)):
+                    assert x == y, f"remove_poses changed item {n} of what the remaining poses {stay} read back"
+            if observe and op["op"] in S.GEN3_READ_ONLY:      # read-only, the error word included
+                assert (dev.fresh()[2], dev.f.lib.octl_last_error(dev.f.ctx.handle)) == before
+            if observe and op["op"] in S.MOVED:
+                _check_moved(dev, op)
             if op["op"] in S.SUBDIVIDES:
                 last_build = op
             displaced = displaced or op.get("fn") == "shift_z"
@@ -730,7 +848,7 @@ def _replay(seq, observe):
     return dev
 
 
-@pytest.mark.parametrize("seed", S.SEEDS + S.SEEDS2)
+@pytest.mark.parametrize("seed", S.SEEDS + S.SEEDS2 + S.SEEDS3)
 def test_random_operation_sequences_vs_model(seed):
     seq = S.generate(seed)
     a = _replay(seq, observe=True)
