@@ -571,6 +571,27 @@ int octl_forest_remove_poses(octl_forest* f, const uint8_t* slot_sel, int32_t n_
                              int64_t* n_removed);
 /* Rows the point store holds (alive or not), alive rows among them, poses.  Any output may be NULL. */
 int octl_forest_store_size(octl_forest* f, int64_t* n_store, int64_t* n_alive, int32_t* n_poses);
+/* Prune the scheme: top-level voxels that hold no point any more leave the voxel list with their whole subtree, and an
+ * internal node below which no point is left becomes a leaf (first_child -1, epoch 0); an internal node that stays keeps
+ * all eight children, empty ones included.  Nodes are renumbered by a stable compaction - roots stay the nodes
+ * [0, voxels_after) in voxel order, levels stay ranges, children stay consecutive; corner, edge, depth and the epochs of
+ * the nodes that stay internal keep their bits - and the block table's node column follows.  Points, their order, the
+ * store, the alive flags and a pending RANSAC mask are not touched (blocks a pending mask will empty still count as
+ * occupied: apply the mask first).  Nothing calls this implicitly.
+ * node_map (the first nodes_before of cap_nodes int32, may be NULL): the new id of the node whose cube contains the old
+ * node's cube - itself or the collapsed node it vanished into - -1 where the voxel is gone.  old_node (the first
+ * nodes_after of cap_nodes int32, may be NULL): new id -> old id.  OCTL_E_INVALID before anything changes when either
+ * is given and cap_nodes < nodes_before.  Every buffer is reserved before anything changes: OCTL_E_NOMEM leaves the
+ * forest as it was.  Launches and host waits do not depend on the number of points, nodes or levels: one fill, three
+ * kernels and ONE host wait find what goes; when nothing does the call ends there and has written no table.  Otherwise
+ * two more kernels follow (the node table out of place, then the blocks' node column) without a wait; asking for
+ * node_map / old_node costs a second wait, for their download.  A forest without tables (never built, or reset by
+ * octl_forest_transform_poses): zeros, no launch.  OCTL_E_STATE: a built forest to which points were added since
+ * (build first).  The split statistics of a planar build are dropped.  No reference counterpart.                  */
+typedef struct {
+  int64_t nodes_before, nodes_after, voxels_before, voxels_after, internal_after, collapsed;
+} octl_prune_info;
+int octl_forest_prune(octl_forest* f, int64_t cap_nodes, int32_t* node_map, int32_t* old_node, octl_prune_info* info);
 /* The eigensolver alone, for tests: n symmetric matrices given as 6 upper-triangle values each. */
 int octl_debug_sym3_eigen(octl_ctx* ctx, const double* cov6, int64_t n, double* eigval, double* eigvec);
 

@@ -1143,6 +1143,41 @@ class Forest:
         self._invalidate()
         return new_slot, removed.value
 
+    def prune(self):
+        """Drop the top-level voxels that hold no point any more and collapse the empty subtrees of the rest
+        (octl_forest_prune; query.prune_np is the definition): a query.PruneResult.  Points, their order and a
+        pending RANSAC mask are not touched.  The voxels that go leave every pose's membership and the creation order;
+        the order of the rest is kept."""
+        from octreelib_amd.query import PruneResult
+
+        if self.has_scheme or self.info is not None:
+            self.ensure_built()
+        self._resolve_membership()   # (pending captures name voxel ranks of the table as it is now)
+        built = self.info is not None and not self._dirty
+        N = self.n_scheme_nodes() if built else 0
+        node_map = np.empty(N, dtype=np.int32)
+        old_node = np.empty(N, dtype=np.int32)
+        vox_before = self.voxels if built and self.mode == 0 else None
+        pi = nat.PruneInfo()
+        self.ctx.check(self.lib.octl_forest_prune(self.handle, N, nat.ptr(node_map) if N else None,
+                                                  nat.ptr(old_node) if N else None, C.byref(pi)))
+        if pi.nodes_before != N:
+            raise RuntimeError(f"prune: {pi.nodes_before} nodes on the device, {N} in the host's table")
+        V = int(pi.voxels_before)
+        if vox_before is not None and pi.voxels_after != V:
+            gone = self._voxel_codes(vox_before[node_map[:V] < 0])
+            self.slot_voxel_keys = [k if k is None or len(k) == 0 else k[~np.isin(self._voxel_codes(k), gone)]
+                                    for k in self.slot_voxel_keys]
+            self._creation_codes = self._creation_codes[~np.isin(self._creation_codes, gone)]
+        if self.info is not None:
+            self.info.n_voxels = pi.voxels_after
+            self.info.n_nodes = pi.nodes_after
+            self.info.n_internal = pi.internal_after
+        self._invalidate()
+        return PruneResult(node_map, old_node[:pi.nodes_after].copy(), int(pi.nodes_after), int(pi.voxels_after),
+                           int(pi.nodes_before - pi.nodes_after), int(pi.voxels_before - pi.voxels_after),
+                           int(pi.collapsed))
+
     def store_size(self):
         """(rows the store holds, alive rows among them, poses) as the library counts them."""
         a, b, p = C.c_int64(0), C.c_int64(0), C.c_int32(0)

@@ -46,6 +46,17 @@ class BuildInfo(C.Structure):
     ]
 
 
+class PruneInfo(C.Structure):
+    _fields_ = [
+        ("nodes_before", C.c_int64),
+        ("nodes_after", C.c_int64),
+        ("voxels_before", C.c_int64),
+        ("voxels_after", C.c_int64),
+        ("internal_after", C.c_int64),
+        ("collapsed", C.c_int64),
+    ]
+
+
 _p = C.c_void_p
 _i32, _i64, _f64 = C.c_int32, C.c_int64, C.c_double
 _pi32, _pi64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -112,6 +123,7 @@ SIGNATURES = {
     "octl_forest_transform_poses": (C.c_int, [_p, _p, _i32, _p]),
     "octl_forest_remove_poses": (C.c_int, [_p, _p, _i32, _p, _pi64]),
     "octl_forest_store_size": (C.c_int, [_p, _pi64, _pi64, _pi32]),
+    "octl_forest_prune": (C.c_int, [_p, _i64, _p, _p, _p]),
     "octl_forest_ransac": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, _f64, _p, _p, _p]),
     "octl_forest_reference_order": (C.c_int, [_p, _p, _i32, _i64, _p, _pi64]),
     "octl_forest_ransac_all": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _f64]),

@@ -262,8 +262,9 @@ int forest_sync_vkeys(octl_forest* f);
 // that the box lies inside the window of the keys; OCTL_E_DOMAIN otherwise
 int forest_fix_origin(octl_forest* f, const int bb[6]);
 // incremental.hip: device copy of the packed voxel keys; poses appended to a built forest placed into
-// its scheme in O(new points).  *done = 0: not applicable, nothing was changed
-int forest_sync_vcodes(octl_forest* f);
+// its scheme in O(new points).  *done = 0: not applicable, nothing was changed.  wait = false: an upload of the host's
+// keys is not waited for - the caller waits for the stream before f->vkeys can change
+int forest_sync_vcodes(octl_forest* f, bool wait = true);
 int forest_insert_incremental(octl_forest* f, int* done, octl_build_info* info);
 
 // The block table, the ordered points, the node table or the pose offsets have changed or are about to (a pose added

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void k_inc_block_sizes(const uint32_t* __restr
 }  // namespace
 
 // The sorted packed voxel codes of the current scheme on the device (roots = nodes [0, V) in this order).
-int forest_sync_vcodes(octl_forest* f) {
+int forest_sync_vcodes(octl_forest* f, bool wait) {
   if (f->vcode_valid) return OCTL_OK;
   octl_ctx* ctx = f->ctx;
   const int64_t V = f->n_voxels;
@@ -278,7 +278,8 @@ int forest_sync_vcodes(octl_forest* f) {
     } else {
       HIP_TRY(ctx, hipMemcpyAsync(f->vcode_dev[0].p, f->vkeys.data(), (size_t)V * 8, hipMemcpyHostToDevice,
                                   ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable source
+      // pageable source.  wait = false: the caller waits for the stream before it returns (octl_forest_prune)
+      if (wait) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
   }
   f->vcode_valid = true;

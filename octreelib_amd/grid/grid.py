@@ -356,6 +356,25 @@ class Grid(GridBase):
         self._slots = {p: int(new_slot[s]) for p, s in self._slots.items() if p not in gone}
         return removed
 
+    def prune(self):
+        """Make the subdivision follow the points again, on the device: top-level voxels that hold no point of any
+        pose any more (after carve, filter, a RANSAC mask that was applied, remove_poses) leave the map with their
+        whole subtree, and an internal node below which no point is left becomes a leaf; an internal node that stays
+        keeps all eight children, empty ones included.  Nothing calls this implicitly.  Every read of every pose
+        gives the same points, leaves and statistics as before, minus the empty leaves that are gone; points, their
+        order and a pending RANSAC mask are not touched (prune after the mask is applied: what a pending mask will
+        empty still counts as occupied).  Node ids change: the PruneResult returned maps them (node_map, old_node),
+        and RayEvidence.remapped(result) carries evidence over.  A pose that no longer has a voxel it was inserted
+        into no longer lists that voxel's (empty) leaves.  A later scan that falls into a dropped voxel creates it
+        anew, as any voxel seen for the first time: an unsplit root at the END of the creation order, until the next
+        subdivide.  Launches and host waits do not depend on the number of points, nodes or levels
+        (octl_forest_prune).  ValueError on the caller's own plug types."""
+        if self._plug is not None:
+            raise ValueError(
+                "prune renumbers the scheme of the device-resident map: a Grid on the caller's own plug types keeps "
+                "its points in those types on the host, and there is no host path for them")
+        return self._forest.prune()
+
     def _adjust_names(self, pose_numbers):
         """The selected pose numbers in ascending slot order: the order of the transforms and of every result row."""
         chosen = self._slots if pose_numbers is None else set(pose_numbers)

@@ -135,6 +135,12 @@ class Octree(OctreeBase, Generic[T]):
         return self._forest.carve_rays(origins, directions, ranges, margin, min_range, returned, min_through,
                                        max_hits, None)
 
+    def prune(self):
+        """Collapse the subtrees below which no point is left into leaves (a PruneResult; Grid.prune describes it).
+        The root always stays: an empty octree becomes its bare root."""
+        self._query_ready()
+        return self._forest.prune()
+
     def leaf_planes(self):
         """One least-squares plane per non-empty leaf, in ascending node id (a LeafPlanes)."""
         self._query_ready()

@@ -350,6 +350,16 @@ class OctreeManager(VoxelBase):
         self._slots = {p: int(new_slot[s]) for p, s in self._slots.items() if p not in gone}
         return removed
 
+    def prune(self):
+        """Collapse the subtrees below which no point of any pose is left into leaves (a PruneResult; Grid.prune
+        describes it).  The root always stays: an empty manager becomes its bare root.  ValueError on the caller's
+        own plug types."""
+        if self._plug is not None:
+            raise ValueError(
+                "prune renumbers the scheme of the device-resident map: an OctreeManager on the caller's own plug "
+                "types keeps its points in those types on the host, and there is no host path for them")
+        return self._forest.prune()
+
     def _adjust_names(self, pose_numbers):
         """The selected pose numbers in ascending slot order: the order of the transforms and of every result row."""
         chosen = self._slots if pose_numbers is None else set(pose_numbers)

@@ -26,7 +26,8 @@ from octreelib_amd.leaf_stats import LeafStatistics, cov6_to_full, leaf_statisti
 __all__ = ["LeafPlanes", "PointToPlane", "locate_np", "pooled_leaf_statistics_np", "point_to_plane_np",
            "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K", "PlaneSegments",
            "SegmentTable", "plane_segments_np", "segment_probes_np", "RayHits", "raycast_np", "normalize_directions",
-           "RAY_CAP_EDGES", "RayEvidence", "ray_evidence_np", "carve_keep_np", "evidence_inputs"]
+           "RAY_CAP_EDGES", "RayEvidence", "ray_evidence_np", "carve_keep_np", "evidence_inputs", "PruneResult",
+           "PrunedTables", "prune_np"]
 
 VOX_ABS_LIMIT = 1 << 30   # absolute voxel indices travel as int32
 NN_MAX_K = 8              # OCTL_NN_MAX_K: the largest k of nearest()
@@ -442,11 +443,99 @@ class RayEvidence:
             raise ValueError(f"evidence over {len(self)} nodes + evidence over {len(other)} nodes")
         return RayEvidence(self.through + other.through, self.hits + other.hits)
 
+    def remapped(self, result: "PruneResult") -> "RayEvidence":
+        """This evidence on the scheme prune() left: every node that still exists carries its counters
+        (through[old_node], hits[old_node]).  A node that prune collapsed into a leaf was internal and had none: it
+        starts at zero, whatever its vanished children had seen.  ValueError for evidence of another size than the
+        scheme that was pruned."""
+        if len(self) != len(result.node_map):
+            raise ValueError(f"remapped: evidence over {len(self)} nodes, the map had {len(result.node_map)} (evidence "
+                             f"belongs to the scheme it was taken on)")
+        old = np.asarray(result.old_node, dtype=np.int64)
+        return RayEvidence(np.ascontiguousarray(self.through[old]), np.ascontiguousarray(self.hits[old]))
+
     def free(self, min_through: int = 2, max_hits: int = 0) -> np.ndarray:
         """(n_nodes,) bool: at least min_through rays passed through the node and at most max_hits ended in it - the
         nodes carve empties."""
         min_through, max_hits = check_carve_args(min_through, max_hits)
         return (self.through.astype(np.int64) >= min_through) & (self.hits.astype(np.int64) <= max_hits)
+
+
+@dataclass
+class PruneResult:
+    """Answer of prune(): how the node ids of the scheme before map to the scheme after."""
+
+    node_map: np.ndarray      # (nodes before,) int32 new id of the node whose cube contains the old node's cube - the
+                              # node itself or the collapsed node it vanished into; -1 where the voxel is gone
+    old_node: np.ndarray      # (nodes after,) int32 old id of every node that stays
+    n_nodes: int              # nodes after
+    n_voxels: int             # top-level voxels after
+    nodes_dropped: int
+    voxels_dropped: int
+    collapsed: int            # internal nodes that became leaves
+
+
+@dataclass
+class PrunedTables:
+    """What prune_np returns: the tables after, and the two maps of a PruneResult."""
+
+    nodes: dict
+    blocks: dict
+    voxel_keep: np.ndarray    # (voxels before,) bool: the voxel stays (the order of those that do is unchanged)
+    node_map: np.ndarray
+    old_node: np.ndarray
+    collapsed: int
+
+
+def prune_np(nodes, blocks, mode: int) -> PrunedTables:
+    """The definition of prune(): drop the top-level voxels that hold no point, collapse the empty subtrees of the rest.
+
+    nodes: the node table (voxel, depth, parent, first_child, corner, edge, epoch; roots are the nodes [0, V) in voxel
+    order), blocks: the (leaf, pose) block table (node, slot, start, size; every block is non-empty), mode: 0 grid,
+    1 single cube.  With occ[n] = some block lies in the subtree of n:
+      keep      a root stays iff occ[root] (mode 1: the one root always stays); any other node stays iff occ[parent], so
+                the eight children of a node stay or go together;
+      collapse  a kept internal node with not occ becomes a leaf (first_child -1, epoch 0); an internal node that stays
+                internal keeps its eight children, empty ones included, as the reference has it (octree.py:177-191);
+      number    kept nodes are renumbered by a stable compaction: roots stay [0, V') in voxel order, level ranges stay
+                ranges; parent, first_child and voxel are remapped, corner, edge, depth and the other epochs keep their
+                bits;
+      blocks    keep their order, start, size and slot; node is remapped (a node that holds a block always stays)."""
+    parent = np.asarray(nodes["parent"], dtype=np.int64)
+    fc = np.asarray(nodes["first_child"], dtype=np.int64)
+    N = len(parent)
+    occ = np.zeros(N, dtype=bool)
+    for n in np.unique(np.asarray(blocks["node"], dtype=np.int64)).tolist():
+        while n >= 0 and not occ[n]:
+            occ[n] = True
+            n = int(parent[n])
+    root = parent < 0
+    keep = np.where(root, occ | (mode == 1), occ[np.maximum(parent, 0)])
+    new_id = np.cumsum(keep) - keep
+    old_node = np.nonzero(keep)[0].astype(np.int32)
+    collapse = keep & (fc >= 0) & ~occ
+    node_map = np.full(N, -1, dtype=np.int32)
+    for i in range(N):
+        c = i
+        while c >= 0 and not keep[c]:
+            c = int(parent[c])
+        if c >= 0:
+            node_map[i] = new_id[c]
+    o = old_node.astype(np.int64)
+    remap = lambda a: np.where(a >= 0, new_id[np.maximum(a, 0)], -1).astype(np.int32)
+    out = {
+        "voxel": new_id[np.asarray(nodes["voxel"], dtype=np.int64)[o]].astype(np.int32),
+        "depth": np.asarray(nodes["depth"], dtype=np.int32)[o],
+        "parent": remap(parent[o]),
+        "first_child": np.where(collapse[o], -1, remap(fc[o])).astype(np.int32),
+        "corner": np.asarray(nodes["corner"], dtype=np.float64).reshape(N, 3)[o],
+        "edge": np.asarray(nodes["edge"], dtype=np.float64)[o],
+        "epoch": np.where(collapse[o], 0, np.asarray(nodes["epoch"], dtype=np.int32)[o]).astype(np.int32),
+    }
+    blk = {k: np.array(v, copy=True) for k, v in blocks.items()}
+    blk["node"] = node_map[np.asarray(blocks["node"], dtype=np.int64)].astype(np.int32)
+    V = int(np.count_nonzero(root))
+    return PrunedTables(out, blk, keep[:V].copy(), node_map, old_node, int(np.count_nonzero(collapse)))
 
 
 def check_carve_args(min_through, max_hits):
