@@ -484,6 +484,39 @@ int octl_forest_registration_system_device(octl_forest* f, const double* xyz_dev
                                            double max_distance, double huber_delta, double* sys_dev,
                                            int64_t* counts_dev, int32_t* node_dev, int32_t* row_dev,
                                            double* residual_dev);
+/* The point-to-point normal equations of a scan against the NEAREST STORED POINT of every transformed query, for ONE
+ * rigid transform: classic ICP where the map has no accepted plane to offer (octreelib_amd/registration.py:
+ * point_registration_system_np is the definition of every number below).  T, origin = c and p as above.  Per query:
+ * the stored point m of the poses of slot_sel / n_sel (NULL: all) nearest to p within max_distance, exactly as
+ * octl_forest_nearest answers it for k = 1 (same search, same d2 bits, same total order (d2, slot, index), same state
+ * rules); the point is USED iff there is one.  e = fl(p - m) per component, d = p - c, J = [-[d]x, I3] (the derivative
+ * of e under p <- Rot(w)(p - c) + c + v), w = 1, or for huber_delta > 0 decided on d2: 1 if d2 <= fl(delta delta) else
+ * delta / sqrt(d2):
+ *   sys[0..21)  = upper triangle of H = sum w J^T J, row-major: H_ww = sum w (|d|^2 I - d d^T), H_wv = [sum w d]x,
+ *                 H_vv = (sum w) I - 17 distinct sums, the rest copies, sign changes and +0.0,
+ *   sys[21..27) = g = (sum w d x e, sum w e),  sys[27] = cost = sum rho, rho = d2 / 2 or delta (sqrt(d2) - delta / 2),
+ *   counts[0] = used points, counts[1] = queries whose p is finite.
+ * slot / index / distance2: all three NULL, or all three given and then written for every query (-1, -1, +inf where
+ * nothing lies within max_distance).  The sums are reduced in the tree of octl_forest_registration_system (a function
+ * of n alone): the same call gives the same bits on any device and in either form.  With eps = 2^-53 and D as above
+ * every entry is within (D + 8) eps sum |term| of the exact sum (csrc/reg_point_term.h fixes the operation order and
+ * counts the roundings).  n = 0: no launch, sys = +0.0, counts = 0.  OCTL_E_INVALID: what octl_forest_nearest refuses
+ * (max_distance not finite or <= 0 or above twice the voxel edge), n >= 2^31, a NULL pointer, a subset of the three
+ * per-point pointers, a non-finite T or origin; OCTL_E_STATE: before build, after map_leaf_points moved rows outside
+ * their leaves - all before anything runs.  Three kernels (the block index of the selection is made first when it is
+ * missing or stale); the host form adds one upload, the 240-byte download and one wait.  Read-only.  No reference
+ * counterpart.                                                                                                        */
+int octl_forest_point_registration_system(octl_forest* f, const double* xyz, int64_t n, const double T[12],
+                                          const double origin[3], double max_distance, double huber_delta,
+                                          const uint8_t* slot_sel, int32_t n_sel, double sys[28], int64_t counts[2],
+                                          int32_t* slot, int64_t* index, double* distance2);
+/* The same with pointers from octl_dev_alloc (T, origin and slot_sel stay host arrays); no host wait.  n = 0: sys_dev
+ * and counts_dev are zeroed by two fills.  No reference counterpart.                                                 */
+int octl_forest_point_registration_system_device(octl_forest* f, const double* xyz_dev, int64_t n, const double T[12],
+                                                 const double origin[3], double max_distance, double huber_delta,
+                                                 const uint8_t* slot_sel, int32_t n_sel, double* sys_dev,
+                                                 int64_t* counts_dev, int32_t* slot_dev, int64_t* index_dev,
+                                                 double* distance2_dev);
 /* Multi-pose plane adjustment: for ONE rigid transform PER selected pose, the point-to-plane normal equations of every
  * pose against the leaf planes pooled at those transforms - what one block-Jacobi iteration of a sliding-window plane
  * adjustment needs from the device (the 6x6 solves and the iteration are the caller's; octreelib_amd/adjustment.py has

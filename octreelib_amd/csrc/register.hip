@@ -27,11 +27,9 @@
 #include "common.h"
 #include "forest.h"
 #include "query_walk.h"
-#include "sums28.h"
+#include "reg_fold.h"
 
 namespace {
-
-constexpr int RS_CHUNK = 4096;
 
 struct RegParams {
   double T[12];         // row-major 3 x 4: R | t
@@ -101,27 +99,6 @@ __global__ __launch_bounds__(256) void k_reg_partial(const double* __restrict__ 
   if (threadIdx.x == 0) {
     reinterpret_cast<long long*>(out)[RS_SUMS] = a.used;
     reinterpret_cast<long long*>(out)[RS_SUMS + 1] = a.located;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_reg_fold(const double* __restrict__ rows, int64_t n_rows,
-                                                  double* __restrict__ sys, int64_t* __restrict__ counts) {
-  __shared__ double lds[4][RS_SUMS];
-  __shared__ long long ldc[4][2];
-  RegAcc a;
-  reg_zero(a);
-  for (int64_t r = threadIdx.x; r < n_rows; r += 256) {
-    const double* in = rows + r * RS_ROW;
-#pragma unroll
-    for (int k = 0; k < RS_SUMS; ++k) a.s[k] += in[k];
-    a.used += reinterpret_cast<const long long*>(in)[RS_SUMS];
-    a.located += reinterpret_cast<const long long*>(in)[RS_SUMS + 1];
-  }
-  reg_block_reduce(a, lds, ldc);
-  if (threadIdx.x < RS_SUMS) sys[threadIdx.x] = a.s[0];
-  if (threadIdx.x == 0) {
-    counts[0] = a.used;
-    counts[1] = a.located;
   }
 }
 

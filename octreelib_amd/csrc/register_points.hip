@@ -1,0 +1,274 @@
+// Point-to-point scan-to-map registration, the device's share: for ONE rigid transform T the normal equations of a
+// scan against the nearest stored point of every transformed query (octl_forest_point_registration_system, DESIGN.md
+// 4.19) - classic ICP where the map has no planes to offer.  The 6x6 solve, the pose update and the loop stay on the
+// host (octreelib_amd/registration.py: point_registration_system_np is the definition, align_np the loop).  No
+// reference counterpart: the reference has no registration.
+//
+// Per query q:
+//   p = ((R_i0 q_x + R_i1 q_y) + R_i2 q_z) + t_i, every product and sum rounded (the bits of transform_np);
+//   the nearest stored point m of the selection within max_distance: the search of octl_forest_nearest with k = 1
+//   (nearest_walk.h - the same cubes, the same d2 bits, the same total order (d2, slot, index));
+//   used iff there is one; e = fl(p - m), d2 as the search formed it;
+//   the point's term of the 17 distinct sums: reg_point_term.h, which fixes the operation order.
+//
+// Three launches in stream order:
+//   k_reg_match    one query per lane, grid-stride, launched as k_nearest is: writes one 32-byte record {e, d2} per
+//                  query (d2 = +inf: unused) and, in its second instance, slot / index / distance2;
+//   k_regp_partial the summation tree of k_reg_partial unchanged (register.hip): chunks of 4096, lane tid takes
+//                  4096 k + 256 j + tid for j = 0..15 in that order, the 17 sums expanded to the 28-number row by
+//                  copies and sign changes, reg_block_reduce, row k.  No walk: 56 bytes per query streamed;
+//   k_reg_fold     as it is (reg_fold.h).
+// The tree is a function of n alone: no floating-point atomics, nothing sized by the CU count (the grid of k_reg_match
+// is, and it adds nothing).  The host form adds one upload, the 240-byte download through the pinned mirror and ONE
+// host wait; the device form does not wait.  LDS: 960 bytes (k_regp_partial, k_reg_fold), none in k_reg_match.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+#include "forest.h"
+#include "nearest_walk.h"
+#include "reg_fold.h"
+#include "reg_point_term.h"
+
+namespace {
+
+struct RegPointParams {
+  double T[12];  // row-major 3 x 4: R | t
+  double c[3];   // origin of the rotational part
+  double delta;  // <= 0: no weights
+  double delta2;
+};
+
+// the best candidate of a walk with k = 1, and where it lies in the ordered arrays
+struct RegBest {
+  double bd;
+  uint64_t bid;
+  uint32_t pos;
+  __device__ __forceinline__ double worst() const { return bd; }
+  __device__ __forceinline__ void offer(double d2, uint64_t id, uint32_t at) {
+    if (cand_less(d2, id, bd, bid)) {
+      bd = d2;
+      bid = id;
+      pos = at;
+    }
+  }
+};
+
+__device__ __forceinline__ void reg_transform(const double* __restrict__ T, double qx, double qy, double qz,
+                                              double p[3]) {
+  // (separate products and sums: the library is built with -ffp-contract=off, and the host forms the same bits)
+  p[0] = ((T[0] * qx + T[1] * qy) + T[2] * qz) + T[3];
+  p[1] = ((T[4] * qx + T[5] * qy) + T[6] * qz) + T[7];
+  p[2] = ((T[8] * qx + T[9] * qy) + T[10] * qz) + T[11];
+}
+
+template <bool PER_POINT>
+__global__ __launch_bounds__(256) void k_reg_match(const double* __restrict__ xyz, int64_t n, RegPointParams P, double r,
+                                                   double r2, NNTables T, double4* __restrict__ rec_out,
+                                                   int32_t* __restrict__ slot_out, int64_t* __restrict__ index_out,
+                                                   double* __restrict__ d2_out) {
+  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    double p[3];
+    reg_transform(P.T, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], p);
+    RegBest best = {INF, ~0ull, 0u};
+    nearest_walk(T, p[0], p[1], p[2], r, r2, best);
+    const bool has = best.bid != ~0ull;
+    double4 rec = make_double4(0.0, 0.0, 0.0, INF);
+    if (has) {
+      // (the operands and the operation of the walk's own dx, dy, dz: the same bits)
+      const double* __restrict__ m = T.xyz_ord + 3 * (int64_t)best.pos;
+      rec = make_double4(p[0] - m[0], p[1] - m[1], p[2] - m[2], best.bd);
+    }
+    rec_out[i] = rec;
+    if (PER_POINT) {
+      slot_out[i] = has ? (int32_t)(best.bid >> 32) : -1;
+      index_out[i] = has ? (int64_t)(best.bid & 0xffffffffull) : -1;
+      d2_out[i] = best.bd;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_regp_partial(const double* __restrict__ xyz, int64_t n, RegPointParams P,
+                                                      const double4* __restrict__ rec, double* __restrict__ rows) {
+  __shared__ double lds[4][RS_SUMS];
+  __shared__ long long ldc[4][2];
+  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+  double S[RP_SUMS];
+#pragma unroll
+  for (int k = 0; k < RP_SUMS; ++k) S[k] = 0.0;
+  long long used = 0, located = 0;
+  const int64_t base = (int64_t)blockIdx.x * RS_CHUNK + threadIdx.x;
+#pragma unroll 1
+  for (int j = 0; j < RS_CHUNK / 256; ++j) {
+    const int64_t i = base + (int64_t)j * 256;
+    if (i >= n) break;
+    double p[3];
+    reg_transform(P.T, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], p);
+    located += (fabs(p[0]) < INF && fabs(p[1]) < INF && fabs(p[2]) < INF) ? 1 : 0;  // (false for NaN)
+    const double4 m = rec[i];
+    if (!(m.w < INF)) continue;  // (no match: skipped, never multiplied by zero)
+    used += 1;
+    const double e[3] = {m.x, m.y, m.z};
+    reg_point_term(p, P.c, e, m.w, P.delta, P.delta2, S);
+  }
+  RegAcc a;
+  reg_point_expand(S, a.s);
+  a.used = used;
+  a.located = located;
+  reg_block_reduce(a, lds, ldc);
+  double* out = rows + (int64_t)blockIdx.x * RS_ROW;
+  if (threadIdx.x < RS_SUMS) out[threadIdx.x] = a.s[0];
+  if (threadIdx.x == 0) {
+    reinterpret_cast<long long*>(out)[RS_SUMS] = a.used;
+    reinterpret_cast<long long*>(out)[RS_SUMS + 1] = a.located;
+  }
+}
+
+struct RegPointCall {
+  RegPointParams P;
+  NNTables T;
+  double r;
+};
+
+const char* const WHAT = "point_registration_system";
+
+// the checks every form starts with (nothing has run when one of them fails): the search's, then the system's
+int regp_begin(octl_forest* f, const void* xyz, int64_t n, const double* T, const double* origin, double max_distance,
+               double huber_delta, const uint8_t* slot_sel, int32_t n_sel, const void* sys, const void* counts,
+               const void* slot, const void* index, const void* distance2, RegPointCall* c) {
+  const int per_point = (slot ? 1 : 0) + (index ? 1 : 0) + (distance2 ? 1 : 0);
+  const bool pointers_ok = (n <= 0 || xyz) && T && origin && sys && counts && (per_point == 0 || per_point == 3);
+  octl_ctx* ctx = f->ctx;
+  // (nearest_begin ends by making the block index: what the system refuses comes first.  Before build, and with
+  //  pointers missing, nearest_begin itself refuses - state, then arguments)
+  if (f->built && pointers_ok) {
+    for (int k = 0; k < 12; ++k)
+      if (!std::isfinite(T[k])) return octl_set_error(ctx, OCTL_E_INVALID, "%s: the transform is not finite", WHAT);
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(origin[k])) return octl_set_error(ctx, OCTL_E_INVALID, "%s: the origin is not finite", WHAT);
+  }
+  OCTL_TRY(nearest_begin(f, WHAT, n, 1, max_distance, slot_sel, n_sel, pointers_ok, &c->T));
+  std::memcpy(c->P.T, T, sizeof c->P.T);
+  std::memcpy(c->P.c, origin, sizeof c->P.c);
+  c->P.delta = huber_delta > 0.0 ? huber_delta : 0.0;
+  c->P.delta2 = c->P.delta * c->P.delta;
+  c->r = max_distance;
+  return OCTL_OK;
+}
+
+// scratch of one call in f->rg_rows: [0, 256) the result (28 sums, 2 counts), the rows, then the records
+struct RegPointScratch {
+  double *result, *rows;
+  double4* rec;
+};
+
+int regp_scratch(octl_forest* f, int64_t n, RegPointScratch* s) {
+  const size_t rows_bytes = (size_t)ceil_div(n, RS_CHUNK) * RS_ROW * 8;
+  OCTL_TRY(devbuf_reserve(f->ctx, f->rg_rows, 256 + rows_bytes + (size_t)n * 32));
+  char* base = static_cast<char*>(f->rg_rows.p);
+  s->result = reinterpret_cast<double*>(base);
+  s->rows = reinterpret_cast<double*>(base + 256);
+  s->rec = reinterpret_cast<double4*>(base + 256 + rows_bytes);
+  return OCTL_OK;
+}
+
+// the three kernels
+int regp_launch(octl_ctx* ctx, const RegPointCall& c, const double* xyz_dev, int64_t n, const RegPointScratch& s,
+                int32_t* slot, int64_t* index, double* distance2, double* sys_dev, int64_t* counts_dev) {
+  const int64_t n_rows = ceil_div(n, RS_CHUNK);
+  const double r2 = c.r * c.r;
+  {
+    KTimer timer(ctx, "reg_match");
+    const unsigned wgs =
+        (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+    if (slot)
+      OCTL_LAUNCH(k_reg_match<true>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, s.rec, slot,
+                  index, distance2);
+    else
+      OCTL_LAUNCH(k_reg_match<false>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, s.rec,
+                  nullptr, nullptr, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  {
+    KTimer timer(ctx, "regp_partial");
+    OCTL_LAUNCH(k_regp_partial, dim3((unsigned)n_rows), dim3(256), 0, ctx->stream, xyz_dev, n, c.P,
+                (const double4*)s.rec, s.rows);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  KTimer timer(ctx, "reg_fold");
+  OCTL_LAUNCH(k_reg_fold, dim3(1), dim3(256), 0, ctx->stream, (const double*)s.rows, n_rows, sys_dev, counts_dev);
+  HIP_TRY(ctx, hipGetLastError());
+  return OCTL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int octl_forest_point_registration_system(octl_forest* f, const double* xyz, int64_t n, const double T[12],
+                                          const double origin[3], double max_distance, double huber_delta,
+                                          const uint8_t* slot_sel, int32_t n_sel, double sys[28], int64_t counts[2],
+                                          int32_t* slot, int64_t* index, double* distance2) {
+  if (!f) return OCTL_E_INVALID;
+  RegPointCall c;
+  OCTL_TRY(regp_begin(f, xyz, n, T, origin, max_distance, huber_delta, slot_sel, n_sel, sys, counts, slot, index,
+                      distance2, &c));
+  if (n == 0) {
+    for (int k = 0; k < RS_SUMS; ++k) sys[k] = 0.0;
+    counts[0] = counts[1] = 0;
+    return OCTL_OK;
+  }
+  octl_ctx* ctx = f->ctx;
+  hipStream_t st = ctx->stream;
+  Carve plan;  // f->q_stage: [queries 3 f64 | index i64 | d2 f64 | slot i32]
+  const auto q_part = plan.add<double>((size_t)n * 3);
+  const size_t q_only = plan.total;
+  const auto idx_part = plan.add<int64_t>((size_t)n);
+  const auto d2_part = plan.add<double>((size_t)n);
+  const auto slot_part = plan.add<int32_t>((size_t)n);
+  OCTL_TRY(devbuf_reserve(ctx, f->q_stage, slot ? plan.total : q_only));
+  RegPointScratch s;
+  OCTL_TRY(regp_scratch(f, n, &s));
+  double* q_d = Carve::at(f->q_stage, q_part);
+  int64_t* idx_d = slot ? Carve::at(f->q_stage, idx_part) : nullptr;
+  double* d2_d = slot ? Carve::at(f->q_stage, d2_part) : nullptr;
+  int32_t* slot_d = slot ? Carve::at(f->q_stage, slot_part) : nullptr;
+  HIP_TRY(ctx, hipMemcpyAsync(q_d, xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
+  OCTL_TRY(regp_launch(ctx, c, q_d, n, s, slot_d, idx_d, d2_d, s.result,
+                       reinterpret_cast<int64_t*>(s.result + RS_SUMS)));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, s.result, (RS_SUMS + 2) * 8, hipMemcpyDeviceToHost, st));
+  if (slot) {
+    HIP_TRY(ctx, hipMemcpyAsync(slot, slot_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(index, idx_d, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(distance2, d2_d, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  std::memcpy(sys, ctx->small_host, RS_SUMS * 8);
+  std::memcpy(counts, static_cast<const char*>(ctx->small_host) + RS_SUMS * 8, 16);
+  return OCTL_OK;
+}
+
+int octl_forest_point_registration_system_device(octl_forest* f, const double* xyz_dev, int64_t n, const double T[12],
+                                                 const double origin[3], double max_distance, double huber_delta,
+                                                 const uint8_t* slot_sel, int32_t n_sel, double* sys_dev,
+                                                 int64_t* counts_dev, int32_t* slot_dev, int64_t* index_dev,
+                                                 double* distance2_dev) {
+  if (!f) return OCTL_E_INVALID;
+  RegPointCall c;
+  OCTL_TRY(regp_begin(f, xyz_dev, n, T, origin, max_distance, huber_delta, slot_sel, n_sel, sys_dev, counts_dev,
+                      slot_dev, index_dev, distance2_dev, &c));
+  octl_ctx* ctx = f->ctx;
+  if (n == 0) {  // (nothing to reduce: the zeros are two fills in stream order)
+    HIP_TRY(ctx, hipMemsetAsync(sys_dev, 0, RS_SUMS * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(counts_dev, 0, 16, ctx->stream));
+    return OCTL_OK;
+  }
+  RegPointScratch s;
+  OCTL_TRY(regp_scratch(f, n, &s));
+  OCTL_TRY(ctx_wait_uploads(ctx, xyz_dev, (size_t)n * 24));
+  return regp_launch(ctx, c, xyz_dev, n, s, slot_dev, index_dev, distance2_dev, sys_dev, counts_dev);
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // The 28 sums + 2 counts of a 6x6 point-to-plane system and their reduction over a workgroup of 256: shared by
-// register.hip (k_reg_partial / k_reg_fold) and adjust.hip (k_adj_partial / k_adj_fold) - one fixed tree.
+// register.hip (k_reg_partial), register_points.hip (k_regp_partial), reg_fold.h (k_reg_fold) and adjust.hip
+// (k_adj_partial / k_adj_fold) - one fixed tree.
 #pragma once
 #include "common.h"
 

@@ -282,6 +282,44 @@ class Grid(GridBase):
         return self._forest.align(points, initial, sel, min_points, max_variance, max_distance, huber_delta,
                                   max_iterations, tolerance, damping)
 
+    def point_registration_system(self, points, transform=None, *, max_distance: float,
+                                  pose_numbers: Optional[List[int]] = None, huber_delta: Optional[float] = None,
+                                  origin=None, per_point: bool = False) -> RegistrationSystem:
+        """The point-to-point normal equations of a scan under `transform` (4x4 or 3x4, None: identity) against the
+        NEAREST STORED POINT of the given poses (None: all) within max_distance - classic ICP for maps without planes
+        (vegetation, rubble, a sparse first scan): a RegistrationSystem (H 6x6, g, cost, n_used, n_located, origin)
+        for the left update p <- Rot(w)(p - origin) + origin + v; .solve() is the Gauss-Newton step.  The
+        correspondences are those of nearest(transform_np(transform, points), k=1, max_distance=...) exactly; a point
+        without one is not used; huber_delta: Huber weights on the distance; origin None: the centroid of the
+        transformed scan; per_point: the Neighbours come back in .neighbours.  Three kernels once the block index of
+        the selection exists, one host wait (octreelib_amd/registration.py: point_registration_system_np is the
+        definition).  ValueError for a max_distance that is not finite and positive or above twice the voxel edge;
+        RuntimeError after map_leaf_points moved rows outside their leaves; KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().point_registration_system(points, transform, max_distance=max_distance,
+                                                              pose_numbers=sel, huber_delta=huber_delta,
+                                                              origin=origin, per_point=per_point)
+        names = [p for p, _ in sorted(self._slots.items(), key=lambda kv: kv[1])]
+        return self._forest.point_registration_system(points, transform, origin, sel, max_distance, huber_delta,
+                                                      per_point, names)
+
+    def align_points(self, points, initial=None, *, max_distance: float, pose_numbers: Optional[List[int]] = None,
+                     huber_delta: Optional[float] = None, max_iterations: int = 20, tolerance: float = 1e-9,
+                     damping: float = 0.0) -> Alignment:
+        """Gauss-Newton alignment of a scan to the nearest stored points, from `initial` (None: identity): an
+        Alignment (transform 4x4, iterations, converged, costs, n_used, reason).  The block index is made once and the
+        scan is uploaded once (or is a DeviceCloud of f64 points); an iteration is three kernels, a 240-byte download
+        and a 6x6 solve on the host.  Ends when |xi| < tolerance, at max_iterations, or - not converged, last good
+        transform - when fewer than six points are used."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().align_points(points, initial, max_distance=max_distance, pose_numbers=sel,
+                                                 huber_delta=huber_delta, max_iterations=max_iterations,
+                                                 tolerance=tolerance, damping=damping)
+        return self._forest.align_points(points, initial, sel, max_distance, huber_delta, max_iterations, tolerance,
+                                         damping)
+
     def adjustment_system(self, transforms=None, pose_numbers: Optional[List[int]] = None, origin=None,
                           min_points: int = 8, min_poses: int = 2, max_variance: Optional[float] = None,
                           leaves: bool = False) -> AdjustmentSystem:

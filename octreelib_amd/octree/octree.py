@@ -173,6 +173,23 @@ class Octree(OctreeBase, Generic[T]):
         return self._forest.align(points, initial, None, min_points, max_variance, max_distance, huber_delta,
                                   max_iterations, tolerance, damping)
 
+    def point_registration_system(self, points, transform=None, *, max_distance: float, huber_delta=None, origin=None,
+                                  per_point: bool = False):
+        """The point-to-point normal equations of a scan under `transform` against the nearest stored points within
+        max_distance (a RegistrationSystem; Grid.point_registration_system describes it).  One cube has no cap on
+        max_distance."""
+        self._query_ready()
+        return self._forest.point_registration_system(points, transform, origin, None, max_distance, huber_delta,
+                                                      per_point, [0] * self._forest.n_slots)
+
+    def align_points(self, points, initial=None, *, max_distance: float, huber_delta=None, max_iterations: int = 20,
+                     tolerance: float = 1e-9, damping: float = 0.0):
+        """Gauss-Newton alignment of a scan to the nearest stored points (an Alignment; Grid.align_points describes
+        it)."""
+        self._query_ready()
+        return self._forest.align_points(points, initial, None, max_distance, huber_delta, max_iterations, tolerance,
+                                         damping)
+
     def node_cubes(self):
         """(corner (N, 3), edge (N,)) of every node id that locate / leaf_planes can name."""
         self._query_ready()

@@ -921,6 +921,29 @@ class HostMap:
             raise ValueError(f"nearest: max_distance {r} exceeds twice the voxel edge {self.edge}")
         return nearest_np(points, self.clouds(pose_numbers), k, max_distance=r)
 
+    def _point_clouds(self, max_distance, pose_numbers):
+        _, r = check_nearest_args(1, max_distance)
+        if self.mode == 0 and r > 2.0 * self.edge:
+            raise ValueError(f"point_registration_system: max_distance {r} exceeds twice the voxel edge {self.edge}")
+        return r, self.clouds(pose_numbers)
+
+    def point_registration_system(self, points, transform=None, *, max_distance, pose_numbers=None, huber_delta=None,
+                                  origin=None, per_point=False):
+        from octreelib_amd.registration import point_registration_system_np
+
+        r, clouds = self._point_clouds(max_distance, pose_numbers)
+        return point_registration_system_np(clouds, points, transform, origin, max_distance=r,
+                                            huber_delta=huber_delta, per_point=per_point)
+
+    def align_points(self, points, initial=None, *, max_distance, pose_numbers=None, huber_delta=None,
+                     max_iterations=20, tolerance=1e-9, damping=0.0):
+        from octreelib_amd.registration import align_np, point_registration_system_np
+
+        r, clouds = self._point_clouds(max_distance, pose_numbers)   # (once: the map does not change meanwhile)
+        pts = _as_queries(points)
+        system = lambda T, c: point_registration_system_np(clouds, pts, T, c, max_distance=r, huber_delta=huber_delta)
+        return align_np(system, initial, max_iterations, tolerance, damping)
+
     def raycast(self, origins, directions, max_range, *, min_range=0.0, pose_numbers=None, surface="cube",
                 min_points=None, max_variance=None) -> RayHits:
         """raycast_np over the leaves of the node table: the directions normalised, the grid's cap checked, counts

@@ -1,6 +1,8 @@
 """
 Scan-to-map registration against the pooled leaf planes: the point-to-plane normal equations of a scan under a rigid
-transform (registration_system), and the Gauss-Newton loop over them (align).
+transform (registration_system), and the Gauss-Newton loop over them (align).  Further down the same against the
+nearest stored points - classic ICP where the map has no planes to offer (point_registration_system, align_points:
+point_registration_system_np is their definition).
 
 The device reduces a scan to the 6x6 system - 28 sums and two counts (octl_forest_registration_system, csrc/
 register.hip); the solve, the pose update and the loop are NumPy on the host (one download of 240 bytes per iteration).
@@ -22,11 +24,11 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from octreelib_amd.query import LeafPlanes, _as_queries, point_to_plane_np
+from octreelib_amd.query import LeafPlanes, Neighbours, _as_queries, check_nearest_args, nearest_np, point_to_plane_np
 
 __all__ = ["RegistrationSystem", "Alignment", "as_transform", "transform_np", "transform_rows_np",
            "as_transform_rows", "default_origin", "se3_exp",
-           "system_from_sums", "registration_system_np", "align_np"]
+           "system_from_sums", "registration_system_np", "point_registration_system_np", "align_np"]
 
 _TRIU = np.triu_indices(6)
 
@@ -34,7 +36,8 @@ _TRIU = np.triu_indices(6)
 @dataclass
 class RegistrationSystem:
     """The normal equations of one transform.  node / row / residual / planes: the per-point answers (those of
-    point_to_plane for the transformed scan) when they were asked for, None otherwise."""
+    point_to_plane for the transformed scan) when they were asked for, None otherwise.  neighbours: the per-point
+    answers of a point-to-point system (those of nearest with k = 1 for the transformed scan), likewise."""
 
     H: np.ndarray            # (6, 6) symmetric
     g: np.ndarray            # (6,)
@@ -46,6 +49,7 @@ class RegistrationSystem:
     row: Optional[np.ndarray] = None
     residual: Optional[np.ndarray] = None
     planes: Optional[LeafPlanes] = None
+    neighbours: Optional[Neighbours] = None
 
     def solve(self, damping: float = 0.0) -> np.ndarray:
         """xi = -(H + damping diag(H))^-1 g; ValueError when fewer than six points were used."""
@@ -244,6 +248,79 @@ def registration_system_np(locate: Callable, planes: LeafPlanes, points, transfo
                              int((node >= 0).sum()), c)
     if per_point:
         out.node, out.row, out.residual, out.planes = node, row, r, planes
+    return out
+
+
+def point_registration_system_np(clouds, points, transform=None, origin=None, *, max_distance: float,
+                                 huber_delta: Optional[float] = None, dtype=np.float64, answers=None,
+                                 per_point: bool = False) -> RegistrationSystem:
+    """The point-to-point normal equations of a scan against the nearest stored point of every transformed query, on
+    the host: the definition of point_registration_system (octl_forest_point_registration_system, csrc/
+    register_points.hip).  clouds: [(pose number, (m, 3) points)] of the selected poses in ascending slot order, as
+    nearest_np takes them.  Per query q, with T = (R, t), the origin c, r = max_distance and delta = huber_delta:
+
+      p = transform_np(T, q)                                   the bits of registration_system
+      (pose, index, d2, count) = nearest_np(p, clouds, k=1, max_distance=r)
+                                                               the total order (d2, slot, index), d2 <= fl(r r) inclusive
+      used = count == 1; m = the stored point, bit for bit; e = p - m, one rounding per component (nearest's own dx,
+      dy, dz; d2 is its d2); n_located = the queries whose p is finite (a query that is not is skipped by a branch)
+      d = p - c; the residual under p <- Rot(w)(p - c) + c + v is e + w x d + v, so J = [-[d]x, I3]
+      Huber, decided on d2: inlier iff d2 <= fl(delta delta): w = 1, rho = d2 / 2; otherwise s = sqrt(d2), w = delta / s,
+      rho = delta (s - delta / 2)
+      H = sum w J^T J, g = sum w J^T e, cost = sum rho:  H_ww = sum w (|d|^2 I - d d^T), H_wv = [sum w d]x,
+      H_vv = (sum w) I, g_w = sum w d x e, g_v = sum w e - 17 distinct sums; the rest of system_from_sums' 28 numbers
+      are copies, sign changes and structural zeros (+0.0).
+
+    origin None: default_origin.  The sums are formed in `dtype` (np.longdouble for a reference of higher precision)
+    from the f64 bits of p, e and d2.  answers = a Neighbours (k = 1) for the transformed scan: take these per-point
+    answers as given instead of searching here - the reference of a sum over exactly the terms another
+    implementation selected.  per_point: the Neighbours come back in .neighbours."""
+    _, r = check_nearest_args(1, max_distance)
+    R, t = as_transform(transform)
+    T = _matrix(R, t)
+    q = _as_queries(points)
+    p = transform_np(T, q)
+    c = default_origin(T, q) if origin is None else _as_origin(origin)
+    clouds = [(int(k), np.asarray(a, dtype=np.float64).reshape(-1, 3)) for k, a in clouds]
+    nb = nearest_np(p, clouds, 1, max_distance=r) if answers is None else answers
+    used = np.asarray(nb.count).reshape(-1) > 0
+    pose, index = np.asarray(nb.pose).reshape(-1)[used], np.asarray(nb.index).reshape(-1)[used]
+    m = np.empty((int(used.sum()), 3))
+    for k, a in clouds:
+        of = pose == k
+        m[of] = a[index[of]]
+    with np.errstate(invalid="ignore", over="ignore"):      # (a wild origin overflows; the sums say so)
+        n_located = int(np.all(np.isfinite(p), axis=1).sum())
+        e = (p[used] - m).astype(dtype)
+        d2_64 = np.asarray(nb.distance2, dtype=np.float64).reshape(-1)[used]
+        d2 = d2_64.astype(dtype)
+        d = p[used].astype(dtype) - c.astype(dtype)
+        w = np.ones(len(d2), dtype=dtype)
+        rho = d2 / 2
+        if huber_delta is not None and huber_delta > 0:
+            tail = d2_64 > np.float64(huber_delta) * np.float64(huber_delta)
+            dl = dtype(huber_delta)
+            s = np.sqrt(d2[tail])
+            w[tail] = dl / s
+            rho[tail] = dl * (s - dl / 2)
+        wd, we = d * w[:, None], e * w[:, None]
+        x, y, z = d[:, 0], d[:, 1], d[:, 2]
+        sm = lambda a: a.sum(dtype=dtype) if len(a) else dtype(0)
+        X, Y, Z, W = sm(wd[:, 0]), sm(wd[:, 1]), sm(wd[:, 2]), sm(w)
+        gw = np.cross(wd, e).reshape(-1, 3)
+        zero = dtype(0)
+        sums = np.array([
+            sm(wd[:, 1] * y + wd[:, 2] * z), sm(-wd[:, 0] * y), sm(-wd[:, 0] * z), zero, zero - Z, Y,
+            sm(wd[:, 0] * x + wd[:, 2] * z), sm(-wd[:, 1] * z), Z, zero, zero - X,
+            sm(wd[:, 0] * x + wd[:, 1] * y), zero - Y, X, zero,
+            W, zero, zero,
+            W, zero,
+            W,
+            sm(gw[:, 0]), sm(gw[:, 1]), sm(gw[:, 2]), sm(we[:, 0]), sm(we[:, 1]), sm(we[:, 2]),
+            sm(rho)], dtype=dtype)
+    out = system_from_sums(sums, (int(used.sum()), n_located), c)
+    if per_point:
+        out.neighbours = nb
     return out
 
 
