@@ -287,7 +287,7 @@ int octl_forest_leaf_stats(octl_forest* f, const int32_t* block_ids, int64_t nb,
  * every covariance entry within 4 g R^2 of the exact value; eigenvalues within 64 * 2^-53 * |C|_F of those of the
  * returned covariance.  A leaf's bits depend on its own points and on the selection only.  The table also stays on
  * the device for octl_forest_point_to_plane, until a call changes the forest's contents or scheme (build*, add_pose*,
- * extend_pose*, apply_mask*, apply_host_mask, filter_count, carve*, set_contents, set_scheme, clear).  Read-only
+ * extend_pose*, apply_mask*, apply_host_mask, filter_count, carve*, remove_sparse, set_contents, set_scheme, clear).  Read-only
  * otherwise.
  * OCTL_E_STATE before the first build.  No reference counterpart (the reference has no per-leaf statistics).        */
 int octl_forest_pooled_leaf_stats(octl_forest* f, const uint8_t* slot_sel, int32_t n_sel, int64_t cap, int32_t* node,
@@ -428,6 +428,48 @@ int octl_forest_carve(octl_forest* f, const uint32_t* through, const uint32_t* h
 int octl_forest_carve_device(octl_forest* f, const uint32_t* through_dev, const uint32_t* hits_dev, int64_t n_nodes,
                              const uint8_t* slot_sel, int32_t n_sel, int64_t min_through, int64_t max_hits,
                              int64_t* n_alive);
+/* How many stored points lie within `radius` of every query point?  For query q and stored point p: d2 as
+ * octl_forest_nearest forms it (dx = q_x - p_x, d2 = (dx dx + dy dy) + dz dz in f64, every product and sum rounded, no
+ * fma); p counts iff d2 <= radius * radius (formed once, inclusive) - exactly the candidates of octl_forest_nearest, of
+ * the same points: those of the selected poses (slot_sel: n_sel = number of poses flags, NULL = every pose) that are
+ * alive and in the leaf-ordered arrays; what a mask, a filter, carve or remove_poses took out never counts.  count[i] =
+ * min(number of counting points, max_count), int32; max_count = 0: uncapped.  A query with a coordinate that is not
+ * finite counts 0.  octreelib_amd/query.py: radius_count_np is the same by brute force, count for count.  The search
+ * is the walk of octl_forest_nearest with a sink that counts; a capped query stops at the cap.
+ * OCTL_E_INVALID: max_count < 0; radius not finite or <= 0; a grid with radius above twice the voxel edge; n < 0 or
+ * >= 2^31; a NULL array with n > 0; a selection of the wrong length.  OCTL_E_STATE: before the first build; a forest
+ * whose rows map_leaf_points moved outside their leaves.  All before anything runs.  n = 0 returns without a kernel.
+ * The index of the blocks by node (octl_forest_nearest's own, under its stamp) is made by the call that finds it
+ * missing, stale or made for another selection; with it in place a call is one kernel, plus one upload, one download
+ * and one wait.  Read-only otherwise.  No reference counterpart.                                                   */
+int octl_forest_radius_count(octl_forest* f, const double* xyz, int64_t n, double radius, int32_t max_count,
+                             const uint8_t* slot_sel, int32_t n_sel, int32_t* count);
+/* The same with pointers from octl_dev_alloc (slot_sel stays a host array): one kernel, nothing is downloaded and
+ * the host does not wait.  No reference counterpart.                                                             */
+int octl_forest_radius_count_device(octl_forest* f, const double* xyz_dev, int64_t n, double radius, int32_t max_count,
+                                    const uint8_t* slot_sel, int32_t n_sel, int32_t* count_dev);
+/* Radius outlier removal: every point x of the leaf-ordered arrays that belongs to a tested pose (slot_sel[slot] != 0;
+ * NULL: every pose; otherwise n_sel = number of poses) and has fewer than min_neighbours OTHER points of the counted
+ * poses (among_sel / n_among likewise) within `radius` is removed.  c(x) = the stored points y of the counted poses
+ * with d2(x, y) <= radius * radius, d2 as octl_forest_radius_count forms it with q = the stored bits of x, and y != x
+ * decided by identity (pose, row), not by distance: a duplicate at the same coordinates is a neighbour, and a tested
+ * pose that is not counted loses nothing to itself.  keep(x) iff c(x) >= min_neighbours (the count saturates there).
+ * Every decision is made on the map as it is before the call - one simultaneous round, not idempotent: a second
+ * call may remove more.  octreelib_amd/query.py: sparse_keep_np is the rule.  Points that a pending RANSAC mask is
+ * about to drop are still in the ordered arrays: they count as neighbours and are judged (octl_forest_filter_count's
+ * rule).  The kernel clears bytes in the mask and the mask is applied as octl_forest_carve applies its own: a pending
+ * RANSAC mask goes into the same ONE compaction.  The scheme stays (voxels and leaves that lose every point stay,
+ * empty: octl_forest_prune drops them); the index of octl_forest_nearest of a surviving row is unchanged; the block
+ * index, the pooled planes, the segments and the adjustment tables go stale as after octl_forest_carve.  *n_alive
+ * (nullable) = points left in the leaf-ordered arrays.
+ * OCTL_E_INVALID: min_neighbours < 1; radius not finite or <= 0; a grid with radius above twice the voxel edge; a
+ * selection of the wrong length.  OCTL_E_STATE: before the first build; a forest whose rows map_leaf_points moved
+ * outside their leaves.  All before anything runs: a refused call leaves points and mask as they were, and every
+ * buffer is reserved before the mask is written.  One wavefront per (leaf, pose) block; with the index of among_sel
+ * in place a call is one kernel (which also writes the ones of a mask that was not pending) and the compaction, plus
+ * one upload and one wait for a tested selection.  No reference counterpart.                                        */
+int octl_forest_remove_sparse(octl_forest* f, double radius, int32_t min_neighbours, const uint8_t* slot_sel,
+                              int32_t n_sel, const uint8_t* among_sel, int32_t n_among, int64_t* n_alive);
 /* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
  * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
  * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in

@@ -730,6 +730,74 @@ class Forest:
             slot = names[slot]
         return Neighbours(slot, index, d2, count)
 
+    def radius_count(self, points, radius, max_count=None, slots=None) -> np.ndarray:
+        """How many stored points of the poses of `slots` (None: all) lie within `radius` of every query point, capped
+        at max_count (None: uncapped): (n,) int32 as query.radius_count_np defines it (octl_forest_radius_count: one
+        kernel once the block index of the selection exists).  points: a host array, or a feed.DeviceCloud of f64
+        points, which is read where it lies."""
+        from octreelib_amd.feed import DeviceCloud
+        from octreelib_amd.query import _as_queries, check_radius_args
+
+        r, max_count, _ = check_radius_args(radius, max_count)
+        cap = 0 if max_count is None else max_count
+        if isinstance(points, DeviceCloud):
+            if np.dtype(points.dtype) != np.float64:
+                raise ValueError("radius_count: a DeviceCloud of float64 points is needed (f32 queries are not "
+                                 "supported)")
+            points.wait()
+            n = len(points)
+            count = np.zeros(n, dtype=np.int32)
+            lib, h = self.lib, self.ctx.handle
+            out = C.c_void_p()
+            self.ctx.check(lib.octl_dev_alloc(h, max(4 * n, 8), C.byref(out)))
+            try:
+                self.radius_count_device(points.ptr, n, r, out, max_count, slots)
+                if n:
+                    self.ctx.check(lib.octl_dev_download(h, nat.ptr(count), out, count.nbytes))
+            finally:
+                lib.octl_dev_free(h, out)
+            return count
+        pts = _as_queries(points)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        n = len(pts)
+        count = np.zeros(n, dtype=np.int32)
+        # (n = 0 still goes to the library: what it refuses whatever the queries is refused for an empty scan too)
+        self.ctx.check(self.lib.octl_forest_radius_count(self.handle, nat.ptr(pts), n, r, cap, nat.ptr(sel), n_sel,
+                                                         nat.ptr(count)))
+        return count
+
+    def radius_count_device(self, xyz_dptr, n: int, radius, count_dptr, max_count=None, slots=None):
+        """radius_count for points that are in device memory already, the (n,) int32 answer left there (pointers from
+        octl_dev_alloc); enqueued on the context's stream, the host does not wait."""
+        from octreelib_amd.query import check_radius_args
+
+        r, max_count, _ = check_radius_args(radius, max_count)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        self.ctx.check(self.lib.octl_forest_radius_count_device(self.handle, xyz_dptr, int(n), r,
+                                                                0 if max_count is None else max_count, nat.ptr(sel),
+                                                                n_sel, count_dptr))
+
+    def remove_sparse(self, radius, min_neighbours, slots=None, among=None) -> int:
+        """Radius outlier removal: every point of the poses of `slots` (None: all) with fewer than min_neighbours other
+        points of the poses of `among` (None: all) within `radius` leaves the map (octl_forest_remove_sparse: one
+        kernel, one compaction that also applies a pending RANSAC mask; query.sparse_keep_np is the rule); the scheme
+        stays.  Returns the number of points removed."""
+        from octreelib_amd.query import _required, check_radius_args
+
+        r, _, m = check_radius_args(radius, None, _required(min_neighbours), what="remove_sparse")
+        self.ensure_built()
+        before = self.n_ord
+        sel, n_sel, _ = self._adjust_selection(slots)
+        asel, n_asel, _ = self._adjust_selection(among)
+        n = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_remove_sparse(self.handle, r, m, nat.ptr(sel), n_sel, nat.ptr(asel), n_asel,
+                                                          C.byref(n)))
+        self.n_ord = n.value
+        self._invalidate()
+        return before - n.value
+
     def _raycast_args(self, max_range, min_range, surface, min_points, max_variance, origins, directions):
         from octreelib_amd.query import check_raycast_args, check_raycast_cap, normalize_directions, ray_inputs
 

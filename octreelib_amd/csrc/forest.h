@@ -314,3 +314,6 @@ int ensure_mask(octl_forest* f);
 // becomes 1), their sizes are added to *removed_dev, and the ONE compaction runs (the host waits for its counts).
 int mask_retire_reserve(octl_forest* f);
 int mask_retire_slots(octl_forest* f, const uint8_t* sel_dev, unsigned long long* removed_dev);
+// mask.hip, for octl_forest_remove_sparse (radius.hip): the ONE compaction over f->mask as it stands (valid: the
+// caller has cleared its bytes in it, a pending RANSAC mask with them); *n_alive (nullable) = points left
+int mask_apply(octl_forest* f, int64_t* n_alive);

@@ -537,6 +537,8 @@ int mask_retire_slots(octl_forest* f, const uint8_t* sel_dev, unsigned long long
   return apply_device_mask(f, nullptr);
 }
 
+int mask_apply(octl_forest* f, int64_t* n_alive) { return apply_device_mask(f, n_alive); }
+
 int forest_settle(octl_forest* f) {
   if (!f->totals_pending) return OCTL_OK;
   octl_ctx* ctx = f->ctx;

@@ -214,6 +214,45 @@ class Grid(GridBase):
         return self._forest.carve_rays(origins, directions, ranges, margin, min_range, returned, min_through,
                                        max_hits, sel)
 
+    def radius_count(self, points, radius, *, max_count: Optional[int] = None,
+                     pose_numbers: Optional[List[int]] = None) -> np.ndarray:
+        """How many stored points of the given poses (None: all) lie within `radius` of every query point: (n,) int32,
+        min(count, max_count) with max_count None: uncapped - density gates, occupancy tests for new scan points,
+        adaptive radii.  The counted points are exactly the candidates of nearest (distance2 <= radius^2 inclusive;
+        what a mask, a filter, carve or remove_poses took out never counts) without its limit of 8; a query that is
+        not finite counts 0; a capped query stops searching at the cap.  points: any (n, 3) array-like, or a
+        DeviceCloud of float64 points, read where it lies.  One kernel once the block index of the selection exists
+        (octreelib_amd/query.py: radius_count_np is the definition, count for count).  ValueError for a radius that
+        is not finite and positive or above twice the voxel edge, or a max_count that is not an integer in
+        1 .. 2^31 - 1; RuntimeError after map_leaf_points moved rows outside their leaves; KeyError for an unknown
+        pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().radius_count(points, radius, max_count=max_count, pose_numbers=sel)
+        return self._forest.radius_count(points, radius, max_count, sel)
+
+    def remove_sparse(self, radius, min_neighbours: int, *, pose_numbers: Optional[List[int]] = None,
+                      among: Optional[List[int]] = None) -> int:
+        """Radius outlier removal: every stored point of the given poses (None: all) that has fewer than
+        min_neighbours OTHER stored points of the poses of `among` (None: all) within `radius` leaves the map - sensor
+        speckle, the halo carve leaves round a removed object, single returns from rain, dust and glass.
+        pose_numbers=[newest], among=None cleans a new scan against the whole map.  A point never counts itself, a
+        duplicate at the same coordinates does; every decision is made on the map as it is before the call (one
+        simultaneous round: a second call may remove more); points a pending RANSAC mask is about to drop still count
+        and are judged, and that mask is applied in the same compaction.  The scheme stays (prune() afterwards drops
+        what became empty), every cached table is dropped, Neighbours.index of the surviving rows is unchanged.  One
+        kernel and the compaction (octreelib_amd/query.py: sparse_keep_np is the rule).  Returns the number of points
+        removed.  ValueError for a radius that is not finite and positive or above twice the voxel edge, or a
+        min_neighbours that is not an integer in 1 .. 2^31 - 1; RuntimeError after map_leaf_points moved rows outside
+        their leaves; KeyError for an unknown pose; NotImplementedError on the caller's own plug types."""
+        if self._plug is not None:
+            raise NotImplementedError(
+                "remove_sparse removes points of the device-resident map: a Grid on the caller's own plug types keeps "
+                "its points in those types on the host (HostMap.remove_sparse gives the decision)")
+        sel = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+        asel = None if among is None else [self._slots[p] for p in among]
+        return self._forest.remove_sparse(radius, min_neighbours, sel, asel)
+
     def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
         """One least-squares plane per leaf over the given poses (None: all), all their points pooled: a LeafPlanes in
         ascending node id.  KeyError for an unknown pose."""

@@ -135,6 +135,18 @@ class Octree(OctreeBase, Generic[T]):
         return self._forest.carve_rays(origins, directions, ranges, margin, min_range, returned, min_through,
                                        max_hits, None)
 
+    def radius_count(self, points, radius, *, max_count=None) -> np.ndarray:
+        """How many stored points lie within `radius` of every query point, capped at max_count ((n,) int32;
+        Grid.radius_count describes it).  One cube has no cap on the radius."""
+        self._query_ready()
+        return self._forest.radius_count(points, radius, max_count, None)
+
+    def remove_sparse(self, radius, min_neighbours) -> int:
+        """Radius outlier removal: every point with fewer than min_neighbours other points within `radius` leaves
+        the octree (Grid.remove_sparse describes it).  Returns the number of points removed."""
+        self._query_ready()
+        return self._forest.remove_sparse(radius, min_neighbours, None, None)
+
     def prune(self):
         """Collapse the subtrees below which no point is left into leaves (a PruneResult; Grid.prune describes it).
         The root always stays: an empty octree becomes its bare root."""

@@ -213,6 +213,30 @@ class OctreeManager(VoxelBase):
         return self._forest.carve_rays(origins, directions, ranges, margin, min_range, returned, min_through,
                                        max_hits, sel)
 
+    def radius_count(self, points, radius, *, max_count: Optional[int] = None,
+                     pose_numbers: Optional[List[int]] = None) -> np.ndarray:
+        """How many stored points of the given poses (None: all) lie within `radius` of every query point, capped at
+        max_count (None: uncapped): (n,) int32; Grid.radius_count describes it (one cube has no cap on the radius).
+        ValueError for a radius that is not finite and positive or a max_count that is not an integer in 1 .. 2^31 - 1;
+        RuntimeError after map_leaf_points moved rows outside their leaves; KeyError for an unknown pose."""
+        sel = self._query_slots(pose_numbers)
+        if self._plug is not None:
+            return self._host_map().radius_count(points, radius, max_count=max_count, pose_numbers=sel)
+        return self._forest.radius_count(points, radius, max_count, sel)
+
+    def remove_sparse(self, radius, min_neighbours: int, *, pose_numbers: Optional[List[int]] = None,
+                      among: Optional[List[int]] = None) -> int:
+        """Radius outlier removal: every point of the given poses (None: all) with fewer than min_neighbours other
+        points of the poses of `among` (None: all) within `radius` leaves the map; Grid.remove_sparse describes it.
+        Returns the number of points removed.  NotImplementedError on the caller's own plug types."""
+        if self._plug is not None:
+            raise NotImplementedError(
+                "remove_sparse removes points of the device-resident map: an OctreeManager on the caller's own plug "
+                "types keeps its points in those types on the host (HostMap.remove_sparse gives the decision)")
+        sel = None if pose_numbers is None else [self._slots[p] for p in pose_numbers]
+        asel = None if among is None else [self._slots[p] for p in among]
+        return self._forest.remove_sparse(radius, min_neighbours, sel, asel)
+
     def leaf_planes(self, pose_numbers: Optional[List[int]] = None) -> LeafPlanes:
         """One least-squares plane per leaf over the given poses (None: all), their points pooled; ascending node id.
         KeyError for an unknown pose."""

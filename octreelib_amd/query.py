@@ -27,10 +27,11 @@ __all__ = ["LeafPlanes", "PointToPlane", "locate_np", "pooled_leaf_statistics_np
            "node_table_from_leaves", "HostMap", "Neighbours", "nearest_np", "NN_MAX_K", "PlaneSegments",
            "SegmentTable", "plane_segments_np", "segment_probes_np", "RayHits", "raycast_np", "normalize_directions",
            "RAY_CAP_EDGES", "RayEvidence", "ray_evidence_np", "carve_keep_np", "evidence_inputs", "PruneResult",
-           "PrunedTables", "prune_np"]
+           "PrunedTables", "prune_np", "radius_count_np", "sparse_keep_np", "sparse_counts_np", "check_radius_args"]
 
 VOX_ABS_LIMIT = 1 << 30   # absolute voxel indices travel as int32
 NN_MAX_K = 8              # OCTL_NN_MAX_K: the largest k of nearest()
+COUNT_MAX = 2 ** 31 - 1   # the largest max_count of radius_count() and min_neighbours of remove_sparse(): int32
 RAY_CAP_EDGES = 256.0     # a grid's raycast: t_max - t_min in voxel edges at most ...
 RAY_T_LIMIT = 2.0 ** 40   # ... and |t_min|, |t_max| in voxel edges at most
 RAY_SURFACES = {"cube": 0, "plane": 1}   # OCTL_RAY_CUBE, OCTL_RAY_PLANE
@@ -235,6 +236,112 @@ def nearest_np(points, clouds, k: int = 1, *, max_distance: float, dtype=np.floa
                 dist2[a + i, :c] = d2[i, cand]
                 count[a + i] = c
     return Neighbours(pose, index, dist2, count)
+
+
+def _count_arg(name, v, what):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= COUNT_MAX:
+        raise ValueError(f"{what}: {name} = {v!r} is not an integer in 1 .. 2^31 - 1")
+    return int(v)
+
+
+def _required(min_neighbours):
+    """min_neighbours of remove_sparse has no default: None is refused as any other value that is not a count."""
+    if min_neighbours is None:
+        raise ValueError("remove_sparse: min_neighbours = None is not an integer in 1 .. 2^31 - 1")
+    return min_neighbours
+
+
+def check_radius_args(radius, max_count=None, min_neighbours=None, what="radius_count"):
+    """(radius, max_count, min_neighbours) as (float, int or None, int or None); ValueError for what radius_count and
+    remove_sparse refuse whatever the map: a radius that is not finite and positive, a max_count or min_neighbours that
+    is given and not an integer in 1 .. 2^31 - 1 (max_count None: uncapped)."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: radius must be finite and positive, got {radius!r}") from None
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"{what}: radius must be finite and positive, got {radius!r}")
+    if max_count is not None:
+        max_count = _count_arg("max_count", max_count, what)
+    if min_neighbours is not None:
+        min_neighbours = _count_arg("min_neighbours", min_neighbours, what)
+    return r, max_count, min_neighbours
+
+
+def radius_count_np(points, clouds, radius, *, max_count=None, dtype=np.float64, chunk: int = 256) -> np.ndarray:
+    """How many stored points lie within `radius` of every query point, by brute force: the definition of
+    radius_count.  clouds: [(pose number, (m, 3) points)] of the counted poses in ascending slot order, as nearest_np
+    takes them.  For query q and stored point p: dx = q_x - p_x (dy, dz likewise), d2 = (dx dx + dy dy) + dz dz in
+    `dtype` with separate products and sums in that order; p counts iff d2 <= r2 = radius * radius (inclusive, r2 formed
+    once) - exactly the candidates of nearest_np.  The answer, (n,) int32, is min(number of counting points,
+    max_count); max_count None: uncapped.  A query with a coordinate that is not finite counts 0."""
+    r, max_count, _ = check_radius_args(radius, max_count)
+    q = _as_queries(points)
+    n = len(q)
+    count = np.zeros(n, dtype=np.int64)
+    parts = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for _, c in clouds]
+    m = sum(len(c) for c in parts)
+    if n == 0 or m == 0:
+        return count.astype(np.int32)
+    P = np.concatenate(parts).astype(dtype)
+    r2 = dtype(r) * dtype(r)
+    ok = np.all(np.isfinite(q), axis=1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for a in range(0, n, chunk):
+            qa = q[a: a + chunk].astype(dtype)
+            dx = qa[:, None, 0] - P[None, :, 0]
+            dy = qa[:, None, 1] - P[None, :, 1]
+            dz = qa[:, None, 2] - P[None, :, 2]
+            d2 = (dx * dx + dy * dy) + dz * dz
+            count[a: a + chunk] = np.count_nonzero(d2 <= r2, axis=1)
+    count[~ok] = 0
+    if max_count is not None:
+        count = np.minimum(count, max_count)
+    return count.astype(np.int32)
+
+
+def sparse_counts_np(clouds, tested, radius, *, dtype=np.float64, chunk: int = 256):
+    """c(x) of sparse_keep_np for every judged point: a list of (m,) int64 arrays in the order of sparse_keep_np's
+    answer (an untested cloud's entry is None)."""
+    r, _, _ = check_radius_args(radius, what="remove_sparse")
+    names = [int(p) for p, _ in clouds]
+    parts = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for _, c in clouds]
+    chosen, extra = (set(names), []) if tested is None else (set(), [])
+    for t in (() if tested is None else tested):
+        if isinstance(t, (int, np.integer)):
+            if int(t) not in names:
+                raise ValueError(f"remove_sparse: tested pose {t!r} is not among the counted clouds and brings no points")
+            chosen.add(int(t))
+        else:
+            p, pts = t
+            if int(p) in names:
+                raise ValueError(f"remove_sparse: tested pose {p!r} is among the counted clouds: name it by its number")
+            extra.append(np.asarray(pts, dtype=np.float64).reshape(-1, 3))
+
+    def counts(X, own):
+        c = radius_count_np(X, clouds, r, dtype=dtype, chunk=chunk).astype(np.int64)
+        # y != x by identity: among the counted points x itself is the one candidate taken out, and it IS one exactly
+        # when x is finite (dx = dy = dz = 0, d2 = 0 <= r2); a duplicate of x is another row and stays counted
+        return c - np.all(np.isfinite(X), axis=1) if own else c
+
+    return [counts(X, True) if p in chosen else None for p, X in zip(names, parts)] + [counts(X, False) for X in extra]
+
+
+def sparse_keep_np(clouds, tested, radius, min_neighbours, *, dtype=np.float64, chunk: int = 256):
+    """The rule of remove_sparse (radius outlier removal): which stored points stay.  clouds: [(pose number, (m, 3)
+    points)] of the COUNTED poses in ascending slot order; tested: the poses whose points are judged - pose numbers
+    among `clouds` (None: all of them) and, for a tested pose that is not counted, a (pose number, points) pair.  For a
+    stored point x of a tested pose, c(x) = the number of stored points y of the counted poses with d2(x, y) <= r2 and
+    y != x: q = x in the formula of radius_count_np, the same r2, the same inclusive test, and y != x decided BY
+    IDENTITY (pose, row), not by distance - a duplicate at the same coordinates is a neighbour, and a tested pose that
+    is not counted has no point of its own to exclude.  keep(x) iff c(x) >= min_neighbours.  Every decision is made on
+    the clouds as given: one simultaneous round (not idempotent: a second round may remove more).  Answer: one bool
+    array per cloud in the order of `clouds` (all True for a cloud that is not tested), then one per (pose number,
+    points) pair in the order given."""
+    _, _, m = check_radius_args(radius, None, _required(min_neighbours), what="remove_sparse")
+    cs = sparse_counts_np(clouds, tested, radius, dtype=dtype, chunk=chunk)
+    sizes = [len(np.asarray(c).reshape(-1, 3)) for _, c in clouds]
+    return [np.ones(sizes[i], dtype=bool) if c is None else c >= m for i, c in enumerate(cs)]
 
 
 @dataclass
@@ -920,6 +1027,35 @@ class HostMap:
         if self.mode == 0 and r > 2.0 * self.edge:
             raise ValueError(f"nearest: max_distance {r} exceeds twice the voxel edge {self.edge}")
         return nearest_np(points, self.clouds(pose_numbers), k, max_distance=r)
+
+    def _radius_cap(self, r, what):
+        if self.mode == 0 and r > 2.0 * self.edge:
+            raise ValueError(f"{what}: radius {r} exceeds twice the voxel edge {self.edge}")
+
+    def radius_count(self, points, radius, *, max_count=None, pose_numbers=None) -> np.ndarray:
+        r, max_count, _ = check_radius_args(radius, max_count)
+        self._radius_cap(r, "radius_count")
+        return radius_count_np(points, self.clouds(pose_numbers), r, max_count=max_count)
+
+    def remove_sparse(self, radius, min_neighbours, *, pose_numbers=None, among=None):
+        """The decision of remove_sparse over the map as it stands: [(pose number, keep)] for every tested pose
+        (pose_numbers, None: all) in the order the poses were inserted, keep one bool per row of clouds([pose]).  These
+        classes only know a pose through the caller's leaves, so nothing is removed here: the caller applies it."""
+        r, _, m = check_radius_args(radius, None, _required(min_neighbours), what="remove_sparse")
+        self._radius_cap(r, "remove_sparse")
+        counted = self.clouds(among)
+        have = {p for p, _ in counted}
+        tested = [t if t[0] not in have else t[0] for t in self.clouds(pose_numbers)]
+        keep = sparse_keep_np(counted, tested, r, m)
+        by_name = {p: keep[i] for i, (p, _) in enumerate(counted)}
+        out, extra = [], len(counted)
+        for t in tested:
+            if isinstance(t, tuple):
+                out.append((t[0], keep[extra]))
+                extra += 1
+            else:
+                out.append((t, by_name[t]))
+        return out
 
     def _point_clouds(self, max_distance, pose_numbers):
         _, r = check_nearest_args(1, max_distance)
