@@ -559,6 +559,43 @@ int octl_forest_point_registration_system_device(octl_forest* f, const double* x
                                                  const uint8_t* slot_sel, int32_t n_sel, double* sys_dev,
                                                  int64_t* counts_dev, int32_t* slot_dev, int64_t* index_dev,
                                                  double* distance2_dev);
+/* The nearest-point-to-plane normal equations of a scan, for ONE rigid transform: the correspondence of
+ * octl_forest_point_registration_system, the residual of octl_forest_registration_system - what LiDAR odometry uses
+ * (octreelib_amd/registration.py: nearest_plane_registration_system_np is the definition of every number below).  T,
+ * origin = c and p as above.  Per query: the stored point m of the poses of slot_sel / n_sel (NULL: all) nearest to p
+ * within max_distance, exactly as octl_forest_nearest answers it for k = 1; node = the scheme leaf m lies in (as
+ * octl_forest_locate answers it for m; -1 without a match) - NOT the leaf of p; row and r = the residual of p against
+ * the pooled plane of `node` under the gates min_points / max_variance, as octl_forest_point_to_plane forms them for a
+ * point of that leaf (row -1 and r NaN where the leaf has no accepted plane).  The point is USED iff row >= 0 and r is
+ * finite; J, the Huber weight on |r| and the 28 sums are those of octl_forest_registration_system (csrc/
+ * reg_plane_term.h is the code of both); counts[0] = used points, counts[1] = queries with a correspondence (node >=
+ * 0).  max_distance is the search radius alone: there is no gate on |r|.  slot / index / distance2 / node / row /
+ * residual: all six NULL, or all six given and then written for every query (-1, -1, +inf, -1, -1, NaN where nothing
+ * lies within max_distance).  The sums are reduced in the tree of octl_forest_registration_system (a function of n
+ * alone), with its bound.  n = 0: no launch, sys = +0.0, counts = 0.  Refused before anything runs, the forest as it
+ * was: what octl_forest_nearest refuses, in its order (OCTL_E_STATE before build; OCTL_E_INVALID for n >= 2^31, a NULL
+ * pointer, a subset of the six per-point pointers, a max_distance that is not finite and positive or above twice the
+ * voxel edge, a selection of the wrong length; OCTL_E_STATE after map_leaf_points moved rows outside their leaves);
+ * OCTL_E_INVALID for a non-finite T or origin; OCTL_E_STATE when the pooled leaf planes are missing or stale, or were
+ * made for another pose selection than slot_sel (planes and points must come from the same poses: call
+ * octl_forest_pooled_leaf_stats with this selection first).  Three kernels (the block index of the selection is made
+ * first when it is missing or stale); the host form adds one upload, the 240-byte download and one wait.  Read-only.
+ * No reference counterpart.                                                                                          */
+int octl_forest_nearest_plane_registration_system(octl_forest* f, const double* xyz, int64_t n, const double T[12],
+                                                  const double origin[3], double max_distance, double huber_delta,
+                                                  const uint8_t* slot_sel, int32_t n_sel, int32_t min_points,
+                                                  double max_variance, double sys[28], int64_t counts[2],
+                                                  int32_t* slot, int64_t* index, double* distance2, int32_t* node,
+                                                  int32_t* row, double* residual);
+/* The same with pointers from octl_dev_alloc (T, origin and slot_sel stay host arrays); no host wait.  n = 0: sys_dev
+ * and counts_dev are zeroed by two fills.  No reference counterpart.                                                 */
+int octl_forest_nearest_plane_registration_system_device(octl_forest* f, const double* xyz_dev, int64_t n,
+                                                         const double T[12], const double origin[3],
+                                                         double max_distance, double huber_delta,
+                                                         const uint8_t* slot_sel, int32_t n_sel, int32_t min_points,
+                                                         double max_variance, double* sys_dev, int64_t* counts_dev,
+                                                         int32_t* slot_dev, int64_t* index_dev, double* distance2_dev,
+                                                         int32_t* node_dev, int32_t* row_dev, double* residual_dev);
 /* Multi-pose plane adjustment: for ONE rigid transform PER selected pose, the point-to-plane normal equations of every
  * pose against the leaf planes pooled at those transforms - what one block-Jacobi iteration of a sliding-window plane
  * adjustment needs from the device (the 6x6 solves and the iteration are the caller's; octreelib_amd/adjustment.py has

@@ -20,8 +20,10 @@ from octreelib_amd.query import (LeafPlanes, Neighbours, PlaneSegments, PointToP
                                  RayHits, carve_keep_np, locate_np, nearest_np, normalize_directions, plane_segments_np,
                                  point_to_plane_np, pooled_leaf_statistics_np, prune_np, radius_count_np, ray_evidence_np,
                                  raycast_np, sparse_keep_np)
-from octreelib_amd.registration import (Alignment, RegistrationSystem, align_np, point_registration_system_np,
-                                        registration_system_np, se3_exp, transform_np, transform_rows_np)
+from octreelib_amd.matching import align_nearest_planes, nearest_plane_registration_system
+from octreelib_amd.registration import (Alignment, RegistrationSystem, align_np, nearest_plane_registration_system_np,
+                                        point_registration_system_np, registration_system_np, se3_exp, transform_np,
+                                        transform_rows_np)
 
 __version__ = "0.1.0"
 __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "LeafPlanes",
@@ -31,4 +33,5 @@ __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empt
            "AdjustmentLeaves", "BlockMoments", "adjustment_system_np", "adjust_np", "block_moments_np", "Neighbours",
            "nearest_np", "PlaneSegments", "plane_segments_np", "RayHits", "raycast_np", "normalize_directions",
            "RayEvidence", "ray_evidence_np", "carve_keep_np", "PruneResult", "prune_np", "radius_count_np",
-           "sparse_keep_np", "__version__"]
+           "sparse_keep_np", "nearest_plane_registration_system_np", "nearest_plane_registration_system",
+           "align_nearest_planes", "__version__"]

@@ -1177,6 +1177,119 @@ class Forest:
             if out.value:
                 lib.octl_dev_free(h, out)
 
+    # -- nearest-point-to-plane registration (registration.nearest_plane_registration_system_np is the definition) -----
+    def nearest_plane_registration_system(self, points, transform=None, origin=None, slots=None, max_distance=None,
+                                          min_points: int = 8, max_variance=None, huber_delta=None,
+                                          per_point: bool = False, pose_of_slot=None):
+        """The point-to-plane normal equations of a scan under `transform`, every point scored against the pooled
+        plane of the leaf its nearest stored point of the poses of `slots` (None: all) lies in
+        (octl_forest_nearest_plane_registration_system: three kernels once the tables of the selection exist, one
+        host wait); origin None: the centroid of the transformed scan.  per_point: neighbours (the answers of nearest
+        with k = 1 for the transformed scan, the pose column named through pose_of_slot), node, row, residual and
+        planes come back with the system."""
+        from octreelib_amd.query import Neighbours, _as_queries, check_nearest_args
+        from octreelib_amd.registration import default_origin, system_from_sums
+
+        check_nearest_args(1, max_distance)
+        pts = _as_queries(points)
+        if origin is None:
+            origin = default_origin(transform, pts)
+        T12, c, r, hd = self._regp_args(transform, origin, max_distance, huber_delta)
+        planes = self.leaf_planes(slots)
+        sel, n_sel, _ = self._adjust_selection(slots)
+        mv = -1.0 if max_variance is None else float(max_variance)
+        n = len(pts)
+        sums = np.empty(28, dtype=np.float64)
+        counts = np.empty(2, dtype=np.int64)
+        slot = np.full((n, 1), -1, dtype=np.int32) if per_point else None
+        index = np.full((n, 1), -1, dtype=np.int64) if per_point else None
+        d2 = np.full((n, 1), np.inf, dtype=np.float64) if per_point else None
+        node = np.full(n, -1, dtype=np.int32) if per_point else None
+        row = np.full(n, -1, dtype=np.int32) if per_point else None
+        res = np.full(n, np.nan, dtype=np.float64) if per_point else None
+        # (n = 0 still goes to the library: what it refuses whatever the scan is refused for an empty one too)
+        self.ctx.check(self.lib.octl_forest_nearest_plane_registration_system(
+            self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), r, hd, nat.ptr(sel), n_sel, int(min_points), mv,
+            nat.ptr(sums), nat.ptr(counts), nat.ptr(slot), nat.ptr(index), nat.ptr(d2), nat.ptr(node), nat.ptr(row),
+            nat.ptr(res)))
+        out = system_from_sums(sums, counts, c)
+        if per_point:
+            count = (slot[:, 0] >= 0).astype(np.int32)
+            if pose_of_slot is not None and slot.size:
+                names = np.asarray(list(pose_of_slot) + [-1], dtype=np.int32)   # (-1 pads index the last entry)
+                slot = names[slot]
+            out.neighbours = Neighbours(slot, index, d2, count)
+            out.node, out.row, out.residual, out.planes = node, row, res, planes
+        return out
+
+    def nearest_plane_registration_system_device(self, xyz_dptr, n: int, transform, origin, sys_dptr, counts_dptr,
+                                                 max_distance=None, min_points: int = 8, max_variance=None,
+                                                 huber_delta=None, slots=None, slot_dptr=None, index_dptr=None,
+                                                 d2_dptr=None, node_dptr=None, row_dptr=None, residual_dptr=None):
+        """nearest_plane_registration_system against the pooled table the device holds (leaf_planes(slots) first), for
+        points that are in device memory already, device pointers in and out (28 f64 and 2 i64; slot i32, index i64,
+        distance2 f64, node i32, row i32 and residual f64 per point, all six or none); the host does not wait."""
+        T12, c, r, hd = self._regp_args(transform, origin, max_distance, huber_delta)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        mv = -1.0 if max_variance is None else float(max_variance)
+        self.ctx.check(self.lib.octl_forest_nearest_plane_registration_system_device(
+            self.handle, xyz_dptr, int(n), nat.ptr(T12), nat.ptr(c), r, hd, nat.ptr(sel), n_sel, int(min_points), mv,
+            sys_dptr, counts_dptr, slot_dptr, index_dptr, d2_dptr, node_dptr, row_dptr, residual_dptr))
+
+    def align_nearest_planes(self, points, initial=None, slots=None, max_distance=None, min_points: int = 8,
+                             max_variance=None, huber_delta=None, max_iterations: int = 20, tolerance: float = 1e-9,
+                             damping: float = 0.0):
+        """Gauss-Newton scan-to-map alignment, nearest stored point to the plane of its leaf (registration.align_np
+        over nearest_plane_registration_system): the pooled planes and the block index are made once, the scan is
+        uploaded once - or is a feed.DeviceCloud of f64 points, read where it lies - and every iteration is the
+        device form on the resident scan plus one download of the 28 + 2 numbers (three launches, one host wait,
+        whatever the size of the scan)."""
+        from octreelib_amd.feed import DeviceCloud
+        from octreelib_amd.query import _as_queries, check_nearest_args
+        from octreelib_amd.registration import align_np, default_origin, system_from_sums
+
+        check_nearest_args(1, max_distance)
+        lib, h = self.lib, self.ctx.handle
+        scan, out = C.c_void_p(), C.c_void_p()
+        resident = isinstance(points, DeviceCloud)
+        if resident:
+            if np.dtype(points.dtype) != np.float64:
+                raise ValueError("align_nearest_planes: a DeviceCloud of float64 points is needed (f32 queries are not "
+                                 "supported)")
+            points.wait()
+            n, scan = len(points), points.ptr
+            pts = np.empty((n, 3), dtype=np.float64)     # (the origin of the first iteration needs the points once)
+            if n:
+                self.ctx.check(lib.octl_dev_download(h, nat.ptr(pts), scan, pts.nbytes))
+        else:
+            pts = _as_queries(points)
+            n = len(pts)
+        self.leaf_planes(slots)
+        if not resident:
+            self.ctx.check(lib.octl_dev_alloc(h, max(pts.nbytes, 8), C.byref(scan)))
+        try:
+            self.ctx.check(lib.octl_dev_alloc(h, 256, C.byref(out)))
+            if n and not resident:
+                self.ctx.check(lib.octl_dev_upload(h, scan, nat.ptr(pts), pts.nbytes))
+            counts_dptr = C.c_void_p(out.value + 28 * 8)
+            buf = np.empty(30, dtype=np.float64)
+
+            def system(T, origin):
+                if origin is None:
+                    origin = default_origin(T, pts)
+                self.nearest_plane_registration_system_device(scan, n, T, origin, out, counts_dptr, max_distance,
+                                                              min_points, max_variance, huber_delta, slots)
+                self.ctx.check(lib.octl_dev_download(h, nat.ptr(buf), out, buf.nbytes))
+                return system_from_sums(buf[:28].copy(), buf[28:].view(np.int64), origin)
+
+            return align_np(system, initial, max_iterations, tolerance, damping)
+        finally:
+            if not resident:
+                lib.octl_dev_free(h, scan)    # (back to the context's pool: no hipFree on the scan path)
+            if out.value:
+                lib.octl_dev_free(h, out)
+
     # -- plane adjustment (octreelib_amd/adjustment.py is the host definition) ---------------------------------------------
     def _adjust_selection(self, slots):
         """(selection mask or None, its length, the selected slots in ascending order)"""

@@ -125,6 +125,12 @@ SIGNATURES = {
                                               [_p, _p, _i64, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p, _p, _p]),
     "octl_forest_point_registration_system_device": (C.c_int,
                                                      [_p, _p, _i64, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p, _p, _p]),
+    "octl_forest_nearest_plane_registration_system": (C.c_int,
+                                                      [_p, _p, _i64, _p, _p, _f64, _f64, _p, _i32, _i32, _f64, _p, _p,
+                                                       _p, _p, _p, _p, _p, _p]),
+    "octl_forest_nearest_plane_registration_system_device": (C.c_int,
+                                                             [_p, _p, _i64, _p, _p, _f64, _f64, _p, _i32, _i32, _f64,
+                                                              _p, _p, _p, _p, _p, _p, _p, _p]),
     "octl_forest_adjustment_system": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _i32, _f64, _p, _p, _p]),
     "octl_forest_adjustment_tables": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _pi64, _i64, _p, _p, _p, _pi64]),
     "octl_forest_transform_poses": (C.c_int, [_p, _p, _i32, _p]),

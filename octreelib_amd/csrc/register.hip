@@ -28,6 +28,7 @@
 #include "forest.h"
 #include "query_walk.h"
 #include "reg_fold.h"
+#include "reg_plane_term.h"
 
 namespace {
 
@@ -70,28 +71,7 @@ __global__ __launch_bounds__(256) void k_reg_partial(const double* __restrict__ 
     const double ar = fabs(r);
     if (!(row >= 0 && ar < INFINITY && !(P.max_distance >= 0.0 && ar > P.max_distance))) continue;  // (NaN: unused)
     a.used += 1;
-    const double dx = px - P.c[0], dy = py - P.c[1], dz = pz - P.c[2];
-    double J[6];
-    J[0] = fma(dy, nrm[2], -(dz * nrm[1]));
-    J[1] = fma(dz, nrm[0], -(dx * nrm[2]));
-    J[2] = fma(dx, nrm[1], -(dy * nrm[0]));
-    J[3] = nrm[0];
-    J[4] = nrm[1];
-    J[5] = nrm[2];
-    const bool tail = P.huber_delta > 0.0 && ar > P.huber_delta;
-    const double w = tail ? P.huber_delta / ar : 1.0;
-    int k = 0;
-#pragma unroll
-    for (int u = 0; u < 6; ++u) {
-      const double wj = w * J[u];
-#pragma unroll
-      for (int v = u; v < 6; ++v, ++k) a.s[k] = fma(wj, J[v], a.s[k]);
-      a.s[21 + u] = fma(wj, r, a.s[21 + u]);
-    }
-    if (tail)
-      a.s[27] += P.huber_delta * (ar - 0.5 * P.huber_delta);
-    else
-      a.s[27] = fma(0.5 * r, r, a.s[27]);
+    reg_plane_term(px, py, pz, P.c, nrm, r, ar, P.huber_delta, a.s);  // (reg_plane_term.h fixes the operation order)
   }
   reg_block_reduce(a, lds, ldc);
   double* out = rows + (int64_t)blockIdx.x * RS_ROW;

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "forest.h"
 #include "nearest_walk.h"
+#include "reg_best.h"
 #include "reg_fold.h"
 #include "reg_point_term.h"
 
@@ -39,28 +40,7 @@ struct RegPointParams {
   double delta2;
 };
 
-// the best candidate of a walk with k = 1, and where it lies in the ordered arrays
-struct RegBest {
-  double bd;
-  uint64_t bid;
-  uint32_t pos;
-  __device__ __forceinline__ double worst() const { return bd; }
-  __device__ __forceinline__ void offer(double d2, uint64_t id, uint32_t at) {
-    if (cand_less(d2, id, bd, bid)) {
-      bd = d2;
-      bid = id;
-      pos = at;
-    }
-  }
-};
-
-__device__ __forceinline__ void reg_transform(const double* __restrict__ T, double qx, double qy, double qz,
-                                              double p[3]) {
-  // (separate products and sums: the library is built with -ffp-contract=off, and the host forms the same bits)
-  p[0] = ((T[0] * qx + T[1] * qy) + T[2] * qz) + T[3];
-  p[1] = ((T[4] * qx + T[5] * qy) + T[6] * qz) + T[7];
-  p[2] = ((T[8] * qx + T[9] * qy) + T[10] * qz) + T[11];
-}
+// (RegBest, the k = 1 sink, and reg_transform: reg_best.h - register_nearest_plane.hip matches with the same)
 
 template <bool PER_POINT>
 __global__ __launch_bounds__(256) void k_reg_match(const double* __restrict__ xyz, int64_t n, RegPointParams P, double r,

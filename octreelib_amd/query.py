@@ -1057,10 +1057,10 @@ class HostMap:
                 out.append((t, by_name[t]))
         return out
 
-    def _point_clouds(self, max_distance, pose_numbers):
+    def _point_clouds(self, max_distance, pose_numbers, what="point_registration_system"):
         _, r = check_nearest_args(1, max_distance)
         if self.mode == 0 and r > 2.0 * self.edge:
-            raise ValueError(f"point_registration_system: max_distance {r} exceeds twice the voxel edge {self.edge}")
+            raise ValueError(f"{what}: max_distance {r} exceeds twice the voxel edge {self.edge}")
         return r, self.clouds(pose_numbers)
 
     def point_registration_system(self, points, transform=None, *, max_distance, pose_numbers=None, huber_delta=None,
@@ -1078,6 +1078,30 @@ class HostMap:
         r, clouds = self._point_clouds(max_distance, pose_numbers)   # (once: the map does not change meanwhile)
         pts = _as_queries(points)
         system = lambda T, c: point_registration_system_np(clouds, pts, T, c, max_distance=r, huber_delta=huber_delta)
+        return align_np(system, initial, max_iterations, tolerance, damping)
+
+    def nearest_plane_registration_system(self, points, transform=None, *, max_distance, pose_numbers=None,
+                                          min_points=8, max_variance=None, huber_delta=None, origin=None,
+                                          per_point=False):
+        from octreelib_amd.registration import nearest_plane_registration_system_np
+
+        r, clouds = self._point_clouds(max_distance, pose_numbers, "nearest_plane_registration_system")
+        return nearest_plane_registration_system_np(self.locate, self.leaf_planes(pose_numbers), clouds, points,
+                                                    transform, origin, max_distance=r, min_points=min_points,
+                                                    max_variance=max_variance, huber_delta=huber_delta,
+                                                    per_point=per_point)
+
+    def align_nearest_planes(self, points, initial=None, *, max_distance, pose_numbers=None, min_points=8,
+                             max_variance=None, huber_delta=None, max_iterations=20, tolerance=1e-9, damping=0.0):
+        from octreelib_amd.registration import align_np, nearest_plane_registration_system_np
+
+        # (once: the map does not change while a scan is aligned)
+        r, clouds = self._point_clouds(max_distance, pose_numbers, "nearest_plane_registration_system")
+        planes = self.leaf_planes(pose_numbers)
+        pts = _as_queries(points)
+        system = lambda T, c: nearest_plane_registration_system_np(
+            self.locate, planes, clouds, pts, T, c, max_distance=r, min_points=min_points, max_variance=max_variance,
+            huber_delta=huber_delta)
         return align_np(system, initial, max_iterations, tolerance, damping)
 
     def raycast(self, origins, directions, max_range, *, min_range=0.0, pose_numbers=None, surface="cube",

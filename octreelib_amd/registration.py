@@ -2,7 +2,9 @@
 Scan-to-map registration against the pooled leaf planes: the point-to-plane normal equations of a scan under a rigid
 transform (registration_system), and the Gauss-Newton loop over them (align).  Further down the same against the
 nearest stored points - classic ICP where the map has no planes to offer (point_registration_system, align_points:
-point_registration_system_np is their definition).
+point_registration_system_np is their definition), and the two combined: the correspondence of the nearest stored
+point, the residual against the plane of that point's leaf (nearest_plane_registration_system, align_nearest_planes
+in octreelib_amd/matching.py: nearest_plane_registration_system_np is their definition).
 
 The device reduces a scan to the 6x6 system - 28 sums and two counts (octl_forest_registration_system, csrc/
 register.hip); the solve, the pose update and the loop are NumPy on the host (one download of 240 bytes per iteration).
@@ -28,7 +30,8 @@ from octreelib_amd.query import LeafPlanes, Neighbours, _as_queries, check_neare
 
 __all__ = ["RegistrationSystem", "Alignment", "as_transform", "transform_np", "transform_rows_np",
            "as_transform_rows", "default_origin", "se3_exp",
-           "system_from_sums", "registration_system_np", "point_registration_system_np", "align_np"]
+           "system_from_sums", "registration_system_np", "point_registration_system_np",
+           "nearest_plane_registration_system_np", "align_np"]
 
 _TRIU = np.triu_indices(6)
 
@@ -319,6 +322,61 @@ def point_registration_system_np(clouds, points, transform=None, origin=None, *,
             sm(gw[:, 0]), sm(gw[:, 1]), sm(gw[:, 2]), sm(we[:, 0]), sm(we[:, 1]), sm(we[:, 2]),
             sm(rho)], dtype=dtype)
     out = system_from_sums(sums, (int(used.sum()), n_located), c)
+    if per_point:
+        out.neighbours = nb
+    return out
+
+
+def nearest_plane_registration_system_np(locate: Callable, planes: LeafPlanes, clouds, points, transform=None,
+                                         origin=None, *, max_distance: float, min_points: int = 8,
+                                         max_variance: Optional[float] = None, huber_delta: Optional[float] = None,
+                                         dtype=np.float64, answers=None,
+                                         per_point: bool = False) -> RegistrationSystem:
+    """The nearest-point-to-plane normal equations of a scan, on the host: the definition of
+    nearest_plane_registration_system (octl_forest_nearest_plane_registration_system, csrc/
+    register_nearest_plane.hip).  The correspondence of point_registration_system_np, the residual of
+    registration_system_np - a composition of the definitions above, with no arithmetic of its own.  locate: points
+    (n, 3) -> node ids; planes: the pooled table; clouds: [(pose number, (m, 3) points)] in ascending slot order -
+    planes and clouds over the SAME pose selection.  Per query q, with T = (R, t) and r = max_distance:
+
+      p = transform_np(T, q)
+      nb = nearest_np(p, clouds, 1, max_distance=r)            the correspondence of nearest(..., k=1): the same d2
+                                                               bits, the same total order (d2, slot, index)
+      m = the matched stored point, bit for bit; node = locate(m), the scheme leaf the MATCHED POINT lies in, -1
+      where there is no match - not locate(p)
+      row, residual = point_to_plane_np(node, planes, p, min_points, max_variance)
+                                                               the signed distance of the QUERY p to the pooled plane
+                                                               of the matched point's leaf; -1 and NaN where that
+                                                               leaf has no accepted plane
+      the system = registration_system_np(..., answers=(node, row, residual), max_distance=None,
+      huber_delta=huber_delta): J, the Huber rule on |residual|, the 28 sums and n_used unchanged; n_located = the
+      queries that found a correspondence (node >= 0).
+
+    max_distance is the search radius only: there is no gate on |residual|.  answers = (Neighbours, node, row,
+    residual): take these per-point answers as given - the reference of a sum over exactly the terms another
+    implementation selected.  per_point: .neighbours, .node, .row, .residual and .planes come back."""
+    _, r = check_nearest_args(1, max_distance)
+    R, t = as_transform(transform)
+    T = _matrix(R, t)
+    q = _as_queries(points)
+    if answers is None:
+        p = transform_np(T, q)
+        clouds = [(int(k), np.asarray(a, dtype=np.float64).reshape(-1, 3)) for k, a in clouds]
+        nb = nearest_np(p, clouds, 1, max_distance=r)
+        used = np.asarray(nb.count).reshape(-1) > 0
+        pose, index = np.asarray(nb.pose).reshape(-1)[used], np.asarray(nb.index).reshape(-1)[used]
+        m = np.empty((int(used.sum()), 3))
+        for k, a in clouds:
+            of = pose == k
+            m[of] = a[index[of]]
+        node = np.full(len(p), -1, dtype=np.int32)
+        if len(m):
+            node[used] = np.asarray(locate(m), dtype=np.int32)
+        row, res = point_to_plane_np(node, planes, p, min_points, max_variance)
+    else:
+        nb, node, row, res = answers
+    out = registration_system_np(None, planes, q, T, origin, min_points, max_variance, None, huber_delta, dtype,
+                                 answers=(node, row, res), per_point=per_point)
     if per_point:
         out.neighbours = nb
     return out
