@@ -39,8 +39,21 @@ cloud as given and keeps numbering its rows as given), carve (rays from evidence
 with ray_evidence_np over its own scheme leaves and applies carve_keep_np as one oracle apply_mask per pose),
 remove_poses with its refused form (the oracle trees of the poses go, the scheme trees and the voxels stay, the
 numbers are free again), and the read-only ray_evidence and store_size.  SEEDS and SEEDS2 keep the logs they had.
+The fourth generation (SEEDS4, _Generator4) adds the scheme pruned and the radius searches: prune (the model prunes
+its own oracle trees by the definition of DESIGN 4.18 - a grid's voxel without a point of any pose leaves the map, the
+topmost internal nodes without one become leaves in the scheme tree and in every pose tree - books the five numbers
+of the PruneResult, keeps the pooled table valid exactly when nothing was dropped, and carries stored evidence over by
+the rule of RayEvidence.remapped: a carve record with "remapped" takes it), remove_sparse (sparse_keep_np on the
+model's rows, tile by tile, applied as one oracle apply_mask per judged pose; the rows that left are booked), and
+the read-only radius_count (counted by the model itself with radius_count_np: the count has no order),
+point_registration_system and nearest_plane_registration_system (scans of jittered stored rows under a motion from the
+identity to right out of the scene; n_used and n_located are booked).  An insert or extend that puts a row into a
+node a prune has collapsed is Rejected - nothing defines where such a node stands in a pose's leaf list once it is
+filled again - until a transform_poses has rebuilt the map; an insert into a voxel a prune has dropped is in the
+domain: the voxel is created anew at the end of the creation order.  SEEDS, SEEDS2 and SEEDS3 keep the logs they had.
 """
 
+import collections
 import functools
 
 import numpy as np
@@ -65,8 +78,12 @@ NEW_READ_ONLY = ("nearest", "raycast", "plane_segments", "registration_system", 
 GEN3_MUTATING = ("insert_moved", "extend_moved", "carve", "remove_poses", "remove_poses_refused")
 GEN3_READ_ONLY = ("ray_evidence", "store_size")
 REFUSED = ("transform_poses_refused", "remove_poses_refused")      # raise in the library: nothing changes, nothing is invalidated
-ALL_MUTATING = MUTATING + NEW_MUTATING + GEN3_MUTATING
-ALL_READ_ONLY = READ_ONLY + NEW_READ_ONLY + GEN3_READ_ONLY
+# the fourth generation (SEEDS4): the radius neighbour counts, the scheme pruned, the two nearest-point registrations
+GEN4_MUTATING = ("remove_sparse", "prune")
+GEN4_READ_ONLY = ("radius_count", "point_registration_system", "nearest_plane_registration_system")
+GEN3_ALL_READ_ONLY = READ_ONLY + NEW_READ_ONLY + GEN3_READ_ONLY      # (what the third generation draws its reads from)
+ALL_MUTATING = MUTATING + NEW_MUTATING + GEN3_MUTATING + GEN4_MUTATING
+ALL_READ_ONLY = GEN3_ALL_READ_ONLY + GEN4_READ_ONLY
 SUBDIVIDES = ("subdivide_count", "subdivide_planar_count", "subdivide_planar", "subdivide_callable")
 FILTERS = ("filter_count", "filter_opaque", "filter_subset")
 TRANSITIONS = ("ransac>leaf_planes", "ransac>subdivide", "ransac>insert", "filter>insert", "filter>point_to_plane",
@@ -86,6 +103,19 @@ TRANSITIONS3 = ("carve>remove_poses(carved pose)", "ransac>carve", "carve>plane_
                 "remove_poses(scheme-driving subset)>subdivide_planar_count>split_stats", "remove_poses>remove_poses",
                 "insert_moved(late, piecewise)>nearest", "extend_moved>leaf_statistics",
                 "adjustment_system>remove_poses>adjustment_system")
+SEEDS4 = list(range(300, 324))      # container, first subdivision and motifs by (seed - 300)
+TRANSITIONS4 = ("leaf_planes(S)>prune(changes)>point_to_plane(S)", "leaf_planes(S)>prune(no-op)>point_to_plane(S)",
+                "plane_segments>prune>plane_segments", "nearest>prune>nearest",
+                "adjustment_system>prune(drops an outermost voxel)>adjustment_system(origin None)",
+                "subdivide_planar>prune>split_stats", "ray_evidence>prune>carve(evidence_from, remapped)",
+                "prune(drops a voxel)>insert(into it)>subdivide>ransac", "remove_poses>prune>insert(freed number)",
+                "carve>prune>transform_poses>subdivide", "prune>prune", "radius_count(S)>remove_sparse>radius_count(S)",
+                "remove_sparse>nearest", "remove_sparse(pose subset, among subset)>prune",
+                "plane_segments>remove_sparse>plane_segments", "adjustment_system>remove_sparse>adjustment_system",
+                "nearest(S)>point_registration_system(S')>nearest(S)",
+                "leaf_planes(S)>nearest_plane_registration_system(S')>point_to_plane(S)",
+                "nearest_plane_registration_system>remove_sparse>nearest_plane_registration_system",
+                "point_registration_system>prune>point_registration_system")
 # container and motif (index into TRANSITIONS) by seed % 12; the second entry is for seeds >= 12
 _CONTAINER = {0: "grid", 1: "grid", 2: "grid", 3: "manager", 4: ("octree", "octree"), 5: ("octree", "grid"), 6: "grid",
               7: "manager", 8: ("grid", "manager"), 9: ("manager", "octree"), 10: "grid", 11: "grid"}
@@ -287,6 +317,77 @@ def evidence_rays(rec, stored, edge):
     return np.ascontiguousarray(O), np.ascontiguousarray(D), ranges, returned
 
 
+def count_queries(rec, stored, edge):
+    """The queries of a radius_count record {"seed", "n"}: the recipe of the replay's Device.queries - stored points
+    jittered by 0.01 edge, a tenth of them pushed out of the scene, and the BAD rows - drawn from stored_rows(), which
+    belongs to no build history, so that the model can count for the same queries."""
+    from tests.test_gpu_query import BAD as BAD_QUERIES
+
+    rng = np.random.default_rng([rec["seed"], 0x9E21])
+    n = rec["n"]
+    Q = stored[rng.integers(0, len(stored), n)] + rng.normal(0.0, 0.01 * edge, (n, 3))
+    Q[: n // 10] += rng.uniform(-3.0, 3.0, (n // 10, 3)) * edge
+    return np.concatenate([Q, BAD_QUERIES])
+
+
+def scan_of(rec, stored, edge):
+    """(scan, transform) of a point_registration_system / nearest_plane_registration_system record {"seed", "n",
+    "motion"}: n stored points (stored_rows()) with a jitter of 0.002 edge - the scan as given - and the record's
+    motion as the transform the call is made under."""
+    rng = np.random.default_rng([rec["seed"], 0x5CA4])
+    scan = stored[rng.integers(0, len(stored), rec["n"])] + rng.normal(0.0, 0.002 * edge, (rec["n"], 3))
+    return np.ascontiguousarray(scan), motion(rec["motion"])
+
+
+def sparse_keep_tiled(rows, tested, among, radius, min_neighbours):
+    """{pose: keep} of remove_sparse for the tested poses, by sparse_keep_np - evaluated tile by tile, because the
+    brute force over 45 000 x 45 000 pairs takes minutes.  rows: {pose: (m, 3)}; tested, among: pose numbers in slot
+    order.  The judged rows of a pose are grouped by a lattice of cells of w >= radius; a tile is judged by
+    sparse_keep_np against the counted rows inside the cell's box grown by radius (1 + 1e-6) on every side, which
+    holds every row that can count for it (d2 <= fl(r r) bounds every |dx| by r (1 + 2^-52)); the rows of the tile's
+    own pose in that box are passed as the pose's cloud, so that the rule's own identity test applies."""
+    from octreelib_amd.query import sparse_keep_np
+
+    r = float(radius)
+    out = {p: np.zeros(len(rows[p]), dtype=bool) for p in tested}
+    counted = [rows[q] for q in among if len(rows[q])]
+    if not counted:      # (nothing counts: no row has a neighbour)
+        return out
+    every = np.vstack(counted)
+    lo = every.min(axis=0)
+    w = max(r, float((every.max(axis=0) - lo).max()) / 5.0)
+    pad = r * (1.0 + 1e-6)
+    for p in tested:
+        X = rows[p]
+        if len(X) == 0:
+            continue
+        cell = np.floor((X - lo) / w).astype(np.int64)
+        uniq, inv = np.unique(cell, axis=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        for g, c in enumerate(uniq):
+            mine = np.nonzero(inv == g)[0]
+            a, b = lo + c * w - pad, lo + (c + 1) * w + pad
+            box = {q: np.nonzero(np.all((rows[q] >= a) & (rows[q] <= b), axis=1))[0] for q in among}
+            clouds = [(q, rows[q][box[q]]) for q in among]
+            if p in among:
+                assert np.all(np.isin(mine, box[p]))
+                keep = sparse_keep_np(clouds, [p], r, min_neighbours)[list(among).index(p)]
+                out[p][mine] = keep[np.searchsorted(box[p], mine)]
+            else:
+                out[p][mine] = sparse_keep_np(clouds, [(p, X[mine])], r, min_neighbours)[-1]
+    return out
+
+
+class _Leaf:
+    """A leaf as query.HostMap reads one."""
+
+    def __init__(self, corner, edge, rows):
+        self.corner_min, self.edge_length, self._rows = corner, edge, rows
+
+    def get_points(self):
+        return self._rows
+
+
 # ---- the model ---------------------------------------------------------------------------------------------------------
 class Model:
     """The oracle behind one container: OGrid / OManager / OTree, with the bookkeeping the library keeps on its own
@@ -321,6 +422,13 @@ class Model:
         self.returned = None
         self.n_applied = 0
         self.evidence = {}
+        # the fourth generation: the nodes the prunes collapsed since the model was last rebuilt, as (voxel key, corner
+        # bytes, edge) - the guard of _guard_collapsed; the evidence records a prune has carried over; what the coverage
+        # test tallies about the last operation (never compared with the library)
+        self.collapsed = set()
+        self.dropped = set()
+        self.carried = set()
+        self.facts = None
 
     @classmethod
     def replay(cls, container, log):
@@ -436,6 +544,8 @@ class Model:
     def apply(self, op):
         kind = op["op"]
         index, self.n_applied, self.returned = self.n_applied, self.n_applied + 1, None
+        self.facts = None
+        fresh = self.stats_fresh
         if kind == "transform_poses_refused":      # (raises DomainError in the library: nothing changes, nothing is invalidated)
             self._transform(op)
         elif kind == "remove_poses_refused":       # (KeyError, before anything changes)
@@ -448,16 +558,24 @@ class Model:
                              len(self.poses))
         elif kind in ALL_MUTATING:
             self.untouched = False
-            getattr(self, "_" + kind.split("_")[0])(op)
+            getattr(self, "_sparse" if kind == "remove_sparse" else "_" + kind.split("_")[0])(op)
             if not self.untouched:
                 self.pooled = False
                 self.pooled_key = None
             if kind not in ("subdivide_planar", "subdivide_planar_count"):
                 self.stats_fresh = False
+            if kind == "prune" and self.untouched:      # (the call ends before anything is written: the statistics stand)
+                self.stats_fresh = fresh
             if self.max_depth() >= 2:
                 self.flags["depth2"] = True
-        elif kind in ("leaf_planes", "point_to_plane", "plane_segments", "registration_system") \
-                or (kind == "raycast" and op["surface"] == "plane"):
+        elif kind == "radius_count":
+            self._radius(op)
+        elif kind == "point_registration_system":
+            self._register(op)
+        elif kind in ("leaf_planes", "point_to_plane", "plane_segments", "registration_system",
+                      "nearest_plane_registration_system") or (kind == "raycast" and op["surface"] == "plane"):
+            if kind == "nearest_plane_registration_system":
+                self._register(op)
             self.pooled = True      # (each of them makes the pooled table of its selection when the device's is not that)
             self.pooled_key = None if op.get("poses") is None else tuple(sorted(op["poses"]))
 
@@ -474,6 +592,11 @@ class Model:
         self._set_orig(p, np.arange(len(pts), dtype=np.int64))
         self.n_inserted[p] = len(pts)
         self._distinct([p])
+        self._guard_collapsed()
+        if self.dropped:      # (a voxel a prune dropped is created anew: an unsplit root at the end of the creation order)
+            hit = [k for k in self.o.pose_voxels[p] if k in self.dropped]
+            self.facts = {"recreated": len(hit)}
+            self.dropped -= set(hit)
         if late >= 100:
             self.flags["late100"] = True
 
@@ -498,6 +621,7 @@ class Model:
         tree.orig = np.concatenate([tree.orig, self.n_inserted[p] + np.arange(len(pts), dtype=np.int64)])
         self.n_inserted[p] += len(pts)
         self._distinct([p])
+        self._guard_collapsed()
         if late >= 100:
             self.flags["late100"] = True
 
@@ -632,6 +756,8 @@ class Model:
             fresh._set_orig(p, orig)
             fresh._distinct([p])
         self.o = fresh.o
+        self.collapsed = set()      # (a fresh map: no node of it was ever collapsed)
+        self.dropped = set()
         self.stats, self.stats_fresh = "none", False
 
     # -- the third generation ---------------------------------------------------------------------------------------------
@@ -668,7 +794,8 @@ class Model:
         assert not self.displaced and (op["poses"] is None or self.kind != "octree")
         if op.get("evidence_from") is not None:
             keys, through, hits = self.evidence[op["evidence_from"]]
-            if keys != self.scheme_leaves()[0]:
+            # (evidence a prune has carried over needs RayEvidence.remapped: the record says so with "remapped")
+            if keys != self.scheme_leaves()[0] or (op["evidence_from"] in self.carried and not op.get("remapped")):
                 raise Rejected("the node table has changed since the evidence was taken")
         else:
             keys, through, hits = self._evidence(op)
@@ -720,6 +847,171 @@ class Model:
             del self.n_inserted[p]
         if sum(self.counters(p)[1] for p in self.poses) < before:
             self.flags["emptied"] = True
+
+    # -- the fourth generation -------------------------------------------------------------------------------------------
+    def clouds(self, poses):
+        """[(pose, rows)] of the given poses (None: all) in slot order, the rows in the pose's own leaf order."""
+        return [(p, self.pose_rows(p)) for p in self.poses if poses is None or p in poses]
+
+    def host_map(self):
+        """query.HostMap over the model's own leaves (empty ones included): the host definitions of the map queries."""
+        from octreelib_amd.query import HostMap
+
+        leaves = {p: [_Leaf(c, e, r) for c, e, r in self.leaf_rows(p, non_empty=False)] for p in self.poses}
+        edge = float(self.c["edge"])
+        if self.kind == "grid":
+            keys = sorted(k for k, mg in self.o.managers.items() if mg.octrees)
+            return HostMap(0, edge, [(np.array(k, dtype=np.float64), edge) for k in keys], leaves)
+        return HostMap(1, edge, [(np.array(self.c["corner"], dtype=np.float64), edge)], leaves)
+
+    def _radius(self, op):
+        """radius_count: the count does not depend on any order, so the model counts over its own rows."""
+        from octreelib_amd.query import radius_count_np
+
+        e = float(cloud_edge(self.c))
+        cnt = radius_count_np(count_queries(op, self.stored(), e), self.clouds(op["poses"]), op["radius"] * e,
+                              max_count=op["max_count"])
+        self.returned = cnt
+        self.facts = {"saturated": 0 if op["max_count"] is None else int((cnt == op["max_count"]).sum())}
+
+    def _register(self, op):
+        """The two nearest-point registration systems: the counts are exact on both sides (the correspondences are
+        those of nearest_np, bit for bit; a plane is accepted by its point count and, with max_variance, by an
+        eigenvalue that the two sides round differently - so n_used of the plane form is booked only without it)."""
+        from octreelib_amd.query import nearest_np
+        from octreelib_amd.registration import transform_np
+
+        e = float(cloud_edge(self.c))
+        scan, T = scan_of(op, self.stored(), e)
+        r = op["max_distance"] * e
+        if op["op"] == "point_registration_system":
+            p = transform_np(T, scan)
+            nb = nearest_np(p, self.clouds(op["poses"]), 1, max_distance=r)
+            used = int((nb.count.reshape(-1) > 0).sum())
+            self.returned = (used, int(np.all(np.isfinite(p), axis=1).sum()))
+            self.facts = {"n": len(scan), "n_used": used}
+            return
+        s = self.host_map().nearest_plane_registration_system(
+            scan, T, max_distance=r, pose_numbers=op["poses"], min_points=op["min_points"],
+            max_variance=op["max_variance"], huber_delta=op["huber_delta"], origin=op["origin"], per_point=True)
+        self.returned = (int(s.n_located), int(s.n_used) if op["max_variance"] is None else None)
+        self.facts = {"n": len(scan), "n_used": int(s.n_used), "no_plane": int(((s.node >= 0) & (s.row < 0)).sum())}
+
+    def _sparse(self, op):
+        """remove_sparse: sparse_keep_np over the model's rows, applied as one oracle apply_mask per tested pose in the
+        pose's own row order; the scheme stays.  The library compacts whatever the decisions are (radius.hip:
+        octl_forest_remove_sparse goes through mask_apply as carve does): the pooled table is invalid afterwards
+        whether rows left or not."""
+        assert not self.displaced
+        tested = [p for p in self.poses if op["poses"] is None or p in op["poses"]]
+        among = [p for p in self.poses if op["among"] is None or p in op["among"]]
+        keep = sparse_keep_tiled({p: self.pose_rows(p) for p in self.poses}, tested, among, op["radius"],
+                                 op["min_neighbours"])
+        before = sum(self.counters(p)[1] for p in self.poses)
+        removed = 0
+        for p in tested:
+            removed += int((~keep[p]).sum())
+            if self.kind == "grid":
+                self.o.apply_mask(p, keep[p])
+            else:
+                self.trees_of(p)[0].apply_mask(keep[p])
+        self.returned = removed
+        self.facts = {"removed": removed}
+        if sum(self.counters(p)[1] for p in self.poses) < before:
+            self.flags["emptied"] = True
+
+    def _groups(self):
+        """(voxel key, [scheme tree, pose trees ...]) of every top-level cube; an octree is its own scheme.  The trees
+        of one cube have the same shape (subdivide_as), so their nodes are walked side by side."""
+        if self.kind == "octree":
+            return [(None, [self.o])]
+        if self.kind == "manager":
+            return [(None, [self.o.scheme] + list(self.o.octrees.values()))]
+        return [(k, [m.scheme] + list(m.octrees.values())) for k, m in self.o.managers.items()]
+
+    @staticmethod
+    def _below(nodes):
+        """The points of every pose below the node the trees of one cube share."""
+        if nodes[0].children is None:
+            return sum(len(n.idx) for n in nodes)
+        return sum(Model._below([n.children[i] for n in nodes]) for i in range(8))
+
+    def _prune(self, op, dry=False):
+        """prune() by the definition of DESIGN 4.18 on the oracle trees: a grid's voxel in which no pose has a point
+        leaves the map (managers, every pose's voxel list) and the order of the rest is kept; in the cubes that stay
+        the topmost internal nodes without a point below become leaves in the scheme tree and in every pose tree
+        (what lay below them goes; a kept internal node keeps its eight children).  dry: nothing changes, the
+        outcome is returned - {"voxels", "collapsed", "outer", "bare"}."""
+        groups = self._groups()
+        nodes_before = sum(trees[0].root.n_nodes() for _, trees in groups)
+        gone = [k for k, trees in groups if self.kind == "grid" and self._below([t.root for t in trees]) == 0]
+        tops = []
+
+        def walk(vox, nodes):
+            if nodes[0].children is None:
+                return
+            if self._below(nodes) == 0:
+                tops.append((vox, nodes))
+                return
+            for i in range(8):
+                walk(vox, [n.children[i] for n in nodes])
+
+        for k, trees in groups:
+            if k is None or k not in gone:
+                walk(k, [t.root for t in trees])
+        dropped = sum(trees[0].root.n_nodes() for k, trees in groups if k is not None and k in gone) \
+            + sum(nodes[0].n_nodes() - 1 for _, nodes in tops)
+        outer = False
+        if gone:
+            every, left = np.array([k for k, _ in groups]), np.array([k for k, _ in groups if k not in gone])
+            outer = len(left) == 0 or not (np.array_equal(every.min(axis=0), left.min(axis=0))
+                                           and np.array_equal(every.max(axis=0), left.max(axis=0)))
+        facts = {"voxels": len(gone), "collapsed": len(tops), "outer": bool(outer),
+                 "bare": self.kind != "grid" and any(nodes[0] is groups[0][1][0].root for _, nodes in tops)}
+        if dry:
+            return facts
+        key = lambda v: ((np.asarray(v.corner, dtype=np.float64) + 0.0).tobytes(), float(v.edge))
+        for k in gone:
+            for p in self.o.managers[k].octrees:
+                self.o.pose_voxels[p].remove(k)
+                del self.o.local_to_pose[(k, p)]
+            del self.o.managers[k]
+        self.collapsed = {c for c in self.collapsed if c[0] not in gone}
+        self.dropped |= set(gone)
+        for vox, nodes in tops:
+            for x in nodes:
+                for ch in x.children:
+                    ch._remove_from_cache()
+                x.children, x.idx = None, np.empty(0, dtype=np.int64)
+                x.tree.cached[id(x)] = x
+            self.collapsed.add((vox,) + key(nodes[0]))
+        self.returned = (nodes_before - dropped, len(groups) - len(gone), dropped, len(gone), len(tops))
+        self.facts = facts
+        if not dropped:      # (the library ends the call before it writes a table: content_stamp stands)
+            self.untouched = True
+            return
+        self.stats = "nan"      # (split_stats_valid = false: zeros and NaN, as after a count-driven build)
+        # stored evidence, by the rule of RayEvidence.remapped: a leaf that is still there keeps its counters, a
+        # collapsed node - it was internal - starts at zero, what was dropped goes
+        now = self.scheme_leaves()[0]
+        for i, (keys, through, hits) in self.evidence.items():
+            old = {k: (t, h) for k, t, h in zip(keys, through.tolist(), hits.tolist())}
+            self.evidence[i] = (now, np.array([old.get(k, (0, 0))[0] for k in now], dtype=through.dtype),
+                                np.array([old.get(k, (0, 0))[1] for k in now], dtype=hits.dtype))
+            self.carried.add(i)
+
+    def _guard_collapsed(self):
+        """After an insert or an extend: Rejected when a row went into a node a prune has collapsed.  Neither the
+        reference nor DESIGN says where in a pose's leaf list a collapsed node stands once it is filled again (it is
+        empty, so until then no listing shows it); transform_poses rebuilds the map and lifts the guard."""
+        if not self.collapsed:
+            return
+        for vox, trees in self._groups():
+            for t in trees[0 if self.kind == "octree" else 1:]:
+                for v in t.cached.values():
+                    if len(v.idx) and (vox, (np.asarray(v.corner, dtype=np.float64) + 0.0).tobytes(), float(v.edge)) \
+                            in self.collapsed:
+                        raise Rejected("a row falls into a node the last prune collapsed")
 
     def _apply(self, op):
         p = op["pose"]
@@ -948,6 +1240,8 @@ class _Generator:
                               "stats": st if isinstance(st, str) or self.model.stats_fresh else "stale"})
             if self.model.returned is not None:      # (the third generation: what the library's call must return)
                 self.meta[-1]["returns"] = self.model.returned
+            if self.model.facts is not None:         # (the fourth generation: what the coverage test tallies)
+                self.meta[-1]["facts"] = self.model.facts
             return True
         return False
 
@@ -1268,10 +1562,10 @@ class _Generator3(_Generator2):
     inside (1.2 s + 0.12 * 1.2 sqrt(3) s + 0.35 s < 2 s).  On a grid it is drawn that small where the motif needs the
     insert to create no voxel (evidence taken before it must still fit the node table)."""
 
-    read_kinds = ALL_READ_ONLY
+    read_kinds = GEN3_ALL_READ_ONLY
 
-    def __init__(self, seed):
-        super().__init__(seed, SEEDS3[0])
+    def __init__(self, seed, first=SEEDS3[0]):
+        super().__init__(seed, first)
         self.inside = False          # moved clouds stay inside the voxels that exist
         self.piecewise = None        # None: drawn
         self.n_moved = self.n_piecewise = 0
@@ -1459,11 +1753,289 @@ class _Generator3(_Generator2):
         self.in_motif = False
 
 
+# the motifs of the fourth generation by seed - 300: the letters are the entries of TRANSITIONS4 in order
+_MOTIF4 = {0: "al", 1: "bm", 2: "ek", 3: "cn", 4: "go", 5: "ds", 6: "h", 7: "jp", 8: "iq", 9: "rt", 10: "fh", 11: "eo",
+           12: "as", 13: "gk", 14: "il", 15: "bm", 16: "ct", 17: "jq", 18: "rd", 19: "fn", 20: "gp", 21: "fk", 22: "h",
+           23: "pd"}
+
+
+class _Generator4(_Generator3):
+    """The fourth generation: remove_sparse and prune among the mutating kinds, radius_count and the two nearest-point
+    registration systems among the read-only ones.  Once a prune has collapsed a node, no insert or extend is drawn
+    (Model._guard_collapsed would reject nearly every cloud: they fill the scene) until a transform_poses has rebuilt
+    the map; the motifs that insert after a prune make holes that collapse nothing - a pose stored one and a half
+    voxels out of the scene, alone in the voxels it adds, and removed again."""
+
+    read_kinds = ALL_READ_ONLY
+
+    def __init__(self, seed):
+        super().__init__(seed, SEEDS4[0])
+        self.n_counts = 0
+
+    def params(self, kind):
+        m, rng = self.model, self.rng
+        e = float(self.cloud_edge)
+        if kind not in GEN4_MUTATING + GEN4_READ_ONLY:
+            if m.collapsed and kind in ("insert", "extend") + MOVED:
+                return None
+            return super().params(kind)
+        if not m.poses or m.displaced:
+            return None
+        has_points = any(m.counters(p)[2] > 0 for p in m.poses)
+        if kind == "prune":
+            return {"op": kind}
+        if not has_points:
+            return None
+        if kind == "radius_count":      # (on a grid the radius is at most twice the voxel edge, which is the cloud edge)
+            self.n_counts += 1      # (the caps in turn, so that the seed set has each of them whatever else is drawn)
+            return {"op": kind, "seed": int(rng.integers(1 << 30)), "n": 300, "radius": float(rng.choice([0.05, 0.2, 0.5])),
+                    "max_count": [None, 1, 3, 7][(self.index // 3 + self.n_counts) % 4], "poses": self._subset()}
+        if kind == "remove_sparse":
+            return {"op": kind, "radius": float(rng.choice([0.05, 0.1, 0.2])) * e,
+                    "min_neighbours": int(rng.choice([1, 2, 4])), "poses": self._subset(), "among": self._subset()}
+        # the two registration systems: from the identity up to a shift of a few leaf edges, or right out of the scene
+        how = str(rng.choice(["identity", "small", "leaves", "far"], p=[0.2, 0.3, 0.35, 0.15]))
+        mo = {"identity": {"xi": [0.0] * 6, "origin": self._centre()}, "small": self._motion(0.02, 0.02 * e),
+              "leaves": self._motion(0.05, 0.5 * e), "far": {"xi": [0.0, 0.0, 0.0, 6.0 * e, 0.0, 0.0], "origin": self._centre()}}[how]
+        op = {"op": kind, "seed": int(rng.integers(1 << 30)), "n": int(rng.integers(300, 1001)), "motion": mo,
+              "max_distance": float(rng.choice([0.05, 0.3, 1.0])), "huber_delta": [None, 0.02 * e][int(rng.integers(0, 2))],
+              "origin": [None, [float(x) for x in np.array(self._centre()) + rng.uniform(-1.0, 1.0, 3) * e]][int(rng.integers(0, 2))],
+              "poses": self._subset()}
+        if kind == "nearest_plane_registration_system":
+            op.update({"min_points": int(rng.choice([1, 8, 16])), "max_variance": [None, 1e-3 * e ** 2][int(rng.integers(0, 2))]})
+        return op
+
+    def holes(self, want="change"):
+        """Mutating operations until a prune would find something to do (want "change"), or a voxel to drop ("voxels"):
+        a remove_sparse that takes the uniform background away - the use the library's docstring names - then count
+        filters of rising strictness."""
+        e = float(self.cloud_edge)
+        ok = lambda f: f["voxels"] + f["collapsed"] > 0 if want == "change" else f[want] > 0
+        if ok(self.model._prune(None, dry=True)):
+            return
+        few = sum(self.model.counters(p)[2] > 0 for p in self.model.poses) < 2
+        steps = [("remove_sparse", {"radius": 0.15 * e, "min_neighbours": 2 if few else 4, "poses": None, "among": None})] \
+            + [("filter_count", {"crit": ["ge", c]}) for c in (8, 20, 50)]
+        for kind, fix in steps[: 1 if self.shallow else None]:
+            if self.step(kind, fix) and ok(self.model._prune(None, dry=True)):
+                return
+        if self.shallow:      # (few, dense internal nodes: none of them can be emptied - the prune finds nothing)
+            return
+        raise AssertionError(f"seed {self.seed}: no holes for a prune\n{Sequence.printed(self)}")
+
+    def tie(self):
+        """{"radius", "min_neighbours", ...} of a remove_sparse over every pose that the INCLUSIVE comparison decides: a
+        stored row x with exactly min_neighbours other rows within the radius, the farthest of them at
+        d2 == fl(radius radius) bit for bit (d2 by the formula of radius_count_np).  x stays; under d2 < r2 it would
+        go.  The radius is kept between 0.05 and 0.25 cloud edges, as the drawn ones are."""
+        e = float(self.cloud_edge)
+        rows = np.vstack([self.model.pose_rows(p) for p in self.model.poses])
+        for _ in range(256):
+            d = rows[int(self.rng.integers(0, len(rows)))] - rows
+            d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+            t = np.partition(d2, 4)[int(self.rng.integers(1, 5))]      # (d2 = 0 is the row itself)
+            if not (0.05 * e) ** 2 <= t <= (0.25 * e) ** 2:
+                continue
+            for r in (np.sqrt(t), np.nextafter(np.sqrt(t), 0.0), np.nextafter(np.sqrt(t), np.inf)):
+                if r * r == t:
+                    return {"radius": float(r), "min_neighbours": int((d2 <= t).sum()) - 1, "poses": None, "among": None}
+        raise AssertionError(f"seed {self.seed}: no radius with an exact tie\n{Sequence.printed(self)}")
+
+    def gentle(self, first):
+        """{"radius", "min_neighbours", ...} of a remove_sparse that takes rows out of leaves of the
+        segments of `first` (a plane_segments record over every pose) and empties no leaf: the pooled plane table keeps
+        its rows, so a segment table kept across the call would still fit it - and would be wrong.  Found by trying
+        the rule on the model's rows."""
+        m, e = self.model, float(self.cloud_edge)
+        hm = m.host_map()
+        seg = hm.plane_segments(None, first["min_points"], first["max_variance"], first["max_angle"], first["max_offset"])
+        key = lambda c, w: ((np.asarray(c, dtype=np.float64) + 0.0).tobytes(), float(w))
+        nd = hm.nodes
+        labelled = {key(nd["corner"][n], nd["edge"][n]) for n, lab in zip(seg.planes.node.tolist(), seg.label.tolist()) if lab >= 0}
+        leaves = {p: [(key(c, w), len(r)) for c, w, r in m.leaf_rows(p)] for p in m.poses}
+        rows = {p: m.pose_rows(p) for p in m.poses}
+        # (one pose alone first: where its row is the last of its own in a leaf, another pose may still hold one there)
+        for r, k in ((0.25, 1), (0.2, 1), (0.15, 1), (0.25, 2), (0.1, 1), (0.2, 2)):
+            for tested in ([[p] for p in m.poses] if len(m.poses) > 1 else []) + [None]:
+                keep = sparse_keep_tiled(rows, m.poses if tested is None else tested, m.poses, r * e, k)
+                left, gone = collections.Counter(), collections.Counter()
+                for p in m.poses:
+                    at = 0
+                    for leaf, n in leaves[p]:
+                        stay = int(keep[p][at: at + n].sum()) if p in keep else n
+                        left[leaf], gone[leaf], at = left[leaf] + stay, gone[leaf] + n - stay, at + n
+                if all(left.values()) and any(gone[leaf] for leaf in labelled):
+                    return {"radius": r * e, "min_neighbours": k, "poses": tested, "among": None}
+        raise AssertionError(f"seed {self.seed}: no remove_sparse that thins a segment and empties no leaf\n{Sequence.printed(self)}")
+
+    def outward(self):
+        """The motion that stores a cloud one and a half voxels out of the scene along an axis the seed fixes."""
+        xi = [0.0] * 6
+        xi[3 + self.index % 3] = (-1.5 if self.index % 2 else 1.5) * float(self.cloud_edge)
+        return {"xi": xi, "origin": self._centre()}
+
+    def lonely_pose(self):
+        """A late pose alone in the voxels it adds, inserted and removed again: holes that collapse no node."""
+        self.piecewise = False
+        self.must("insert_moved", {"motion": self.outward()})
+        self.piecewise = None
+        pose = self.log[-1]["pose"]
+        self.must("remove_poses", {"poses": [pose]})
+        return pose
+
+    def pruned(self, **facts):
+        """A prune whose outcome the motif needs."""
+        self.must("prune")
+        got = self.meta[-1]["facts"]
+        for k, want in facts.items():
+            assert (got[k] > 0) == want, f"seed {self.seed}: prune {got}, wanted {facts}\n{Sequence.printed(self)}"
+
+    def again(self, first):
+        self.must(first["op"], dict(first))
+
+    def run(self):
+        rng, idx = self.rng, self.index
+        names = _MOTIF4[idx]
+        tree = self.kind == "octree"
+        for i in range(1 if tree else 3 if set(names) & set("enpqr") else int(rng.integers(2, 4))):
+            self.must("insert_moved" if i == 0 and idx % 4 == 0 else "insert")
+        self.reads(0, 1)
+        kind, self.first_subdivide = self.first_subdivide, None
+        self.must(kind)
+        if tree and "f" in names:      # (an octree subdivides once: the motif is here)
+            assert kind == "subdivide_planar_count"
+            self.must("prune")
+            self.must("split_stats")
+        self.reads(1, 2)
+        late = ("extend_moved" if idx % 2 else "extend") if tree else ("insert_moved" if idx % 2 else "insert")
+        self.must(late)      # a late pose into the scheme
+        self.reads(1, 1)
+        if idx % 3 != 1 and not set(names) & set("hi"):      # rows leave before the motif: a mask, a filter, a carve or the sparse rows
+            for kind in ("apply_mask", "ransac", "remove_sparse", "carve", "filter_count")[idx % 3:]:
+                if kind != "ransac" or "h" not in names:      # (the motif's own RANSAC: at most two per sequence)
+                    if self.step(kind):
+                        break
+            self.reads(1, 1)
+        for name in names:
+            if not (tree and name == "f"):
+                self._motif4(name)
+                self.reads(1, 1)
+        weights = {"insert": 1, "insert_moved": 2, "extend": 1, "extend_moved": 2, "subdivide_count": 2,
+                   "subdivide_planar_count": 1, "filter_count": 2, "filter_subset": 1, "map_select": 1, "apply_mask": 2,
+                   "ransac": 1, "transform_poses": 2, "carve": 3, "remove_poses": 2, "remove_poses_refused": 1,
+                   "remove_sparse": 6, "prune": 6}
+        for _ in range(int(rng.integers(1, 3))):
+            if len(self.log) >= 23:
+                break
+            self.mutate(weights)
+            self.reads(1, 2)
+        if not self.model.flags["emptied"]:
+            self.step("filter_count", {"crit": ["ge", 6]})
+            self.reads(1, 1)
+        if idx == 20:      # a manager emptied to its bare root: every row is sparse when a million neighbours are asked for
+            self.must("remove_sparse", {"radius": 0.1 * float(self.cloud_edge), "min_neighbours": 10 ** 6, "poses": None,
+                                        "among": None})
+            self.pruned(bare=True)
+            self.reads(1, 2)
+        return Sequence(self.seed, self.container, self.log, self.obs, self.meta, self.draws, self.rejected,
+                        self.model.flags, self.model.closest, self.ident)
+
+    def _motif4(self, name):
+        """The transition of TRANSITIONS4 the letter names, with nothing mutating in between but what it lists."""
+        rng = self.rng
+        poses = lambda: list(self.model.poses)
+        part = lambda: self._subset(always=True) or poses()[:1]      # (a proper subset S where there are two poses)
+        self.in_motif = True
+        if name in ("a", "b"):
+            S_ = part()
+            if name == "a":
+                self.holes()
+            else:
+                self.must("prune")      # (whatever it finds: the next one finds nothing)
+            self.must("leaf_planes", {"poses": S_})
+            self.pruned(voxels=False, collapsed=False) if name == "b" else self.must("prune")
+            self.must("point_to_plane", {"poses": S_})
+        elif name in ("c", "d", "t"):
+            self.holes()
+            self.must({"c": "plane_segments", "d": "nearest", "t": "point_registration_system"}[name])
+            first = self.log[-1]
+            self.must("prune")
+            self.again(first)
+        elif name == "e":
+            self.lonely_pose()
+            self.must("adjustment_system")
+            self.pruned(voxels=True, outer=True)
+            self.must("adjustment_system")
+        elif name == "f":
+            self.must("subdivide_planar_count")
+            self.must("prune")
+            self.must("split_stats")
+        elif name == "g":
+            self.holes()
+            self.must("ray_evidence")
+            k = len(self.log) - 1
+            self.must("prune")
+            self.must("carve", {"evidence_from": k, "fused": False, "remapped": True})
+        elif name == "h":
+            self.lonely_pose()
+            self.pruned(voxels=True, collapsed=False)
+            self.piecewise = False
+            self.must("insert_moved", {"motion": self.outward()})      # (the same number, into the voxels that went)
+            self.piecewise = None
+            assert self.meta[-1]["facts"]["recreated"] > 0
+            self.subdivide_again()
+            self.must("ransac")
+        elif name == "i":
+            pose = self.lonely_pose()
+            self.pruned(collapsed=False)
+            self.must("insert")
+            assert self.log[-1]["pose"] == pose
+        elif name == "j":
+            self.must("carve")
+            self.must("prune")
+            self._fixed_transform({"poses": None if self.index < 12 else self._subset(always=True)})
+            self.subdivide_again()
+        elif name == "k":
+            self.holes()
+            self.must("prune")
+            self.pruned(voxels=False, collapsed=False)
+        elif name == "l":
+            self.must("radius_count", {"poses": None if self.index < 12 else part(), "max_count": None})
+            first = self.log[-1]
+            self.must("remove_sparse")
+            self.again(first)
+        elif name == "m":
+            self.must("remove_sparse", self.tie())      # (decided by d2 == r2: the inclusive comparison)
+            self.must("nearest")
+        elif name == "n":
+            self.must("remove_sparse", {"poses": part(), "among": part()})
+            self.must("prune")
+        elif name in ("o", "p", "s"):
+            self.must({"o": "plane_segments", "p": "adjustment_system", "s": "nearest_plane_registration_system"}[name],
+                      {"poses": None} if name == "o" else
+                      # (the second of the two seeds: right out of the scene, so that no point is used)
+                      {"motion": {"xi": [0.0, 0.0, 0.0, 6.0 * float(self.cloud_edge), 0.0, 0.0], "origin": self._centre()},
+                       "max_distance": 0.3} if name == "s" and self.index >= 12 else None)
+            first = self.log[-1]
+            # (o: the plane table keeps its rows, a stale segment table would still fit; p: decided by d2 == r2)
+            self.must("remove_sparse", self.gentle(first) if name == "o" else self.tie() if name == "p" else None)
+            self.again(first)
+        elif name in ("q", "r"):
+            S_ = part()
+            self.must("nearest" if name == "q" else "leaf_planes", {"poses": S_})
+            first = self.log[-1]
+            self.must("point_registration_system" if name == "q" else "nearest_plane_registration_system", {"poses": None})
+            self.again(first) if name == "q" else self.must("point_to_plane", {"poses": S_})
+        self.in_motif = False
+
+
 @functools.lru_cache(maxsize=None)
 def generate(seed):
     if seed < SEEDS2[0]:
         return _Generator(seed).run()
-    return _Generator2(seed).run() if seed < SEEDS3[0] else _Generator3(seed).run()
+    if seed < SEEDS3[0]:
+        return _Generator2(seed).run()
+    return _Generator3(seed).run() if seed < SEEDS4[0] else _Generator4(seed).run()
 
 
 # ---- what the logs must cover ------------------------------------------------------------------------------------------
@@ -1622,4 +2194,87 @@ def transitions3(log):
                 found.add("insert_moved(late, piecewise)>nearest")
         if k == "extend_moved" and "leaf_statistics" in names:
             found.add("extend_moved>leaf_statistics")
+    return found
+
+
+def transitions4(log, meta):
+    """The names of TRANSITIONS4 that occur in a log of the fourth generation, with nothing mutating in between but
+    what the name itself lists (a refused call counts as mutating here, as in transitions3).  What a prune found and
+    whether an insert re-created a dropped voxel is read from the bookkeeping (meta[i]["facts"])."""
+    found = set()
+    T = TRANSITIONS4
+    fam = lambda k: "subdivide" if k in SUBDIVIDES else "insert" if k in ("insert", "insert_moved") else k
+    mut = [i for i, op in enumerate(log) if op["op"] in ALL_MUTATING]
+    sel = lambda op: None if op.get("poses") is None else tuple(sorted(op["poses"]))
+    pooling = lambda o: o["op"] in ("leaf_planes", "point_to_plane", "plane_segments", "registration_system",
+                                    "nearest_plane_registration_system") or (o["op"] == "raycast" and o["surface"] == "plane")
+
+    def reads_between(a):
+        """The read-only operations after the a-th mutating one (-1: from the start), up to the next."""
+        start = mut[a] + 1 if a >= 0 else 0
+        return log[start: mut[a + 1] if a + 1 < len(mut) else len(log)]
+
+    for a, i in enumerate(mut):
+        op, k = log[i], log[i]["op"]
+        before, after = reads_between(a - 1), reads_between(a)
+        names = [o["op"] for o in after]
+        chain = [fam(log[j]["op"]) for j in mut[a: a + 4]]
+        prev = log[mut[a - 1]] if a else None
+        nxt = log[mut[a + 1]] if a + 1 < len(mut) else None
+
+        def around(name, same=True):
+            """The last `name` before and the first one after - the same record, where that is asked for."""
+            b, c = [o for o in before if o["op"] == name], [o for o in after if o["op"] == name]
+            return bool(b and c and (not same or b[-1] == c[0]))
+
+        if k == "prune":
+            facts = meta[i]["facts"]
+            pb, pa = [o for o in before if pooling(o)], [o for o in after if pooling(o)]
+            if pb and pa and pb[-1]["op"] == "leaf_planes" and pa[0]["op"] == "point_to_plane" \
+                    and sel(pb[-1]) is not None and sel(pb[-1]) == sel(pa[0]):
+                found.add(T[0] if facts["voxels"] + facts["collapsed"] else T[1])
+            if around("plane_segments"):
+                found.add(T[2])
+            if around("nearest"):
+                found.add(T[3])
+            if facts["outer"] and around("adjustment_system", same=False):
+                found.add(T[4])
+            if prev is not None and prev["op"] in ("subdivide_planar", "subdivide_planar_count") and "split_stats" in names:
+                found.add(T[5])
+            if nxt is not None and nxt["op"] == "carve" and nxt.get("remapped") and nxt.get("evidence_from") is not None \
+                    and (mut[a - 1] if a else -1) < nxt["evidence_from"] < i:
+                assert log[nxt["evidence_from"]]["op"] == "ray_evidence"
+                found.add(T[6])
+            if facts["voxels"] and chain[1:] == ["insert", "subdivide", "ransac"] \
+                    and meta[mut[a + 1]].get("facts", {}).get("recreated"):
+                found.add(T[7])
+            if prev is not None and prev["op"] == "remove_poses" and nxt is not None and fam(nxt["op"]) == "insert" \
+                    and nxt["pose"] in prev["poses"]:
+                found.add(T[8])
+            if prev is not None and prev["op"] == "carve" and chain[1:3] == ["transform_poses", "subdivide"]:
+                found.add(T[9])
+            if nxt is not None and nxt["op"] == "prune":
+                found.add(T[10])
+            if prev is not None and prev["op"] == "remove_sparse" and prev["poses"] is not None and prev["among"] is not None:
+                found.add(T[13])
+            if around("point_registration_system"):
+                found.add(T[19])
+        if k == "remove_sparse":
+            if around("radius_count"):
+                found.add(T[11])
+            if "nearest" in names:
+                found.add(T[12])
+            if around("plane_segments"):
+                found.add(T[14])
+            if around("adjustment_system", same=False):
+                found.add(T[15])
+            if around("nearest_plane_registration_system"):
+                found.add(T[18])
+    for i in range(len(log) - 2):
+        x, y, z = log[i: i + 3]
+        if sel(x) is not None and sel(x) == sel(z) and sel(y) != sel(x):
+            if x["op"] == "nearest" and y["op"] == "point_registration_system" and z["op"] == "nearest":
+                found.add(T[16])
+            if x["op"] == "leaf_planes" and y["op"] == "nearest_plane_registration_system" and z["op"] == "point_to_plane":
+                found.add(T[17])
     return found

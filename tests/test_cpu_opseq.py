@@ -289,21 +289,203 @@ def test_third_generation_covers_kinds_containers_and_transitions():
         assert c[k] >= 2, (k, c)
 
 
-class _Leaf:
-    def __init__(self, corner, edge, rows):
-        self.corner_min, self.edge_length, self._rows = corner, edge, rows
+# the same digests for the third generation, computed in a worktree of the commit before the fourth generation was added
+SEED3_DIGESTS = {
+    200: "26b052883fef3114", 201: "dab8d33b4ba1f1b2", 202: "08d7aa7cffd10a8d", 203: "d19ac878e207a6a7",
+    204: "820be7f91144571b", 205: "53463f2498a0eaa9", 206: "f5c16ace3357ed44", 207: "07624a56439b2873",
+    208: "a934d4c87710d077", 209: "edebd86e56ad4c7b", 210: "25179ca4dcc2ea33", 211: "657cd45c17dfbe62",
+    212: "d6823cbf68bf40a3", 213: "16c38240a762b22b", 214: "c9d777fef1dc1cae", 215: "112a4be5c83ae916",
+    216: "87b6b9052019ff58", 217: "b7aee4c3226a5b1a", 218: "12e79ad4736192cd", 219: "3c76649e443f915b",
+    220: "6555fdfb9ec8a5b6", 221: "cd27386ab5d4c21e", 222: "7e645563a83595b9", 223: "518a5446f3e06d98"}
 
-    def get_points(self):
-        return self._rows
+
+@pytest.mark.parametrize("seed", S.SEEDS3)
+def test_third_generation_seeds_are_what_they_were(seed):
+    q = S.generate(seed)
+    assert hashlib.sha256(repr((repr(q.log), q.obs, q.meta)).encode()).hexdigest()[:16] == SEED3_DIGESTS[seed]
+    assert not any(op["op"] in S.GEN4_MUTATING + S.GEN4_READ_ONLY for op in q.log)
 
 
-@pytest.mark.parametrize("seed", [0, 7, 106, 115, 203, 214])
+# ---- the fourth generation: prune, remove_sparse, radius_count, the nearest-point registrations --------------------------
+def _same(a, b):
+    """Equality of two booked return values (a radius_count books an array)."""
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return a is not None and b is not None and np.array_equal(a, b)
+    return a == b
+
+
+@pytest.mark.parametrize("seed", S.SEEDS4)
+def test_fourth_generation_caps_replay_and_scene(seed):
+    q = S.generate(seed)
+    assert 8 <= len(q.log) <= 28, q.printed()
+    assert len(q.log) == len(q.obs) == len(q.meta) == len(q.ident)
+    assert q.rejected <= 0.25 * q.draws, (q.rejected, q.draws)
+    m = S.Model(q.container)
+    for i, op in enumerate(q.log):
+        k = op["op"]
+        before = (m.observe(), m.pooled, list(m.poses)) if k in S.REFUSED + S.GEN4_READ_ONLY else None
+        held = {p: m.counters(p) for p in m.poses}
+        rows = {p: sorted(map(bytes, m.pose_rows(p))) for p in m.poses} if k in ("prune", "remove_sparse") else None
+        m.apply(op)
+        assert m.observe() == q.obs[i], f"step {i}\n{q.printed(i)}"
+        assert m.pooled == q.meta[i]["pooled"] and _same(m.returned, q.meta[i].get("returns"))
+        assert list(q.obs[i]) == m.poses
+        if before is not None and k in S.REFUSED:      # a refused call changes nothing and invalidates nothing
+            assert (q.obs[i], q.meta[i]["pooled"], m.poses) == before and q.meta[i]["pooled"] == q.meta[i - 1]["pooled"]
+        if before is not None and k in S.GEN4_READ_ONLY:      # the new reads change nothing; only the plane form makes a table
+            assert (q.obs[i], m.poses) == (before[0], before[2])
+            assert q.meta[i]["pooled"] == (before[1] or k == "nearest_plane_registration_system")
+        ident = m.identity()
+        assert (ident is None) == (q.ident[i] is None)
+        for p in ident or ():
+            assert np.array_equal(ident[p][0], q.ident[i][p][0]) and np.array_equal(ident[p][1], q.ident[i][p][1])
+            assert len(ident[p][0]) == q.obs[i][p][1][2] and np.all(np.diff(ident[p][0]) > 0)
+            assert len(ident[p][0]) == 0 or 0 <= ident[p][0][0] and ident[p][0][-1] < m.n_inserted[p]
+        now = {p: m.counters(p) for p in m.poses}
+        if k == "prune":
+            # every pose reads back the same rows and the same non-empty leaves; the five numbers add up; a prune that
+            # finds nothing leaves the pooled table standing, any other one invalidates it
+            n_nodes, n_voxels, nodes_dropped, voxels_dropped, collapsed = m.returned
+            assert {p: sorted(map(bytes, m.pose_rows(p))) for p in m.poses} == rows
+            assert all(now[p][1:] == held[p][1:] and now[p][0] <= held[p][0] for p in now)
+            assert [t for t, _ in q.obs[i].values()] == [t for t, _ in q.obs[i - 1].values()]
+            assert n_nodes == sum(t.root.n_nodes() for t in m.scheme_trees()) and n_voxels == len(m.scheme_trees())
+            assert (nodes_dropped > 0) == (voxels_dropped + collapsed > 0) and nodes_dropped >= voxels_dropped + 8 * collapsed
+            assert q.meta[i]["pooled"] == (q.meta[i - 1]["pooled"] and nodes_dropped == 0)
+            assert nodes_dropped == 0 or q.meta[i]["stats"] == "nan"
+            assert nodes_dropped > 0 or q.meta[i]["stats"] == q.meta[i - 1]["stats"]
+            assert m._prune(None, dry=True) == {"voxels": 0, "collapsed": 0, "outer": False, "bare": False}
+        if k == "remove_sparse":      # the booked return value is the rows that left, all of them from the tested poses
+            assert m.returned == sum(c[2] for c in held.values()) - sum(c[2] for c in now.values()) >= 0
+            assert all(now[p][2] == held[p][2] for p in now if op["poses"] is not None and p not in op["poses"])
+            assert all(set(sorted(map(bytes, m.pose_rows(p)))) <= set(rows[p]) for p in m.poses)
+            assert not q.meta[i]["pooled"]
+        if k == "radius_count":
+            cnt = m.returned
+            assert cnt.dtype == np.int32 and len(cnt) == op["n"] + 6 and not cnt[-6:-1].any() and cnt.min() >= 0
+            assert op["max_count"] is None or cnt.max() <= op["max_count"]
+        if k == "transform_poses":
+            assert not m.collapsed and not m.dropped      # (the map is rebuilt: the collapsed-node guard is lifted)
+            nxt = next(o["op"] for o in q.log[i + 1:] if o["op"] in S.ALL_MUTATING)
+            assert nxt in S.SUBDIVIDES, q.printed()
+        if k == "ransac":
+            assert sorted(m.poses) == list(range(len(m.poses)))
+    assert q.flags["depth2"] and q.flags["emptied"], q.printed()
+    assert q.closest > 1e-9
+    for p, (table, counters) in q.obs[-1].items():
+        assert counters[1] == len(table) and counters[2] == sum(d[0] for _, d in table)
+    assert not any(op.get("fn") == "shift_z" for op in q.log)
+
+
+def test_fourth_generation_covers_kinds_containers_and_transitions():
+    kinds, trans, containers, c = collections.Counter(), collections.Counter(), collections.Counter(), collections.Counter()
+    worst, f32, utm = 0.0, 0, 0
+    for seed in S.SEEDS4:
+        q = S.generate(seed)
+        kinds.update(op["op"] for op in q.log)
+        trans.update(S.transitions4(q.log, q.meta))
+        kind = q.container["kind"]
+        containers[kind] += 1
+        worst = max(worst, q.rejected / q.draws)
+        f32 += any(op.get("cloud", {}).get("form") in ("f32", "device32") for op in q.log)
+        utm += bool(q.container["utm"])
+        for i, op in enumerate(q.log):
+            k, facts = op["op"], q.meta[i].get("facts")
+            if k == "prune":
+                c["prune that drops a voxel"] += facts["voxels"] > 0
+                c["prune that collapses a node"] += facts["collapsed"] > 0
+                c["prune that finds nothing"] += facts["voxels"] + facts["collapsed"] == 0
+                c["prune that drops an outermost voxel"] += facts["outer"]
+                c["prune on a " + kind] += 1
+                c["manager emptied to its bare root"] += kind == "manager" and facts["bare"]
+            if k in ("insert", "insert_moved") and facts is not None:
+                c["insert that re-creates a dropped voxel"] += facts["recreated"] > 0
+            if k == "remove_sparse":
+                c["remove_sparse that removes rows"] += facts["removed"] > 0
+                c["remove_sparse that removes nothing"] += facts["removed"] == 0
+                c["remove_sparse of a pose subset"] += op["poses"] is not None
+                c["remove_sparse among a pose subset"] += op["among"] is not None
+            if k == "radius_count":
+                c[f"radius_count capped at {op['max_count']}"] += 1
+                c["radius_count with a saturated query"] += facts["saturated"] > 0
+            if k in ("point_registration_system", "nearest_plane_registration_system"):
+                name = "point" if k == "point_registration_system" else "plane"
+                c[name + " registration with Huber weights"] += op["huber_delta"] is not None
+                c[name + " registration with a given origin"] += op["origin"] is not None
+                c[name + " registration that uses no point"] += facts["n_used"] == 0
+                c[name + " registration that uses some points"] += 0 < facts["n_used"] < facts["n"]
+                if name == "plane":
+                    c["plane registration with a match in a leaf without a plane"] += facts["no_plane"] > 0
+            if k == "carve" and op.get("remapped"):
+                c["carve with evidence carried over a prune"] += 1
+    print("kinds:", dict(kinds))
+    print("transitions:", dict(trans))
+    print("containers:", dict(containers), "f32 / device32 seeds:", f32, "UTM seeds:", utm, "worst rejection share:", worst)
+    print("cases:", dict(c))
+    for k in S.GEN4_MUTATING + S.GEN4_READ_ONLY:
+        assert kinds[k] >= 5, (k, kinds[k])
+    for t in S.TRANSITIONS4:
+        assert trans[t] >= 2, (t, trans[t])
+    for k in ("grid", "manager", "octree"):
+        assert containers[k] >= 4, containers
+    assert f32 >= 3 and utm >= 2
+    assert c["prune that drops a voxel"] >= 3 and c["prune that collapses a node"] >= 4 and c["prune that finds nothing"] >= 2
+    assert c["prune on a manager"] >= 2 and c["prune on a octree"] >= 2 and c["manager emptied to its bare root"] >= 1
+    assert c["remove_sparse that removes rows"] >= 6 and c["remove_sparse that removes nothing"] >= 1
+    assert c["remove_sparse of a pose subset"] >= 2 and c["remove_sparse among a pose subset"] >= 2
+    for cap in (None, 1, 3, 7):
+        assert c[f"radius_count capped at {cap}"] >= 2, (cap, c)
+    assert c["radius_count with a saturated query"] >= 3
+    for name in ("point", "plane"):
+        assert c[name + " registration with Huber weights"] >= 2 and c[name + " registration with a given origin"] >= 2, c
+        assert c[name + " registration that uses no point"] >= 1 and c[name + " registration that uses some points"] >= 3, c
+    assert c["plane registration with a match in a leaf without a plane"] >= 2
+
+
+def test_collapsed_node_guard_rejects_a_refilled_node():
+    """No seed draws an insert once a prune has collapsed a node, so the guard is held here: after seed 303's log (a
+    manager whose prunes collapsed nodes) a cloud that fills the cube is Rejected; a cloud confined to a leaf that was
+    never collapsed is taken; and a transform_poses lifts the guard."""
+    q = S.generate(303)
+    m = S.Model.replay(q.container, q.log)
+    assert m.kind == "manager" and m.collapsed and any(q.meta[i]["facts"]["collapsed"] for i, op in enumerate(q.log)
+                                                        if op["op"] == "prune")
+    pose = next(p for p in S.MANAGER_POSES if p not in m.poses)
+    cloud = {"seed": 999001, "n": 4000, "edge": S.cloud_edge(q.container), "utm": False, "form": "f64", "cube": True}
+    with pytest.raises(S.Rejected, match="collapsed"):
+        m.apply({"op": "insert", "pose": pose, "cloud": cloud})
+    # the rejected draw leaves the model unusable, as in the generator: a fresh replay
+    m = S.Model.replay(q.container, q.log)
+    full = next(v for t in m.trees_of(m.poses[0]) for v in t.leaves(True))
+    key = (None, (np.asarray(full.corner, dtype=np.float64) + 0.0).tobytes(), float(full.edge))
+    assert key not in m.collapsed
+    inside = {**cloud, "n": 2000}
+    rows = S.model_cloud(inside)
+    lo, hi = rows.min(axis=0), rows.max(axis=0)
+    shrunk = np.asarray(full.corner, dtype=np.float64) + (rows - lo) / (hi - lo) * float(full.edge) * 0.999
+    tree = m.trees_of(m.poses[0])[0]
+    start = len(tree.points)
+    m.o.insert_points(m.poses[0], shrunk)      # (an extend by hand: every row into the one occupied leaf)
+    assert len(tree.points) == start + len(shrunk)
+    m._guard_collapsed()
+    identity = {"xi": [0.0] * 6, "origin": [0.0, 0.0, 0.0]}
+    m = S.Model.replay(q.container, q.log)
+    m.apply({"op": "transform_poses", "poses": None, "motions": [identity] * len(m.poses)})
+    assert not m.collapsed and not m.dropped
+
+
+_Leaf = S._Leaf
+
+
+@pytest.mark.parametrize("seed", [0, 7, 106, 115, 203, 214, 303, 302])
 def test_numpy_specifications_answer_the_models_tables(seed):
     """locate_np, pooled_leaf_statistics_np, point_to_plane_np (through HostMap, which rebuilds the node table from
     the leaves) and leaf_statistics_np on the model at the end of a sequence; at the end of two sequences of the second
     generation (115 contains a transform_poses) nearest_np, raycast_np, plane_segments_np, registration_system_np and
     adjustment_system_np too; at the end of two of the third (203: a manager after carve and remove_poses, 214: a UTM
-    grid after two removals) ray_evidence_np as well."""
+    grid after two removals) ray_evidence_np as well; at the end of two of the fourth (303: a manager after
+    remove_sparse and prune, 302: a UTM grid after a prune that dropped voxels) radius_count_np, sparse_keep_np and
+    the two nearest-point registration systems."""
     q = S.generate(seed)
     m = S.Model.replay(q.container, q.log)
     leaves = {p: [_Leaf(c, e, r) for c, e, r in m.leaf_rows(p, non_empty=False)] for p in m.poses}
@@ -361,7 +543,8 @@ def test_numpy_specifications_answer_the_models_tables(seed):
         assert int(ad.blocks.count.sum()) == len(stored)
     if seed < S.SEEDS3[0]:
         return
-    assert sum(op["op"] == "remove_poses" for op in q.log) >= (2 if seed == 214 else 1)
+    if seed < S.SEEDS4[0]:
+        assert sum(op["op"] == "remove_poses" for op in q.log) >= (2 if seed == 214 else 1)
     # rays from outside that measure exactly the distance to the stored point they aim at: every one of them ends in the
     # leaf of its point, none ends in an inner node, and the hits are at least the live rays that reach the map
     r = np.sqrt(((aim - O) ** 2).sum(axis=1))
@@ -374,3 +557,28 @@ def test_numpy_specifications_answer_the_models_tables(seed):
     silent = hm.ray_evidence(O, aim - O, r, 0.05 * e, returned=np.zeros(len(aim), dtype=bool))
     assert not silent.hits.any() and np.all(silent.through >= ev.through)
     assert not np.any(ev.free(1, 0) & (np.bincount(leaf, minlength=len(ev)) > 0))      # carve would keep what was hit
+    if seed < S.SEEDS4[0]:
+        return
+    prunes = [q.meta[i]["facts"] for i, op in enumerate(q.log) if op["op"] == "prune"]
+    assert prunes and any(op["op"] == "remove_sparse" for op in q.log)
+    assert seed != 302 or (q.container["utm"] and any(f["voxels"] > 0 for f in prunes))
+    # every stored point counts itself at a tiny radius; a cap only cuts the count
+    some = stored[::20]
+    assert np.all(hm.radius_count(some, 1e-6 * e, max_count=1) == 1)
+    free, capped = hm.radius_count(some, 0.2 * e), hm.radius_count(some, 0.2 * e, max_count=3)
+    assert free.dtype == np.int32 and np.all(free >= capped) and np.array_equal(capped, np.minimum(free, 3))
+    # the decisions of remove_sparse: one per stored row - and the model's tiled evaluation is the rule itself
+    decided = hm.remove_sparse(0.1 * e, 2)
+    assert [p for p, _ in decided] == m.poses and all(len(k) == len(m.pose_rows(p)) for p, k in decided)
+    tiled = S.sparse_keep_tiled({p: m.pose_rows(p) for p in m.poses}, m.poses, m.poses, 0.1 * e, 2)
+    assert all(np.array_equal(k, tiled[p]) for p, k in decided) and any((~k).any() for _, k in decided)
+    part = m.poses[:1]
+    other = [(p, k) for p, k in hm.remove_sparse(0.1 * e, 2, pose_numbers=m.poses[-1:], among=part)]
+    tiled = S.sparse_keep_tiled({p: m.pose_rows(p) for p in m.poses}, m.poses[-1:], part, 0.1 * e, 2)
+    assert [p for p, _ in other] == m.poses[-1:] and np.array_equal(other[0][1], tiled[m.poses[-1]])
+    # stored rows as a scan at the identity: every point is its own nearest point
+    scan = stored[::15][:600]
+    ps = hm.point_registration_system(scan, None, max_distance=0.05 * e)
+    assert ps.cost == 0 and ps.n_used == ps.n_located == len(scan)
+    ns = hm.nearest_plane_registration_system(scan, None, max_distance=0.05 * e, per_point=True)
+    assert ns.n_used <= ns.n_located == len(scan) and np.array_equal(ns.node, hm.locate(scan))

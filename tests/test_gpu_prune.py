@@ -272,24 +272,32 @@ def _through(x, node_map):
     return dataclasses.replace(x, planes=_through(x.planes, node_map)) if hasattr(x, "planes") else x
 
 
-def _queries(g):
-    """Every map query as ("answer", x), or ("raises", kind) where the map refuses it (both must agree)."""
+# the queries and rays of _queries: this module's scene (a map of another extent passes its own)
+SCENE = {"queries": QUERIES, "origins": RAYS_O, "directions": RAYS_D, "ranges": RAYS_R, "margin": 0.05, "max_range": 6.0,
+         "radius": 0.3, "max_variance": 1e-2, "origin": ORIGIN}
+
+
+def _queries(g, scene=SCENE):
+    """Every map query as ("answer", x), or ("raises", kind) where the map refuses it (both must agree).  g: a Grid,
+    an OctreeManager or an Octree (which takes no pose selection and has no adjustment: that one refuses, both times)."""
+    sel = () if isinstance(g, Octree) else (None,)
+    Q, O, D, R, mv = (scene[k] for k in ("queries", "origins", "directions", "ranges", "max_variance"))
     return {
-        "locate": _try(lambda: g.locate(QUERIES)),
+        "locate": _try(lambda: g.locate(Q)),
         "planes": _try(lambda: g.leaf_planes()),
-        "p2p": _try(lambda: g.point_to_plane(QUERIES, None, 8, 1e-2)),
-        "ray_cube": _try(lambda: g.raycast(RAYS_O, RAYS_D, 6.0)),
-        "ray_plane": _try(lambda: g.raycast(RAYS_O, RAYS_D, 6.0, surface="plane", max_variance=1e-2)),
-        "nearest": _try(lambda: g.nearest(QUERIES, 4, max_distance=0.3)),
-        "registration": _try(lambda: g.registration_system(QUERIES, None, None, max_variance=1e-2)),
-        "adjustment": _try(lambda: g.adjustment_system(None, None, origin=ORIGIN, max_variance=1e-2)),
-        "segments": _try(lambda: g.plane_segments(None, max_variance=1e-2)),
-        "evidence": _try(lambda: g.ray_evidence(RAYS_O, RAYS_D, RAYS_R, 0.05)),
+        "p2p": _try(lambda: g.point_to_plane(Q, *sel, 8, mv)),
+        "ray_cube": _try(lambda: g.raycast(O, D, scene["max_range"])),
+        "ray_plane": _try(lambda: g.raycast(O, D, scene["max_range"], surface="plane", max_variance=mv)),
+        "nearest": _try(lambda: g.nearest(Q, 4, max_distance=scene["radius"])),
+        "registration": _try(lambda: g.registration_system(Q, None, *sel, max_variance=mv)),
+        "adjustment": _try(lambda: g.adjustment_system(None, None, origin=scene["origin"], max_variance=mv)),
+        "segments": _try(lambda: g.plane_segments(*sel, max_variance=mv)),
+        "evidence": _try(lambda: g.ray_evidence(O, D, R, scene["margin"])),
     }
 
 
-def _queries_equal(a, b, res, nodes_before, g, what):
-    """a: before (or the unpruned twin), b: after, on the map g."""
+def _queries_equal(a, b, res, nodes_before, g, what, scene=SCENE):
+    """a: before (or the unpruned twin), b: after, on the map g; scene: what _queries was given."""
     m = res.node_map
     for name in a:
         assert a[name][0] == b[name][0] and (a[name][0] == "answer" or a[name][1] == b[name][1]), (what, name, a[name])
@@ -313,9 +321,9 @@ def _queries_equal(a, b, res, nodes_before, g, what):
         table = a["segments"].segments
         table = dataclasses.replace(table, root=_mapped(table.root, m))        # (a segment's root leaf is a node id)
         _same_bits(b["segments"].segments, table, f"{what}: segments.segments")
-        spec = plane_segments_np(b["planes"], f.nodes, f.voxels, f.mode, f._cube[1], max_variance=1e-2)
+        spec = plane_segments_np(b["planes"], f.nodes, f.voxels, f.mode, f._cube[1], max_variance=scene["max_variance"])
         _same_bits(b["segments"].neighbour, spec.neighbour, f"{what}: segments.neighbour")
-    inp = evidence_inputs(RAYS_O, RAYS_D, RAYS_R, 0.05)
+    inp = evidence_inputs(scene["origins"], scene["directions"], scene["ranges"], scene["margin"])
     assert_evidence_equal(b["evidence"], evidence_of_nodes(f.nodes, *inp), f"{what}: ray_evidence")
     carried = a["evidence"].remapped(res)
     same = (nodes_before["first_child"][res.old_node] >= 0) == (f.nodes["first_child"] >= 0)      # (not collapsed)

@@ -7,7 +7,13 @@ compared with those after through PruneResult.node_map (_queries_equal).  The pr
 are compared by everything a pose reads back (_reads_equal) after every prune - up to the first late pose inserted
 into a map that has been pruned: from there on the two schemes differ by definition (a re-created voxel is an unsplit
 root at the end of the creation order, a collapsed node that is split again has a new epoch), per-leaf operations see
-other leaves, and the twin is no reference any more; the two self-checks go on to the end of the sequence."""
+other leaves, and the twin is no reference any more; the two self-checks go on to the end of the sequence.
+
+The two sequence tests divide the work: this one holds prune against an UNPRUNED TWIN, on one Grid in f64 with seven
+kinds of operation; tests/test_gpu_opseq.py (SEEDS4) draws prune among every other operation of the API - on Grid,
+OctreeManager and Octree, f32 and UTM clouds, next to plane_segments, adjustment_system, transform_poses, filters and
+the radius searches - against the oracle MODEL pruned by the definition, with the same two self-checks on every
+drawn prune."""
 
 import numpy as np
 import pytest
