@@ -470,6 +470,50 @@ int octl_forest_radius_count_device(octl_forest* f, const double* xyz_dev, int64
  * one upload and one wait for a tested selection.  No reference counterpart.                                        */
 int octl_forest_remove_sparse(octl_forest* f, double radius, int32_t min_neighbours, const uint8_t* slot_sel,
                               int32_t n_sel, const uint8_t* among_sel, int32_t n_among, int64_t* n_alive);
+/* How many stored points lie in the lattice cell of every query point?  The lattice is absolute (origin 0, nothing to
+ * do with the subdivision): the cell of p is floor(p / cell) per axis, the floor of the TRUE quotient as
+ * np.floor_divide forms it, and two points share a cell iff the three indices are equal.  The counted points are those
+ * of octl_forest_radius_count: of the selected poses (slot_sel: n_sel = number of poses flags, NULL = every pose),
+ * alive and in the leaf-ordered arrays.  count[i] = min(number of stored points of the cell, max_count), int32;
+ * max_count = 0: uncapped.  A query with a coordinate that is not finite counts 0.  octreelib_amd/thinning.py:
+ * cell_count_np is the same by hashing, count for count.  The search is the stackless walk of octl_forest_nearest with
+ * a box prune and a sink that counts; membership is decided on the signs of two fused remainders, without a division;
+ * a capped query stops at the cap.
+ * OCTL_E_INVALID: max_count < 0; cell not finite or <= 0; a grid with cell above the voxel edge L or below L 2^-20, a
+ * single cube with max(|corner|, |corner + edge|) / cell >= 2^50 (every cell index of the map's domain stays an exact
+ * double); n < 0 or >= 2^31; a NULL array with n > 0; a selection of the wrong length.  OCTL_E_STATE: before the first
+ * build; a forest whose rows map_leaf_points moved outside their leaves.  All before anything runs.  n = 0 returns
+ * without a kernel.  The index of the blocks by node (octl_forest_nearest's own, under its stamp) is made by the call
+ * that finds it missing, stale or made for another selection; with it in place a call is one kernel, plus one upload,
+ * one download and one wait.  Read-only otherwise.  No reference counterpart.                                       */
+int octl_forest_cell_count(octl_forest* f, const double* xyz, int64_t n, double cell, int32_t max_count,
+                           const uint8_t* slot_sel, int32_t n_sel, int32_t* count);
+/* The same with pointers from octl_dev_alloc (slot_sel stays a host array): one kernel, nothing is downloaded and
+ * the host does not wait.  No reference counterpart.                                                             */
+int octl_forest_cell_count_device(octl_forest* f, const double* xyz_dev, int64_t n, double cell, int32_t max_count,
+                                  const uint8_t* slot_sel, int32_t n_sel, int32_t* count_dev);
+/* Voxel-grid thinning: of the points of the leaf-ordered arrays that share a lattice cell (octl_forest_cell_count's
+ * cells) only the first max_per_cell stay.  The order is that of the point store: poses in slot order, rows in
+ * insertion order - the (slot, index) order of octl_forest_nearest.  For a point x of a tested pose (slot_sel[slot]
+ * != 0; NULL: every pose; otherwise n_sel = number of poses), rank(x) = the stored points y of the counted poses
+ * (among_sel / n_among likewise) in the cell of x that come BEFORE x in that order: x never counts itself, an earlier
+ * duplicate at the same coordinates does, and a tested pose that is not counted is judged against the counted ones
+ * only.  keep(x) iff rank(x) < max_per_cell (the count saturates there).  Every decision is made on the map as it is
+ * before the call - one simultaneous round; with every pose tested and counted it keeps exactly the first
+ * max_per_cell points of every cell and a second call removes nothing.  octreelib_amd/thinning.py: thin_keep_np is
+ * the rule.  Points that a pending RANSAC mask is about to drop are still in the ordered arrays: they occupy cells and
+ * are judged (the kernel never reads the mask).  The kernel clears bytes in the mask and the mask is applied as
+ * octl_forest_remove_sparse applies its own: a pending RANSAC mask goes into the same ONE compaction.  The scheme
+ * stays; the index of octl_forest_nearest of a surviving row is unchanged; the block index, the pooled planes, the
+ * segments and the adjustment tables go stale.  *n_alive (nullable) = points left in the leaf-ordered arrays.
+ * OCTL_E_INVALID: max_per_cell < 1; cell as octl_forest_cell_count refuses it; a selection of the wrong length.
+ * OCTL_E_STATE: before the first build; a forest whose rows map_leaf_points moved outside their leaves.  All before
+ * anything runs: a refused call leaves points and mask as they were, and every buffer is reserved before the mask is
+ * written.  One wavefront per (leaf, pose) block; with the index of among_sel in place a call is one kernel (which
+ * also writes the ones of a mask that was not pending) and the compaction, plus one upload and one wait for a tested
+ * selection.  No reference counterpart.                                                                            */
+int octl_forest_thin(octl_forest* f, double cell, int32_t max_per_cell, const uint8_t* slot_sel, int32_t n_sel,
+                     const uint8_t* among_sel, int32_t n_among, int64_t* n_alive);
 /* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
  * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
  * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in

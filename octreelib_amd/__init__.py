@@ -24,6 +24,7 @@ from octreelib_amd.matching import align_nearest_planes, nearest_plane_registrat
 from octreelib_amd.registration import (Alignment, RegistrationSystem, align_np, nearest_plane_registration_system_np,
                                         point_registration_system_np, registration_system_np, se3_exp, transform_np,
                                         transform_rows_np)
+from octreelib_amd.thinning import cell_count, cell_count_np, cell_index_np, check_cell_args, thin, thin_keep_np
 
 __version__ = "0.1.0"
 __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empty", "upload_async", "LeafPlanes",
@@ -34,4 +35,5 @@ __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empt
            "nearest_np", "PlaneSegments", "plane_segments_np", "RayHits", "raycast_np", "normalize_directions",
            "RayEvidence", "ray_evidence_np", "carve_keep_np", "PruneResult", "prune_np", "radius_count_np",
            "sparse_keep_np", "nearest_plane_registration_system_np", "nearest_plane_registration_system",
-           "align_nearest_planes", "__version__"]
+           "align_nearest_planes", "cell_index_np", "cell_count_np", "thin_keep_np", "check_cell_args", "cell_count",
+           "thin", "__version__"]

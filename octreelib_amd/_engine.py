@@ -798,6 +798,76 @@ class Forest:
         self._invalidate()
         return before - n.value
 
+    def cell_count(self, points, cell, max_count=None, slots=None) -> np.ndarray:
+        """How many stored points of the poses of `slots` (None: all) lie in the lattice cell of every query point,
+        capped at max_count (None: uncapped): (n,) int32 as thinning.cell_count_np defines it (octl_forest_cell_count:
+        one kernel once the block index of the selection exists).  points: a host array, or a feed.DeviceCloud of f64
+        points, which is read where it lies."""
+        from octreelib_amd.feed import DeviceCloud
+        from octreelib_amd.query import _as_queries
+        from octreelib_amd.thinning import check_cell_args
+
+        c, max_count, _ = check_cell_args(cell, max_count)
+        cap = 0 if max_count is None else max_count
+        if isinstance(points, DeviceCloud):
+            if np.dtype(points.dtype) != np.float64:
+                raise ValueError("cell_count: a DeviceCloud of float64 points is needed (f32 queries are not "
+                                 "supported)")
+            points.wait()
+            n = len(points)
+            count = np.zeros(n, dtype=np.int32)
+            lib, h = self.lib, self.ctx.handle
+            out = C.c_void_p()
+            self.ctx.check(lib.octl_dev_alloc(h, max(4 * n, 8), C.byref(out)))
+            try:
+                self.cell_count_device(points.ptr, n, c, out, max_count, slots)
+                if n:
+                    self.ctx.check(lib.octl_dev_download(h, nat.ptr(count), out, count.nbytes))
+            finally:
+                lib.octl_dev_free(h, out)
+            return count
+        pts = _as_queries(points)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        n = len(pts)
+        count = np.zeros(n, dtype=np.int32)
+        # (n = 0 still goes to the library: what it refuses whatever the queries is refused for an empty scan too)
+        self.ctx.check(self.lib.octl_forest_cell_count(self.handle, nat.ptr(pts), n, c, cap, nat.ptr(sel), n_sel,
+                                                       nat.ptr(count)))
+        return count
+
+    def cell_count_device(self, xyz_dptr, n: int, cell, count_dptr, max_count=None, slots=None):
+        """cell_count for points that are in device memory already, the (n,) int32 answer left there (pointers from
+        octl_dev_alloc); enqueued on the context's stream, the host does not wait."""
+        from octreelib_amd.thinning import check_cell_args
+
+        c, max_count, _ = check_cell_args(cell, max_count)
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        self.ctx.check(self.lib.octl_forest_cell_count_device(self.handle, xyz_dptr, int(n), c,
+                                                              0 if max_count is None else max_count, nat.ptr(sel),
+                                                              n_sel, count_dptr))
+
+    def thin(self, cell, max_per_cell=1, slots=None, among=None) -> int:
+        """Voxel-grid thinning: of the points that share a lattice cell, every point of the poses of `slots` (None:
+        all) that has max_per_cell or more points of the poses of `among` (None: all) before it - poses in slot order,
+        rows in insertion order - leaves the map (octl_forest_thin: one kernel, one compaction that also applies a
+        pending RANSAC mask; thinning.thin_keep_np is the rule); the scheme stays.  Returns the number of points
+        removed."""
+        from octreelib_amd.thinning import _required, check_cell_args
+
+        c, _, m = check_cell_args(cell, None, _required(max_per_cell), what="thin")
+        self.ensure_built()
+        before = self.n_ord
+        sel, n_sel, _ = self._adjust_selection(slots)
+        asel, n_asel, _ = self._adjust_selection(among)
+        n = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_thin(self.handle, c, m, nat.ptr(sel), n_sel, nat.ptr(asel), n_asel,
+                                                 C.byref(n)))
+        self.n_ord = n.value
+        self._invalidate()
+        return before - n.value
+
     def _raycast_args(self, max_range, min_range, surface, min_points, max_variance, origins, directions):
         from octreelib_amd.query import check_raycast_args, check_raycast_cap, normalize_directions, ray_inputs
 

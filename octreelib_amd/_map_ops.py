@@ -11,6 +11,8 @@ The inheriting class provides
   _plug_poses()            the plug's table that is keyed by pose number
   _noun                    "a Grid" / "an OctreeManager", for the refusals on the caller's own plug types
 
+The module-level map functions (matching.py, thinning.py) take any of the three classes and start with _resolve below.
+
 Octree is not served from here: its operations take no pose_numbers, so every signature differs, and each is already
 two lines over Forest.
 """
@@ -24,6 +26,25 @@ from octreelib_amd.query import LeafPlanes, Neighbours, PlaneSegments, PointToPl
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
 __all__ = ["MapOperations"]
+
+
+def _resolve(map, pose_numbers, what):
+    """What the module-level map functions (matching.py, thinning.py) start with: (forest or None, HostMap or None,
+    selection, pose numbers in slot order) of a Grid, an OctreeManager or an Octree; TypeError for anything else,
+    ValueError for an Octree with pose_numbers, KeyError for an unknown pose."""
+    from octreelib_amd.octree import Octree
+
+    if isinstance(map, Octree):
+        if pose_numbers is not None:
+            raise ValueError(f"{what}: an Octree holds a single pose and takes no pose_numbers")
+        map._query_ready()
+        return map._forest, None, None, [0] * map._forest.n_slots
+    if not isinstance(map, MapOperations):
+        raise TypeError(f"{what}: expected a Grid, an OctreeManager or an Octree, got {type(map).__name__}")
+    sel = map._query_slots(pose_numbers)
+    if map._plug is not None:
+        return None, map._host_map(), sel, None
+    return map._forest, None, sel, map._adjust_names(None)
 
 
 class MapOperations:

@@ -141,22 +141,11 @@ int nn_prepare(octl_forest* f, const std::vector<uint8_t>& sel) {
   return OCTL_OK;
 }
 
-// what both forms start with, and octl_forest_point_registration_system (register_points.hip) too: the refusals, the
-// tables, the index - made only when missing or stale (the declaration: nearest_walk.h)
-int nearest_begin(octl_forest* f, const char* what, int64_t n, int32_t k, double max_distance, const uint8_t* slot_sel,
-                  int32_t n_sel, bool pointers_ok, NNTables* T) {
-  OCTL_TRY(query_begin(f, what, &T->t));
+// the tail of nearest_begin, shared with cell_begin (cell.hip): the selection, the refusal of displaced rows, then -
+// for n > 0 - the index, made only when missing, stale or made for another selection, and the tables of the walk
+// (T->t is the caller's, from query_begin).  The declaration: nearest_walk.h
+int nn_tables(octl_forest* f, const char* what, int64_t n, const uint8_t* slot_sel, int32_t n_sel, NNTables* T) {
   octl_ctx* ctx = f->ctx;
-  if (query_bad_count(n) || !pointers_ok) return octl_set_error(ctx, OCTL_E_INVALID, "bad %s arguments", what);
-  if (k < 1 || k > OCTL_NN_MAX_K)
-    return octl_set_error(ctx, OCTL_E_INVALID, "%s: k = %d is outside 1 .. %d", what, k, OCTL_NN_MAX_K);
-  if (!(std::isfinite(max_distance) && max_distance > 0.0))
-    return octl_set_error(ctx, OCTL_E_INVALID, "%s: max_distance must be finite and positive", what);
-  if (f->mode == 0 && max_distance > 2.0 * f->edge)
-    return octl_set_error(ctx, OCTL_E_INVALID,
-                          "%s: max_distance %g exceeds twice the voxel edge %g (a query would touch more than 5 "
-                          "voxels per axis)",
-                          what, max_distance, f->edge);
   std::vector<uint8_t> sel;
   OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
   if (f->displaced_rows)
@@ -176,6 +165,25 @@ int nearest_begin(octl_forest* f, const char* what, int64_t n, int32_t k, double
   T->ord_idx = f->ord_idx.as<uint32_t>();
   T->max_steps = 4 * nt.n + 64;
   return OCTL_OK;
+}
+
+// what both forms start with, and octl_forest_point_registration_system (register_points.hip) too: the refusals, the
+// tables, the index - made only when missing or stale (the declaration: nearest_walk.h)
+int nearest_begin(octl_forest* f, const char* what, int64_t n, int32_t k, double max_distance, const uint8_t* slot_sel,
+                  int32_t n_sel, bool pointers_ok, NNTables* T) {
+  OCTL_TRY(query_begin(f, what, &T->t));
+  octl_ctx* ctx = f->ctx;
+  if (query_bad_count(n) || !pointers_ok) return octl_set_error(ctx, OCTL_E_INVALID, "bad %s arguments", what);
+  if (k < 1 || k > OCTL_NN_MAX_K)
+    return octl_set_error(ctx, OCTL_E_INVALID, "%s: k = %d is outside 1 .. %d", what, k, OCTL_NN_MAX_K);
+  if (!(std::isfinite(max_distance) && max_distance > 0.0))
+    return octl_set_error(ctx, OCTL_E_INVALID, "%s: max_distance must be finite and positive", what);
+  if (f->mode == 0 && max_distance > 2.0 * f->edge)
+    return octl_set_error(ctx, OCTL_E_INVALID,
+                          "%s: max_distance %g exceeds twice the voxel edge %g (a query would touch more than 5 "
+                          "voxels per axis)",
+                          what, max_distance, f->edge);
+  return nn_tables(f, what, n, slot_sel, n_sel, T);
 }
 
 extern "C" {

@@ -28,6 +28,9 @@ struct NNTables {
 // `what`, then the tables and the block index of the selection - made only when missing or stale
 int nearest_begin(octl_forest* f, const char* what, int64_t n, int32_t k, double max_distance, const uint8_t* slot_sel,
                   int32_t n_sel, bool pointers_ok, NNTables* T);
+// nearest.hip.  Its tail, for a search with refusals of its own (cell_walk.h: cell_begin): the selection, the refusal of
+// displaced rows and, for n > 0, the index and the tables of the walk; T->t is the caller's (query_begin)
+int nn_tables(octl_forest* f, const char* what, int64_t n, const uint8_t* slot_sel, int32_t n_sel, NNTables* T);
 
 // A representable lower bound g >= 0 of |fl(q - p)| along one axis for every point p the cube (c, e) can hold.
 //

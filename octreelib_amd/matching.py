@@ -17,28 +17,10 @@ query.HostMap (octreelib_amd/registration.py: nearest_plane_registration_system_
 
 from typing import List, Optional
 
+from octreelib_amd._map_ops import _resolve
 from octreelib_amd.registration import Alignment, RegistrationSystem
 
 __all__ = ["nearest_plane_registration_system", "align_nearest_planes"]
-
-
-def _resolve(map, pose_numbers, what):
-    """(forest or None, HostMap or None, selection, pose numbers in slot order) of a Grid, an OctreeManager or an
-    Octree; TypeError for anything else, ValueError for an Octree with pose_numbers, KeyError for an unknown pose."""
-    from octreelib_amd._map_ops import MapOperations
-    from octreelib_amd.octree import Octree
-
-    if isinstance(map, Octree):
-        if pose_numbers is not None:
-            raise ValueError(f"{what}: an Octree holds a single pose and takes no pose_numbers")
-        map._query_ready()
-        return map._forest, None, None, [0] * map._forest.n_slots
-    if not isinstance(map, MapOperations):
-        raise TypeError(f"{what}: expected a Grid, an OctreeManager or an Octree, got {type(map).__name__}")
-    sel = map._query_slots(pose_numbers)
-    if map._plug is not None:
-        return None, map._host_map(), sel, None
-    return map._forest, None, sel, map._adjust_names(None)
 
 
 def nearest_plane_registration_system(map, points, transform=None, *, max_distance: float,
