@@ -514,6 +514,52 @@ int octl_forest_cell_count_device(octl_forest* f, const double* xyz_dev, int64_t
  * selection.  No reference counterpart.                                                                            */
 int octl_forest_thin(octl_forest* f, double cell, int32_t max_per_cell, const uint8_t* slot_sel, int32_t n_sel,
                      const uint8_t* among_sel, int32_t n_among, int64_t* n_alive);
+/* What the surface looks like round every query point: count, mean, population covariance (6 upper-triangle values xx
+ * xy xz yy yz zz) and its eigen-decomposition - conventions, sign rule and solver of octl_forest_leaf_stats - of the
+ * stored points within `radius`.  The neighbours are exactly the points octl_forest_radius_count counts, uncapped: the
+ * same walk, the same d2 bits, the same inclusive d2 <= radius * radius, the same selection (slot_sel: n_sel = number
+ * of poses flags, NULL = every pose), so count[i] is its count.  Arithmetic: the sums of d = fl(p - q) and of d d^T
+ * (fma) in f64, one neighbour after the other in the order of the walk, then mean = q + S_d / n and cov = S_dd / n -
+ * (S_d / n)(S_d / n)^T; a single neighbour has covariance 0 exactly.  With n neighbours, R = max |p - q|_inf over them
+ * and g = (n + 16) * 2^-53: mean within 2 g R + 2^-53 |mean|, every covariance entry within 4 g R^2 of the exact value
+ * (the magnitude of the coordinates does not enter); eigenvalues within 64 * 2^-53 * |C|_F of those of the returned
+ * covariance.  A row's bits depend on the forest's tables and on the query's bits only - not on the batch, not on
+ * where the query lies in memory; another subdivision of the same points walks in another order and may differ within
+ * the bound.  A query that is not finite, and one without a neighbour, has count 0 and NaN in every other field.
+ * outputs: count (n) i64, mean (n,3), cov (n,6), eigval (n,3), eigvec (n,3,3) columns = eigenvectors; any may be NULL,
+ * eigval and eigvec only together (both NULL: no decomposition).  octreelib_amd/neighbourhood.py:
+ * neighbourhood_statistics_np is the definition.
+ * OCTL_E_INVALID: radius not finite or <= 0; a grid with radius above twice the voxel edge; n < 0 or >= 2^31; xyz NULL
+ * with n > 0; a selection of the wrong length.  OCTL_E_STATE: before the first build; a forest whose rows
+ * map_leaf_points moved outside their leaves.  All before anything runs.  n = 0 returns without a kernel.  With the
+ * index of the selection in place (octl_forest_nearest's own) a call is one kernel, plus one upload, the downloads and
+ * one wait.  Read-only otherwise.  No reference counterpart.                                                        */
+int octl_forest_neighbourhood_stats(octl_forest* f, const double* xyz, int64_t n, double radius,
+                                    const uint8_t* slot_sel, int32_t n_sel, int64_t* count, double* mean, double* cov,
+                                    double* eigval, double* eigvec);
+/* The same with pointers from octl_dev_alloc (slot_sel stays a host array; count, mean and cov are required): one
+ * kernel, nothing is downloaded and the host does not wait.  No reference counterpart.                           */
+int octl_forest_neighbourhood_stats_device(octl_forest* f, const double* xyz_dev, int64_t n, double radius,
+                                           const uint8_t* slot_sel, int32_t n_sel, int64_t* count_dev,
+                                           double* mean_dev, double* cov_dev, double* eigval_dev, double* eigvec_dev);
+/* The self-query: one row of octl_forest_neighbourhood_stats for every point of the leaf-ordered arrays that belongs
+ * to a tested pose (slot_sel[slot] != 0; NULL: every pose; otherwise n_sel = number of poses), over the stored points
+ * of the counted poses (among_sel / n_among likewise), with q = the stored bits of the point - the row
+ * octl_forest_neighbourhood_stats gives for those bits under the selection among_sel, bit for bit.  The point counts
+ * itself when its pose is counted (the opposite of octl_forest_remove_sparse).  Points that a pending RANSAC mask is
+ * about to drop are still in the ordered arrays: they have rows and count.  slot[i], index[i] (int32) name the point
+ * of row i: its pose's slot and its row in that pose's cloud as inserted (the index of octl_forest_nearest).  The
+ * rows come in no particular order: the caller sorts them by (slot, index).  *n_rows = number of rows; they are
+ * written only when cap >= *n_rows (size query: cap = 0), and a cap of at least min(ordered points, store rows of
+ * the tested poses) saves the second wait.  Other outputs as above, any may be NULL.
+ * OCTL_E_INVALID: cap < 0; n_rows NULL; radius as above; a selection of the wrong length.  OCTL_E_STATE as above.  One
+ * wavefront per (leaf, pose) block; with the index of among_sel in place a call is one fill and one kernel, plus one
+ * upload for a tested selection, the downloads and one wait (two when cap is below the bound).  Nothing of the forest
+ * changes and no cached table is dropped.  No reference counterpart.                                              */
+int octl_forest_point_stats(octl_forest* f, double radius, const uint8_t* slot_sel, int32_t n_sel,
+                            const uint8_t* among_sel, int32_t n_among, int64_t cap, int64_t* n_rows, int32_t* slot,
+                            int32_t* index, int64_t* count, double* mean, double* cov, double* eigval,
+                            double* eigvec);
 /* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
  * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
  * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in

@@ -21,6 +21,8 @@ from octreelib_amd.query import (LeafPlanes, Neighbours, PlaneSegments, PointToP
                                  point_to_plane_np, pooled_leaf_statistics_np, prune_np, radius_count_np, ray_evidence_np,
                                  raycast_np, sparse_keep_np)
 from octreelib_amd.matching import align_nearest_planes, nearest_plane_registration_system
+from octreelib_amd.neighbourhood import (PointStatistics, neighbourhood_statistics, neighbourhood_statistics_np,
+                                         orient_towards, point_statistics, point_statistics_np)
 from octreelib_amd.registration import (Alignment, RegistrationSystem, align_np, nearest_plane_registration_system_np,
                                         point_registration_system_np, registration_system_np, se3_exp, transform_np,
                                         transform_rows_np)
@@ -36,4 +38,5 @@ __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empt
            "RayEvidence", "ray_evidence_np", "carve_keep_np", "PruneResult", "prune_np", "radius_count_np",
            "sparse_keep_np", "nearest_plane_registration_system_np", "nearest_plane_registration_system",
            "align_nearest_planes", "cell_index_np", "cell_count_np", "thin_keep_np", "check_cell_args", "cell_count",
-           "thin", "__version__"]
+           "thin", "PointStatistics", "neighbourhood_statistics", "neighbourhood_statistics_np", "point_statistics",
+           "point_statistics_np", "orient_towards", "__version__"]

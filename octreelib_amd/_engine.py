@@ -798,6 +798,112 @@ class Forest:
         self._invalidate()
         return before - n.value
 
+    def neighbourhood_stats(self, points, radius, slots=None, eigen: bool = True):
+        """Count, mean, population covariance and (eigen=True) its eigen-decomposition of the stored points of the poses
+        of `slots` (None: all) within `radius` of every query point: a LeafStatistics with one row per query, as
+        neighbourhood.neighbourhood_statistics_np defines it (octl_forest_neighbourhood_stats: one kernel once the block
+        index of the selection exists).  points: a host array, or a feed.DeviceCloud of f64 points, which is read where
+        it lies."""
+        from octreelib_amd.feed import DeviceCloud
+        from octreelib_amd.leaf_stats import LeafStatistics, cov6_to_full
+        from octreelib_amd.query import _as_queries, check_radius_args
+
+        r, _, _ = check_radius_args(radius, what="neighbourhood_statistics")
+        device = isinstance(points, DeviceCloud)
+        if device:
+            if np.dtype(points.dtype) != np.float64:
+                raise ValueError("neighbourhood_statistics: a DeviceCloud of float64 points is needed (f32 queries "
+                                 "are not supported)")
+            points.wait()
+            n = len(points)
+        else:
+            pts = _as_queries(points)
+            n = len(pts)
+        count = np.zeros(n, dtype=np.int64)
+        mean = np.empty((n, 3), dtype=np.float64)
+        cov = np.empty((n, 6), dtype=np.float64)
+        w = np.empty((n, 3), dtype=np.float64) if eigen else None
+        v = np.empty((n, 3, 3), dtype=np.float64) if eigen else None
+        outs = [a for a in (count, mean, cov, w, v) if a is not None]
+        if device:
+            lib, h = self.lib, self.ctx.handle
+            bufs = [C.c_void_p() for _ in outs]
+            try:
+                for b, a in zip(bufs, outs):
+                    self.ctx.check(lib.octl_dev_alloc(h, max(a.nbytes, 8), C.byref(b)))
+                self.neighbourhood_stats_device(points.ptr, n, r, *bufs[:3], *(bufs[3:] if eigen else (None, None)),
+                                                slots=slots)
+                for b, a in zip(bufs, outs):
+                    if n:
+                        self.ctx.check(lib.octl_dev_download(h, nat.ptr(a), b, a.nbytes))
+            finally:
+                for b in bufs:
+                    if b.value:
+                        lib.octl_dev_free(h, b)
+        else:
+            self.ensure_built()
+            sel, n_sel, _ = self._adjust_selection(slots)
+            # (n = 0 still goes to the library: what it refuses whatever the queries is refused for an empty scan too)
+            self.ctx.check(self.lib.octl_forest_neighbourhood_stats(self.handle, nat.ptr(pts), n, r, nat.ptr(sel),
+                                                                    n_sel, nat.ptr(count), nat.ptr(mean), nat.ptr(cov),
+                                                                    nat.ptr(w), nat.ptr(v)))
+        return LeafStatistics(count, mean, cov6_to_full(cov), w, v)
+
+    def neighbourhood_stats_device(self, xyz_dptr, n: int, radius, count_dptr, mean_dptr, cov_dptr, eigval_dptr=None,
+                                   eigvec_dptr=None, slots=None):
+        """neighbourhood_stats for points that are in device memory already, the rows - count (n,) int64, mean (n, 3),
+        cov (n, 6), eigval (n, 3), eigvec (n, 3, 3) float64; the last two None: no decomposition - left there (pointers
+        from octl_dev_alloc); enqueued on the context's stream, the host does not wait."""
+        from octreelib_amd.query import check_radius_args
+
+        r, _, _ = check_radius_args(radius, what="neighbourhood_statistics")
+        self.ensure_built()
+        sel, n_sel, _ = self._adjust_selection(slots)
+        self.ctx.check(self.lib.octl_forest_neighbourhood_stats_device(self.handle, xyz_dptr, int(n), r, nat.ptr(sel),
+                                                                       n_sel, count_dptr, mean_dptr, cov_dptr,
+                                                                       eigval_dptr, eigvec_dptr))
+
+    def point_stats(self, radius, slots=None, among=None, eigen: bool = True, pose_of_slot=None):
+        """The self-query: one row of neighbourhood_stats for every alive stored point of the poses of `slots` (None:
+        all) over the stored points of the poses of `among` (None: all), the point itself included when its pose is
+        counted: a neighbourhood.PointStatistics in ascending (slot, index) (octl_forest_point_stats: one kernel once
+        the block index of `among` exists; nothing of the map changes).  pose_of_slot maps slots to pose numbers (None:
+        slots are the pose numbers)."""
+        from octreelib_amd.leaf_stats import cov6_to_full
+        from octreelib_amd.neighbourhood import PointStatistics
+        from octreelib_amd.query import check_radius_args
+
+        r, _, _ = check_radius_args(radius, what="point_statistics")
+        self.ensure_built()
+        sel, n_sel, chosen = self._adjust_selection(slots)
+        asel, n_asel, _ = self._adjust_selection(among)
+        cap = min(int(self.n_ord), int(sum(self.slot_sizes[s] for s in chosen)))
+        rows = C.c_int64(0)
+        for _ in range(2):
+            slot = np.empty(cap, dtype=np.int32)
+            index = np.empty(cap, dtype=np.int32)
+            count = np.empty(cap, dtype=np.int64)
+            mean = np.empty((cap, 3), dtype=np.float64)
+            cov = np.empty((cap, 6), dtype=np.float64)
+            w = np.empty((cap, 3), dtype=np.float64) if eigen else None
+            v = np.empty((cap, 3, 3), dtype=np.float64) if eigen else None
+            self.ctx.check(self.lib.octl_forest_point_stats(self.handle, r, nat.ptr(sel), n_sel, nat.ptr(asel), n_asel,
+                                                            cap, C.byref(rows), nat.ptr(slot), nat.ptr(index),
+                                                            nat.ptr(count), nat.ptr(mean), nat.ptr(cov), nat.ptr(w),
+                                                            nat.ptr(v)))
+            if rows.value <= cap:
+                break
+            cap = int(rows.value)   # (the host's bound was short: once more with the size the library found)
+        else:
+            raise RuntimeError(f"point_statistics: {rows.value} rows do not fit the {cap} asked for")
+        m = int(rows.value)
+        order = np.lexsort((index[:m], slot[:m]))
+        slot, index = slot[:m][order], index[:m][order]
+        if pose_of_slot is not None and m:
+            slot = np.asarray(list(pose_of_slot), dtype=np.int32)[slot]
+        return PointStatistics(count[:m][order], mean[:m][order], cov6_to_full(cov[:m][order]),
+                               w[:m][order] if eigen else None, v[:m][order] if eigen else None, slot, index)
+
     def cell_count(self, points, cell, max_count=None, slots=None) -> np.ndarray:
         """How many stored points of the poses of `slots` (None: all) lie in the lattice cell of every query point,
         capped at max_count (None: uncapped): (n,) int32 as thinning.cell_count_np defines it (octl_forest_cell_count:

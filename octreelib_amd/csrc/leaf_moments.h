@@ -47,8 +47,8 @@ __device__ __forceinline__ void fold(Sums& acc, const Sums& p) {
   for (int k = 0; k < 9; ++k) acc.s[k] = acc.s[k] + p.s[k];
 }
 
-__device__ __forceinline__ void finish(const Sums& S, int64_t n, double p0x, double p0y, double p0z, double* mean,
-                                       double* cov) {
+__host__ __device__ __forceinline__ void finish(const Sums& S, int64_t n, double p0x, double p0y, double p0z,
+                                                double* mean, double* cov) {
   const double dn = (double)n;
   const double mx = S.s[0] / dn, my = S.s[1] / dn, mz = S.s[2] / dn;
   mean[0] = p0x + mx;

@@ -8,6 +8,8 @@
 //                                                the pose, pos = its row in the ordered arrays (xyz_ord, ord_idx).
 //
 // One definition, so that both kernels examine the same cubes in the same order and form the same d2 bits.
+// __host__ __device__, as cell_walk.h is: a stand-alone host program runs the very walk of the kernels over tables it
+// reads from a file (tests/host/moments_host.cpp).
 #pragma once
 #include "common.h"
 #include "forest.h"
@@ -44,7 +46,7 @@ int nn_tables(octl_forest* f, const char* what, int64_t n, const uint8_t* slot_s
 // at most 2^-53 (|A|) and 2^-53 (|U| + |q - c|), and the subtraction of the slack w rounds once more; all of it is below
 // 3 * 2^-53 (|q| + |c| + e), and w = 2^-50 (|q| + |c| + e) is 8 * 2^-53 of that.  g = max(A - w, U - w, 0) is then a
 // double that does not exceed |q - p| for any such p, hence (fl monotone, g representable) not |fl(q - p)| either.
-__device__ __forceinline__ double cube_gap(double q, double c, double e) {
+__host__ __device__ __forceinline__ double cube_gap(double q, double c, double e) {
   const double w = 0x1p-50 * ((fabs(q) + fabs(c)) + e);
   const double lo = (c - q) - w, hi = ((q - c) - e) - w;
   return fmax(fmax(lo, hi), 0.0);
@@ -52,28 +54,38 @@ __device__ __forceinline__ double cube_gap(double q, double c, double e) {
 
 // ... and of d2: squares, and sums of non-negative doubles, are monotone under rounding, so the formula of d2 applied
 // to the three gaps in the same order is a lower bound of the d2 the kernel forms for p, rounding included.
-__device__ __forceinline__ double cube_bound(double qx, double qy, double qz, double cx, double cy, double cz,
-                                             double e) {
+__host__ __device__ __forceinline__ double cube_bound(double qx, double qy, double qz, double cx, double cy,
+                                                      double cz, double e) {
   const double gx = cube_gap(qx, cx, e), gy = cube_gap(qy, cy, e), gz = cube_gap(qz, cz, e);
   return (gx * gx + gy * gy) + gz * gz;
 }
 
+// +inf, for the device and for a host build of the walk (tests/host/moments_host.cpp) alike
+__host__ __device__ __forceinline__ double nn_infinity() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __longlong_as_double(0x7ff0000000000000ll);
+#else
+  return __builtin_inf();
+#endif
+}
+
 // the child the query would be placed in (any value 0..7 for a query outside the cube: it only orders the visit)
-__device__ __forceinline__ int own_child(double qx, double qy, double qz, double cx, double cy, double cz, double e) {
+__host__ __device__ __forceinline__ int own_child(double qx, double qy, double qz, double cx, double cy, double cz,
+                                                  double e) {
   const double h = e / 2.0;
   return ((qx - cx) >= h ? 4 : 0) | ((qy - cy) >= h ? 2 : 0) | ((qz - cz) >= h ? 1 : 0);
 }
 
-__device__ __forceinline__ bool cand_less(double d, uint64_t id, double bd, uint64_t bid) {
+__host__ __device__ __forceinline__ bool cand_less(double d, uint64_t id, double bd, uint64_t bid) {
   return d < bd || (d == bd && id < bid);
 }
 
 // Every stored point of the index within r of q = (qx, qy, qz), offered to the sink (r2 = fl(r r), formed once on the
 // host).  A query that is not finite, and a forest without roots, offer nothing.
 template <class Sink>
-__device__ __forceinline__ void nearest_walk(const NNTables& T, double qx, double qy, double qz, double r, double r2,
-                                             Sink& sink) {
-  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+__host__ __device__ __forceinline__ void nearest_walk(const NNTables& T, double qx, double qy, double qz, double r,
+                                                      double r2, Sink& sink) {
+  const double INF = nn_infinity();
   const QueryTables& t = T.t;
   const bool finite = fabs(qx) < INF && fabs(qy) < INF && fabs(qz) < INF;  // (false for NaN)
   if (!(finite && t.V > 0)) return;

@@ -1037,6 +1037,37 @@ class HostMap:
         self._radius_cap(r, "radius_count")
         return radius_count_np(points, self.clouds(pose_numbers), r, max_count=max_count)
 
+    def neighbourhood_statistics(self, points, radius, *, pose_numbers=None, eigen=True) -> LeafStatistics:
+        from octreelib_amd.neighbourhood import neighbourhood_statistics_np
+
+        r, _, _ = check_radius_args(radius, what="neighbourhood_statistics")
+        self._radius_cap(r, "neighbourhood_statistics")
+        st = neighbourhood_statistics_np(points, self.clouds(pose_numbers), r, dtype=np.longdouble, eigen=eigen)
+        st.mean = st.mean.astype(np.float64)
+        st.covariance = st.covariance.astype(np.float64)
+        return st
+
+    def point_statistics(self, radius, *, pose_numbers=None, among=None, eigen=True):
+        """The self-query over the map as it stands: a neighbourhood.PointStatistics with one row per point of the
+        tested poses (pose_numbers, None: all) in the order the poses were inserted, index = the row of
+        clouds([pose]); moments in np.longdouble, returned as float64."""
+        from octreelib_amd.neighbourhood import point_statistics_np
+
+        r, _, _ = check_radius_args(radius, what="point_statistics")
+        self._radius_cap(r, "point_statistics")
+        counted = self.clouds(among)
+        have = {p for p, _ in counted}
+        parts = [point_statistics_np(counted, [t[0] if t[0] in have else t], r, dtype=np.longdouble, eigen=eigen)
+                 for t in self.clouds(pose_numbers)]
+        if not parts:
+            parts = [point_statistics_np(counted, [], r, dtype=np.longdouble, eigen=eigen)]
+        st = parts[0]
+        for f in ("count", "mean", "covariance", "pose", "index") + (("eigenvalues", "eigenvectors") if eigen else ()):
+            setattr(st, f, np.concatenate([getattr(p, f) for p in parts]))
+        st.mean = st.mean.astype(np.float64)
+        st.covariance = st.covariance.astype(np.float64)
+        return st
+
     def remove_sparse(self, radius, min_neighbours, *, pose_numbers=None, among=None):
         """The decision of remove_sparse over the map as it stands: [(pose number, keep)] for every tested pose
         (pose_numbers, None: all) in the order the poses were inserted, keep one bool per row of clouds([pose]).  These
