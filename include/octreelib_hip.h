@@ -195,7 +195,18 @@ typedef struct octl_build_info {
  * after octl_forest_extend_pose / octl_forest_set_scheme every point is placed again.  K < 0 means "never split" (the state right after insert_points).
  * max_depth guards the recursion the reference does not bound (<= 0: default 63).
  * On OCTL_E_DOMAIN / OCTL_E_DEPTH / OCTL_E_NOMEM / OCTL_E_HIP the forest keeps its points and
- * voxels but is left without a scheme (the next build starts from the top-level voxels).     */
+ * voxels but is left without a scheme (the next build starts from the top-level voxels).
+ * Streams: everything the build enqueues is ordered by the context's stream, as every call of the library is.  A
+ * build of the route a scan loop takes - one pose read in place (octl_forest_add_pose_adopt) into a fresh scheme,
+ * under the key geometry of the context's previous build - may put its first kernels (the partition of the cloud) on
+ * a second stream of the context, where they run NEXT TO octl_forest_ransac_all / octl_forest_apply_mask(_async) of
+ * the context's previous scan that are still in flight: those kernels read only the adopted cloud and write only
+ * scratch of the build.  Before the call returns the context's stream has been made to wait for them, on error
+ * returns too, so that on return nothing is in flight that the context's stream does not cover: octl_ctx_sync, a
+ * later octl_dev_upload_async into the cloud's buffer and octl_dev_free behave as they always did.  The build stays
+ * on the one stream whenever anything else was enqueued on the context since the forest's previous build, while the
+ * context is profiling, below OCTL_BUILD_AHEAD_MIN_POINTS points, and with OCTL_NO_BUILD_AHEAD=1; results, launches
+ * and host waits are the same either way.                                                              */
 int octl_forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
                       int32_t keep_scheme, int32_t max_depth, octl_build_info* info);
 
@@ -912,6 +923,9 @@ int octl_debug_launches(uint64_t* count);
  * build's totals, its tables sized from the context's previous build) that did the work / that the host had to
  * repeat the ordinary way (process-wide).  No reference counterpart: the reference has no device queue.        */
 int octl_debug_spec_finish(uint64_t* held, uint64_t* missed);
+/* Builds whose partition front ran on the context's ahead stream, next to the previous scan's RANSAC and mask
+ * (octl_forest_build: Streams; process-wide).  No reference counterpart: the reference has no device queue.   */
+int octl_debug_builds_ahead(uint64_t* count);
 
 /* Test hook: the communicator-independent half of octl_route_points for ANY number of ranks -
  * destination of every point (host cloud in), per-destination counts [n_ranks], and the packed
@@ -962,7 +976,8 @@ int octl_device_identity(octl_ctx* ctx, char pci_bus_id[32], uint8_t uuid[16], i
 /* Diagnostic switches of a context (tests and A/B runs compare code paths: "NO_BUCKET_BUILD", "BUCKET_POINTS",
  * "SYNC_GEOM", "NO_GEOM_HINT", "GEOM_MARGIN", "NO_EXACT_DIGITS", "NO_FAST_ORDER", "NO_BUCKET_HISTORY", "NO_CUBE_FAST",
  * "NO_CUBE_PREFIX", "CUBE_PREFIX_MIN", "NO_INCREMENTAL", "ROUTE_SELF_SENDRECV", "TRACE_BUILD", "SCAN",
- * "NO_FUSED_TABLES", "NO_SPIN_WAIT", "NO_SPEC_FINISH", "RANSAC_WAVES", "NO_RANSAC_PRESCREEN"; an "OCTL_" prefix is
+ * "NO_FUSED_TABLES", "NO_SPIN_WAIT", "NO_SPEC_FINISH", "RANSAC_WAVES", "NO_RANSAC_PRESCREEN", "NO_BUILD_AHEAD",
+ * "BUILD_AHEAD_MIN_POINTS" (the one switch whose unset value is not 0: -1 = the library's bound); an "OCTL_" prefix is
  * accepted; the table in INTEGRATION.md says what each one does).  octl_ctx_create reads OCTL_<NAME> from the
  * environment ONCE, as a number: OCTL_X=0 is OFF (rounds 1-4 tested only for the variable's presence), a value that
  * is not a number is 1, and setting the environment after the context exists has no effect - this call changes a

@@ -169,6 +169,7 @@ SIGNATURES = {
     "octl_debug_host_syncs": (C.c_int, [C.POINTER(C.c_uint64)]),
     "octl_debug_launches": (C.c_int, [C.POINTER(C.c_uint64)]),
     "octl_debug_spec_finish": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "octl_debug_builds_ahead": (C.c_int, [C.POINTER(C.c_uint64)]),
     "octl_debug_fail_alloc": (C.c_int, [_i64, _pi64]),
     "octl_debug_set_option": (C.c_int, [_p, C.c_char_p, _i64]),
     "octl_debug_key_geometry": (C.c_int, [_p, C.c_uint64, _i64, C.c_uint32, _i32, _p, _p, _p, _p, _p]),
@@ -276,7 +277,9 @@ class Context:
 
     def reset_options(self):
         for name in list(self.__dict__.get("_options_touched", ())):
-            self.lib.octl_debug_set_option(self.handle, name.encode(), 0)
+            # (0 is the shipped behaviour of every switch but this one, where 0 means "every size")
+            shipped = -1 if name.removeprefix("OCTL_") == "BUILD_AHEAD_MIN_POINTS" else 0
+            self.lib.octl_debug_set_option(self.handle, name.encode(), shipped)
         self.__dict__["_options_touched"] = set()
 
     def set_profiling(self, enabled: bool):

@@ -151,6 +151,10 @@ int octl_forest_create(octl_ctx* ctx, int mode, const double corner[3], double e
 void octl_forest_destroy(octl_forest* f) {
   if (!f) return;
   forest_forget_pending(f);
+  if (f->ctx->ahead_forest == f) {  // (a forest at the same address later is another forest: its build is serial)
+    f->ctx->ahead_forest = nullptr;
+    f->ctx->ahead_mark_valid = f->ctx->ahead_mark_pending = false;
+  }
   (void)hipSetDevice(f->ctx->device);
   (void)hipStreamSynchronize(f->ctx->stream);
   nodes_free(f->ctx, f->nodes[0]);

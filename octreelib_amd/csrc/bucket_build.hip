@@ -15,8 +15,10 @@
 //                                  consecutive voxels: one stable pass on a 12-bit digit (LDS
 //                                  histograms, wave64 ballot ranks) for up to 4096 buckets - the only
 //                                  scatter of coordinates - and a second one on the next 12 bits for
-//                                  clouds that need more buckets (> 10 M points);
-//   k_bucket_build                 one workgroup per bucket (<= 4096 points, a few voxels; larger buckets in
+//                                  clouds that need more buckets (> 10 M points); in a scan loop the single
+//                                  pass of scan i+1 runs on the context's AHEAD stream, next to the RANSAC and
+//                                  the mask of scan i on the context's stream (partition());
+//   k_bucket_build                one workgroup per bucket (<= 4096 points, a few voxels; larger buckets in
 //                                  chunks of whole voxels): level by level the undecided points add
 //                                  themselves to an LDS histogram over (node ordinal, child digit), bins
 //                                  above K become the nodes of the next level (a node splits while its
@@ -2441,9 +2443,12 @@ uint32_t supertiles(octl_ctx* ctx, int64_t items, int wgs, int* tiles) {
 }
 // f->bk_table: [supertile][digit] table of *elems words | the same digit-major (scanned: the buckets' starts) | tail_words
 // of the caller's (the bucket bounds of two passes, the prefix partition's flag)
-int part_table_reserve(octl_forest* f, size_t cells, size_t tail_words, size_t* elems) {
+size_t part_table_bytes(size_t cells, size_t tail_words, size_t* elems) {
   *elems = (cells + 1 + 15) & ~(size_t)15;
-  return devbuf_reserve(f->ctx, f->bk_table, (2 * *elems + tail_words + 16) * 4);
+  return (2 * *elems + tail_words + 16) * 4;
+}
+int part_table_reserve(octl_forest* f, size_t cells, size_t tail_words, size_t* elems) {
+  return devbuf_reserve(f->ctx, f->bk_table, part_table_bytes(cells, tail_words, elems));
 }
 // the partition table's transposes + scan as ONE launch (k_table_scan), the hint's validation inside it
 bool tables_fused(const octl_ctx* ctx, uint32_t nst) { return !ctx->opt.no_fused_tables && nst <= TS_MAX_ROWS; }
@@ -2465,6 +2470,9 @@ struct PartPass {
   size_t tab_elems = 0;             // part_table_reserve
   bool own_scan = false;            // the scatter kernel's workgroups scan the table themselves (ScatterOwnScan)
   PartRec* out = nullptr;
+  // the pass goes to the context's AHEAD stream (partition() decides; fused tables only): its look-back chain takes
+  // the ahead stream's status words
+  bool ahead = false;
   const char *t_hist = nullptr, *t_scan = nullptr, *t_scatter = nullptr;  // KTimer labels; no t_scan: inside t_hist
 };
 
@@ -2480,8 +2488,12 @@ int partition_scan(octl_forest* f, const PartPass& p, bool fused) {
     const unsigned g = (p.nd + TS_COLS - 1) / TS_COLS;
     uint64_t* status = nullptr;
     uint32_t epoch = 0;
-    OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
-    OCTL_LAUNCH(k_table_scan, dim3(g), dim3(TS_THREADS), 0, ctx->stream, table, p.nst, p.nd, table_dm, status, epoch,
+    // (a chain on the ahead stream must not read the status words of the chains on the context's stream - the mask's
+    //  and k_block_prepare's may be in flight beside it: it has words and epochs of its own)
+    if (p.ahead) OCTL_TRY(octl_ahead_status_acquire(ctx, g, &status, &epoch));
+    else OCTL_TRY(octl_scan_status_acquire(ctx, g, &status, &epoch));
+    OCTL_LAUNCH(k_table_scan, dim3(g), dim3(TS_THREADS), 0, p.ahead ? ctx->ahead_stream : ctx->stream, table, p.nst,
+                       p.nd, table_dm, status, epoch,
                        p.validate, p.ask ? (const int32_t*)f->bbox_dev.as<int32_t>() : (const int32_t*)nullptr,
                        p.ask ? *p.ask : GeomAsk{0, 0, 0, 0}, p.lp, p.gdev);
     HIP_TRY(ctx, hipGetLastError());
@@ -2496,7 +2508,7 @@ int partition_scan(octl_forest* f, const PartPass& p, bool fused) {
 // *bstart / *bstride: the first record of digit d in p.out is (*bstart)[d * *bstride]
 int partition_pass(octl_forest* f, const PartPass& p, const uint32_t** bstart, uint32_t* bstride) {
   octl_ctx* ctx = f->ctx;
-  hipStream_t st = ctx->stream;
+  hipStream_t st = p.ahead ? ctx->ahead_stream : ctx->stream;
   const uint32_t nst = p.nst, nd = p.nd;
   const bool fused = tables_fused(ctx, nst);
   uint32_t *table = f->bk_table.as<uint32_t>(), *table_dm = table + p.tab_elems;
@@ -2563,7 +2575,7 @@ enum BuildVerdict { BV_GO, BV_GENERAL, BV_AGAIN_ASYNC, BV_AGAIN_HOST };
 struct BucketBuild {
   octl_forest* f;
   octl_ctx* ctx;
-  hipStream_t st;        // ctx->stream
+  hipStream_t st;        // ctx->stream: everything but the first partition pass of an attempt that runs ahead (partition())
   uint32_t* small;       // the scalar block
   // the plan (plan_geometry)
   GeomAsk ask;           // want, n_alive, target, margin
@@ -2625,6 +2637,33 @@ int geom_read(octl_ctx* ctx, GeomDev* g, BuildVerdict* v) {
   return OCTL_OK;
 }
 
+// buckets: runs of consecutive voxel keys, sized for ~2500 points on average (~1250 in a small cloud)
+// (OCTL_BUCKET_POINTS: tests force many small buckets - and with them the two-pass partition - on small clouds)
+// (a small cloud fills few workgroups and its kernels are chains of latencies, not bytes: half the bucket shortens
+//  every chain - 100 k points 0.165 -> 0.157 ms, 30 k 0.126 -> 0.117; from 1 M points on the larger bucket wins)
+uint64_t bucket_want(const octl_ctx* ctx, int64_t n_alive, uint64_t* target) {
+  *target = ctx->opt.bucket_points > 0 ? (uint64_t)ctx->opt.bucket_points : (n_alive <= 400000 ? 1280 : 2560);
+  uint64_t want = 1;
+  while (want < ((uint64_t)PT_BINS << PT_BITS) && want * *target < (uint64_t)n_alive) want <<= 1;
+  return want;
+}
+// A single pass of nd digits over nst supertiles of f's store that may go to the ahead stream: every stored point alive
+// (no alive flags are read: the previous mask may still be filling them), its table scanned by k_table_scan or the
+// scatter kernel itself with a look-back chain the ahead stream's status words hold, and no buffer it writes to grow.
+bool front_pass_fits(const octl_forest* f, uint32_t nd, uint32_t nst) {
+  size_t elems = 0;
+  return f->n_alive == f->n_store && tables_fused(f->ctx, nst) &&
+         (int64_t)((nd + TS_COLS - 1) / TS_COLS) <= OCTL_AHEAD_TILES &&
+         f->part_xyz[0].cap >= (size_t)f->n_alive * sizeof(PartRec) &&
+         f->bk_table.cap >= part_table_bytes((size_t)nd * nst, 0, &elems);
+}
+// does the first pass of this attempt go to the ahead stream (forest_build has opened a front there)?  Exactly the
+// case forest_bucket_front_fits promised, judged on the attempt's own plan.
+bool front_goes_ahead(const BucketBuild& b, const BucketBuildArgs& a) {
+  return b.ctx->ahead_open && b.hinted && b.async_geom && !b.two_pass && !a.scheme_dev &&
+         front_pass_fits(b.f, b.nd_a, b.nst_a);
+}
+
 // How many buckets, whose geometry, under which hint, in which passes.  Host arithmetic - and, for a cloud taken in
 // place without a usable hint, the box pass; for a host-formed geometry the wait for the box.
 int plan_geometry(BucketBuild& b, bool force_sync, BuildVerdict* v) {
@@ -2632,14 +2671,8 @@ int plan_geometry(BucketBuild& b, bool force_sync, BuildVerdict* v) {
   octl_ctx* ctx = b.ctx;
   const int64_t n_alive = f->n_alive;
   *v = BV_GO;
-  // buckets: runs of consecutive voxel keys, sized for ~2500 points on average (~1250 in a small cloud)
-  // (OCTL_BUCKET_POINTS: tests force many small buckets - and with them the two-pass partition - on small clouds)
-  // (a small cloud fills few workgroups and its kernels are chains of latencies, not bytes: half the bucket shortens
-  //  every chain - 100 k points 0.165 -> 0.157 ms, 30 k 0.126 -> 0.117; from 1 M points on the larger bucket wins)
-  const uint64_t target = ctx->opt.bucket_points > 0 ? (uint64_t)ctx->opt.bucket_points
-                                                     : (n_alive <= 400000 ? 1280 : 2560);
-  uint64_t want = 1;
-  while (want < ((uint64_t)PT_BINS << PT_BITS) && want * target < (uint64_t)n_alive) want <<= 1;
+  uint64_t target = 0;
+  const uint64_t want = bucket_want(ctx, n_alive, &target);
   // One partition pass (want <= 4096 buckets): the key geometry is formed on the device (k_bucket_geom) and
   // the host does not wait for the bounding box; all 4096 buckets exist then, the ones behind the last
   // voxel key are empty.  (OCTL_SYNC_GEOM: tests run the host-side form on small clouds too.)
@@ -2744,6 +2777,13 @@ int partition(BucketBuild& b, const BucketBuildArgs& a) {
   octl_forest* f = b.f;
   octl_ctx* ctx = b.ctx;
   const int64_t n_alive = f->n_alive;
+  // A front that forest_build opened on the ahead stream stays there for this pass only in the case it was opened
+  // for; anything else joins the streams first and is, from here on, the serial build.  (Nothing below grows a buffer
+  // the pass writes when it stays ahead; the buffers behind the join may grow - that waits for the context's stream
+  // and touches nothing of the front's.)
+  const bool ahead = front_goes_ahead(b, a);
+  if (!ahead) octl_ahead_join(ctx);
+  hipStream_t front = ahead ? ctx->ahead_stream : b.st;
   OCTL_TRY(devbuf_reserve(ctx, f->part_xyz[0], (size_t)n_alive * sizeof(PartRec)));
   if (b.two_pass) OCTL_TRY(devbuf_reserve(ctx, f->part_xyz[1], (size_t)n_alive * sizeof(PartRec)));
   // (behind the two tables: the bucket bounds of two passes)
@@ -2762,7 +2802,7 @@ int partition(BucketBuild& b, const BucketBuildArgs& a) {
   if (b.async_geom) {
     if (b.hinted) {
       // (normally in place already: k_build_begin copied it with the scalar block)
-      if (!ctx->geom_hint_staged) OCTL_LAUNCH(k_geom_set, dim3(1), dim3(64), 0, b.st, b.hint, b.gdev);
+      if (!ctx->geom_hint_staged) OCTL_LAUNCH(k_geom_set, dim3(1), dim3(64), 0, front, b.hint, b.gdev);
     } else {
       OCTL_LAUNCH(k_bucket_geom, dim3(1), dim3(64), 0, b.st, (const int32_t*)f->bbox_dev.as<int32_t>(), b.ask, b.lp,
                          b.gdev);
@@ -2791,7 +2831,14 @@ int partition(BucketBuild& b, const BucketBuildArgs& a) {
   p.own_scan = tables_fused(ctx, b.nst_a) && !b.two_pass && !b.hinted2 && b.nd_a <= 256u && b.nst_a <= PS_OWN_MAX_ROWS;
   p.out = f->part_xyz[0].as<PartRec>();
   p.t_hist = "part_hist", p.t_scan = "part_scan", p.t_scatter = "part_scatter";
+  p.ahead = ahead;
   OCTL_TRY(partition_pass(f, p, &b.bstart, &b.bstride));
+  if (ahead) {
+    // the join: k_bucket_build and everything behind it on the context's stream wait for the front
+    octl_ahead_join(ctx);
+    g_octl_builds_ahead.fetch_add(1, std::memory_order_relaxed);
+  }
+  p.ahead = false;
   b.recs = p.out;
   if (!b.two_pass) return OCTL_OK;
   // second (more significant) digit over the records of the first pass, then the bucket bounds
@@ -3084,6 +3131,13 @@ int finish_and_commit(BucketBuild& b, const BucketBuildArgs& a, NodeTable& nt, b
 int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, BucketBuildResult* r) {
   octl_ctx* ctx = f->ctx;
   r->done = 0;
+  // An open front (forest_build put k_build_begin on the ahead stream) stays open up to partition(), which runs the
+  // first pass there and joins; every other way out of this function joins here - AheadJoin's destructor - so that
+  // whatever runs next on the context's stream, the general route or an error's clean-up, is behind the front.
+  struct AheadJoin {
+    octl_ctx* ctx;
+    ~AheadJoin() { octl_ahead_join(ctx); }
+  } ahead_join{ctx};
   // (OCTL_NO_BUCKET_BUILD: tests compare this path with the level-synchronous one)
   if (f->n_alive <= 0 || !f->bbox_dev.p || ctx->opt.no_bucket_build) return OCTL_OK;
   // a single cube (bare Octree / OctreeManager) is ONE bucket: beyond what the oversize launch takes it is the
@@ -3097,6 +3151,7 @@ int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt,
     BucketBuild b{f, ctx, ctx->stream, ctx->small.as<uint32_t>()};  // (the rest: zero)
     BuildVerdict v = BV_GO;
     OCTL_TRY(plan_geometry(b, force_sync, &v));
+    if (!b.hinted) octl_ahead_join(ctx);  // (plan_geometry enqueued nothing when it found the hint usable)
     if (v == BV_AGAIN_HOST) {  // (a two-pass hint whose box asks for one pass)
       force_sync = true;
       continue;
@@ -3127,6 +3182,21 @@ int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt,
     return finish_and_commit(b, a, nt, overfull, r);
   }
   return octl_set_error(ctx, OCTL_E_STATE, "bucket build: the geometry retries do not terminate");
+}
+
+bool forest_bucket_front_fits(const octl_forest* f) {
+  const octl_ctx* ctx = f->ctx;
+  if (f->n_alive <= 0 || f->n_alive != f->n_store || !f->bbox_dev.p || !f->bbox_pending || ctx->opt.no_bucket_build ||
+      (f->mode == 1 && f->n_alive > 65535))
+    return false;
+  // (plan_geometry's decisions for a first attempt, force_sync = false)
+  uint64_t target = 0;
+  const uint64_t want = bucket_want(ctx, f->n_alive, &target);
+  if (ctx->geom_sparse || want > (uint64_t)PT_BINS || ctx->opt.sync_geom) return false;   // async_geom
+  GeomDev hint;
+  if (!hint_load(ctx, f, want, &hint) || ctx->geom_hint_two_pass) return false;           // hinted
+  int tiles = 0;
+  return front_pass_fits(f, (uint32_t)geom_bucket_cap(want), supertiles(f->ctx, f->n_store, OCTL_PT_WGS, &tiles));
 }
 
 // A big single cube (bare Octree / OctreeManager with millions of points) partitioned ONCE by the child digits of

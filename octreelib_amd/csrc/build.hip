@@ -1435,8 +1435,21 @@ int build_validate(octl_forest* f, const BuildRequest& rq, const uint8_t* scheme
 // and, when a pose subset drives the scheme, its mask (rq.scheme_dev)
 int build_begin(octl_forest* f, BuildRequest& rq, const uint8_t* scheme_mask) {
   octl_ctx* ctx = f->ctx;
-  hipStream_t st = ctx->stream;
   const int n_poses = rq.n_poses;
+  // The partition front of this build - the launch below, the pose offsets' copy and the first pass of the bucket
+  // build's partition - on the context's AHEAD stream, next to the RANSAC and the mask of the context's previous scan
+  // that are still in flight on its stream, when all of this holds: the route is the one the headline
+  // takes (one pose read in place whose box is still to be found, a fresh count-driven scheme from it, a single pass
+  // under the context's hint: forest_bucket_front_fits); nothing the front writes has to grow; the context is not
+  // profiling (KTimer records on the context's stream); and since the end of this forest's previous build the library
+  // has enqueued nothing on the context but work that touches none of the front's memory (octl_ahead_untouched).
+  // Otherwise: the same launches in the same order on the context's stream.
+  if (!ctx->opt.no_build_ahead && !ctx->profiling && f->store_borrowed && f->bbox_pending && n_poses == 1 &&
+      !rq.keep_scheme && !rq.planar && rq.all_scheme && !f->built && f->vkeys.empty() && !f->vkeys_stale &&
+      f->n_store >= octl_ahead_min_points(ctx) && f->pose_off_dev.cap >= (size_t)(n_poses + 1) * 8 &&
+      octl_ahead_untouched(ctx, f) && forest_bucket_front_fits(f))
+    (void)octl_ahead_open(ctx, f->xyz.p, (size_t)f->n_store * 24);
+  hipStream_t st = octl_front_stream(ctx);
   // ---- reset the scalar block -------------------------------------------------------------
   {
     uint32_t init[32];
@@ -1486,7 +1499,7 @@ int build_begin(octl_forest* f, BuildRequest& rq, const uint8_t* scheme_mask) {
   }
   if (f->pose_off_uploaded != f->pose_off) {  // (the same offsets step after step: nothing to upload)
     if (fits)
-      OCTL_TRY(octl_copy_from_pinned(ctx, f->pose_off_dev.p, src_off, off_bytes));
+      OCTL_TRY(octl_copy_from_pinned(ctx, f->pose_off_dev.p, src_off, off_bytes, st));   // (st: with the front)
     else
       HIP_TRY(ctx, hipMemcpyAsync(f->pose_off_dev.p, src_off, off_bytes, hipMemcpyHostToDevice, st));
     f->pose_off_uploaded = f->pose_off;
@@ -1513,6 +1526,7 @@ int build_try_incremental(octl_forest* f, const BuildRequest& rq, BuildTrace& tr
   *done = 0;
   const bool unsplit_again = !rq.keep_scheme && !rq.planar && rq.K < 0 && f->built && f->n_internal == 0;
   if (!rq.keep_scheme && !unsplit_again) return OCTL_OK;
+  octl_ahead_join(f->ctx);  // (never open here: a front is opened for a fresh scheme only)
   OCTL_TRY(forest_insert_incremental(f, done, info));
   trace.mark("incremental insertion");
   if (*done) {
@@ -1645,6 +1659,7 @@ int build_bucket_route(octl_forest* f, const BuildRequest& rq, BuildTrace& trace
   const bool over_old = f->built && !f->ctx->opt.no_bucket_history;
   // (not a planar build: its statistic is evaluated level by level, by the level loop of the general route)
   if (rq.keep_scheme || rq.planar || !(fresh0 || over_old) || rq.n_alive <= 0) return OCTL_OK;
+  // (a front that build_begin opened on the ahead stream is joined inside forest_bucket_build, on every way out)
   NodeTable& bt = f->nodes[f->cur ^ 1];
   BucketBuildArgs ba{rq.K, rq.scheme_dev, rq.cur_epoch, rq.max_depth};
   const int64_t old_internal0 = f->built ? f->n_internal : 0;
@@ -2126,6 +2141,27 @@ int build_general_route(octl_forest* f, const BuildRequest& rq, BuildTrace& trac
   return OCTL_OK;
 }
 
+// the steps of a build behind its validation (forest_build)
+int forest_build_steps(octl_forest* f, BuildRequest& rq, const uint8_t* scheme_mask, BuildTrace& trace,
+                       octl_build_info* info) {
+  const int32_t keep_scheme = rq.keep_scheme;
+  OCTL_TRY(build_begin(f, rq, scheme_mask));
+  int placed = 0;
+  OCTL_TRY(build_try_incremental(f, rq, trace, info, &placed));
+  if (placed) return OCTL_OK;
+  rq.n_alive = f->n_alive;
+  rq.cur_epoch = f->epoch + (keep_scheme ? 0 : 1);
+
+  BuildOutcome out;
+  bool bucket_built = false;
+  OCTL_TRY(build_bucket_route(f, rq, trace, out, &bucket_built));
+  octl_ahead_join(f->ctx);  // (joined already wherever the bucket route was taken)
+  if (!bucket_built) OCTL_TRY(build_general_route(f, rq, trace, out));
+  if (!out.blocks_made) OCTL_TRY(build_block_table(f, rq.n_alive, &out.n_blocks));
+  if (!bucket_built) trace.mark("blocks + final sync");  // (the bucket route's marks end with its level loop)
+  return build_commit(f, rq, out, info);
+}
+
 }  // namespace
 
 int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t n_mask,
@@ -2149,18 +2185,15 @@ int forest_build(octl_forest* f, int64_t K, const uint8_t* scheme_mask, int32_t 
   BuildTrace trace;
   trace.on = ctx->opt.trace_build != 0;
 
-  OCTL_TRY(build_begin(f, rq, scheme_mask));
-  int placed = 0;
-  OCTL_TRY(build_try_incremental(f, rq, trace, info, &placed));
-  if (placed) return OCTL_OK;
-  rq.n_alive = f->n_alive;
-  rq.cur_epoch = f->epoch + (keep_scheme ? 0 : 1);
-
-  BuildOutcome out;
-  bool bucket_built = false;
-  OCTL_TRY(build_bucket_route(f, rq, trace, out, &bucket_built));
-  if (!bucket_built) OCTL_TRY(build_general_route(f, rq, trace, out));
-  if (!out.blocks_made) OCTL_TRY(build_block_table(f, rq.n_alive, &out.n_blocks));
-  if (!bucket_built) trace.mark("blocks + final sync");  // (the bucket route's marks end with its level loop)
-  return build_commit(f, rq, out, info);
+  // The end of the build, whichever way it ends: an open front is joined into the context's stream (so that a later
+  // event on it, octl_ctx_sync, the gate of an upload and octl_dev_free cover everything the library has in flight),
+  // and a build that succeeded leaves the "front scratch free" event for the next one to run ahead of.
+  struct BuildEnd {
+    octl_forest* f;
+    bool ok = false;
+    ~BuildEnd() { octl_ahead_build_end(f->ctx, f, ok, f->n_store); }
+  } build_end{f};
+  const int rc = forest_build_steps(f, rq, scheme_mask, trace, info);
+  build_end.ok = rc == OCTL_OK;
+  return rc;
 }

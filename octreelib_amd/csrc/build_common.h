@@ -57,6 +57,12 @@ struct BucketBuildResult {
   BucketBuildGeom geom;
 };
 int forest_bucket_build(octl_forest* f, const BucketBuildArgs& a, NodeTable& nt, BucketBuildResult* r);
+// Will the first attempt of forest_bucket_build(f) be ONE partition pass under the context's hint, over a cloud taken in
+// place with every point alive, with its tables scanned by k_table_scan / the scatter kernel itself, and without
+// growing a buffer that pass writes (part_xyz[0], bk_table)?  Host arithmetic, no side effect: what forest_build asks
+// before it puts the front on the ahead stream.  (A wrong "yes" costs nothing but the overlap: partition() joins
+// the streams in front of whatever it did not expect.)
+bool forest_bucket_front_fits(const octl_forest* f);
 
 // bucket_build.hip: one stable partition of a single cube's store by the child digits of its first pm levels
 // (records of 32 bytes: x, y, z f64 | six digits << 1 | bad | store index + scheme bit).  The layout as the readers

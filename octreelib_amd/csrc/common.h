@@ -30,6 +30,11 @@ static inline hipError_t octl_counted_event_sync(hipEvent_t e) {
 // ... and every kernel launch and asynchronous fill (a fill is a kernel of the runtime's): octl_debug_launches -
 // launches per step is the other figure a small scan lives by
 extern std::atomic<uint64_t> g_octl_launches;
+// ... and everything the library puts on a stream - launches, fills and copies (not part of any reported figure): what
+// a context compares its own tally of harmless work against before a build runs ahead (octl_ctx::ahead_*)
+extern std::atomic<uint64_t> g_octl_enqueues;
+// builds whose partition front ran on the context's ahead stream (octl_debug_builds_ahead)
+extern std::atomic<uint64_t> g_octl_builds_ahead;
 // speculative launches of k_bucket_finish that did the work / that the host had to repeat (octl_debug_spec_finish)
 extern std::atomic<uint64_t> g_octl_spec_held, g_octl_spec_missed;
 // (the project's own launch macro around the PUBLIC hipLaunchKernelGGL - not a redefinition of the runtime's macro
@@ -37,9 +42,13 @@ extern std::atomic<uint64_t> g_octl_spec_held, g_octl_spec_missed;
 #define OCTL_LAUNCH(...)                                                      \
   do {                                                                        \
     g_octl_launches.fetch_add(1, std::memory_order_relaxed);                  \
+    g_octl_enqueues.fetch_add(1, std::memory_order_relaxed);                  \
     hipLaunchKernelGGL(__VA_ARGS__);                                          \
   } while (0)
-#define hipMemsetAsync(...) (g_octl_launches.fetch_add(1, std::memory_order_relaxed), hipMemsetAsync(__VA_ARGS__))
+#define hipMemsetAsync(...)                                                                                      \
+  (g_octl_launches.fetch_add(1, std::memory_order_relaxed), g_octl_enqueues.fetch_add(1, std::memory_order_relaxed), \
+   hipMemsetAsync(__VA_ARGS__))
+#define hipMemcpyAsync(...) (g_octl_enqueues.fetch_add(1, std::memory_order_relaxed), hipMemcpyAsync(__VA_ARGS__))
 
 // Compile-time experiment switches that change RESULTS (ablations, duplicated work) or add instrumentation never
 // belong in a shipped library: they only compile when the variant build script defines OCTL_EXPERIMENTS
@@ -95,6 +104,9 @@ struct OctlOptions {
   int64_t geom_margin = 0;         // OCTL_GEOM_MARGIN: voxels of slack around the true box in a single-pass / hinted key geometry (0: one voxel; negative: none)
   int64_t no_ransac_prescreen = 0; // OCTL_NO_RANSAC_PRESCREEN: every hypothesis of a leaf through the exact plane fit (no approximate prescreen)
   int64_t no_spec_finish = 0;      // OCTL_NO_SPEC_FINISH: k_bucket_finish only behind the host's look at the totals (A/B)
+  int64_t no_build_ahead = 0;      // OCTL_NO_BUILD_AHEAD: the partition front of a build never on the ahead stream (A/B)
+  // OCTL_BUILD_AHEAD_MIN_POINTS: points from which a build may run ahead (unset: OCTL_AHEAD_MIN_POINTS; 0: every size)
+  int64_t build_ahead_min_points = -1;
 };
 // name (without the OCTL_ prefix or with it) -> field; nullptr when there is no such switch
 int64_t* octl_option_field(OctlOptions& o, const char* name);
@@ -131,6 +143,26 @@ struct octl_ctx {
   // larger blocks of a split launch, next to the one-wave instance.
   hipStream_t self_stream = nullptr;
   hipEvent_t self_gate = nullptr, self_done = nullptr;
+  // The context's AHEAD stream (octl_ctx_ahead_stream): the partition front of a build - k_build_begin,
+  // k_part_hist<true,*>, k_table_scan, k_part_scatter, the pose offsets' copy - next to the RANSAC and the mask of the
+  // context's PREVIOUS scan, which are still in flight on the context's stream.
+  //   ahead_free   recorded on the context's stream behind a build's last launch (by the first allow-listed function
+  //                that follows it, in front of its own work): the front's scratch is free;
+  //                the ahead stream waits for it (and for the uploads into the cloud) and for nothing else
+  //   ahead_done   recorded behind the front; the context's stream waits for it in front of k_bucket_build (the JOIN,
+  //                octl_ahead_join - on every path out of forest_build once ahead_open is set)
+  // A build runs ahead only when, since ahead_free, the library enqueued nothing on this context but work that
+  // touches none of the front's memory (AheadAllow): g_octl_enqueues == ahead_mark + ahead_allowed.
+  hipStream_t ahead_stream = nullptr;
+  hipEvent_t ahead_free = nullptr, ahead_done = nullptr;
+  DevBuf ahead_status;               // look-back status words of the front's k_table_scan (OCTL_AHEAD_TILES), with
+  uint32_t ahead_epoch = 0;          // an epoch counter of their own: the context's belong to chains on its stream
+  int ahead_allow_depth = 0;         // AheadAllow scopes that are open (only the outermost one counts)
+  bool ahead_open = false;           // a front is on the ahead stream and the context's stream has not joined it yet
+  bool ahead_mark_pending = false;   // a build of ahead_forest succeeded; ahead_free is still to be recorded (octl_ahead_arm)
+  bool ahead_mark_valid = false;     // ahead_free stands behind that build, with nothing but allow-listed work behind it
+  const struct octl_forest* ahead_forest = nullptr;
+  uint64_t ahead_mark = 0, ahead_allowed = 0;
   struct Upload { const char* dst; size_t bytes; hipEvent_t done; };
   std::vector<Upload> uploads;  // copies that may still be in flight, each with the event recorded behind it
   // device blocks handed back by destroyed forests, kept for the next one: a fresh Grid per scan
@@ -208,17 +240,24 @@ static_assert(MIRROR_COPY_WORDS <= MIRROR_BBOX_WORD && MIRROR_BBOX_WORD + 8 <= M
               MIRROR_RS_VIOLATION < MIRROR_MASK_TOTALS &&
               MIRROR_MASK_TOTALS + 2 <= MIRROR_FLAG_BUILD && MIRROR_FLAG_MASK1 < 1024, "mirror layout");
 // Words of the context's scalar block ctx->small (4 KiB of device uint32; the pinned mirror above has the same size).
-// Words [0, SM_BUILD_WORDS) belong to the build: forest_build's first kernel (k_build_begin) resets them.  A word with
-// more than one name has owners that never hold a live value in it at the same time:
-//  - 28..31: the bucket build (SM_BK_MISSING, SM_CK_COUNT), the incremental insertion (SM_INC_*) and
+// Who may write what, now that the partition front of a build can run on the ahead stream NEXT TO the RANSAC and the
+// apply_mask of the context's previous scan:
+//  - the FRONT's words: [0, SM_BUILD_WORDS), which forest_build's first kernel (k_build_begin) resets, and the key
+//    geometry SM_GEOM.. (staged by k_build_begin, validated by k_table_scan / k_part_scatter).  Work that may be in
+//    flight beside a front - ransac_launch, apply_mask, the hypothesis table's upload (the functions that hold an
+//    AheadAllow) - owns NO word in these ranges: SM_MASK_TOTAL lies behind them, ransac_launch uses none at all.
+//  - every other name in the front's ranges belongs to a build itself or to an operation that is not on that list;
+//    such an operation makes the context's next build serial (octl_ctx::ahead_mark), so it is never in flight beside
+//    a front.  Among them a word with more than one name has owners that never hold a live value at the same time:
+//    28..31: the bucket build (SM_BK_MISSING, SM_CK_COUNT), the incremental insertion (SM_INC_*) and
 //    octl_forest_slot_counts (SM_SLOT_COUNTS).  forest_build tries the incremental insertion first and falls through
 //    to the bucket build only for K < 0 over a scheme without internal nodes: k_inc_place then never counts SM_INC_BAD
 //    (it counts only in cubes that are split), so word 29 still holds the zero SM_CK_COUNT starts from, and the bucket
 //    build zeroes word 28 itself before k_old_voxels_missing counts into it.  build.hip's prefix partition counts
 //    into SM_BK_MISSING only on a forest that was never built, which the incremental insertion leaves alone.
 //    octl_forest_slot_counts zeroes its four words and reads them back before it returns: never inside a build.
-//  - 64..: the key geometry of the bucket build (SM_GEOM) and the RANSAC slot histogram (SM_SLOT_HIST): a build
-//    and the reference order of a RANSAC pass are never in flight at the same time.
+//  - SM_SLOT_HIST (the reference order of a RANSAC pass over several poses) has words of its own behind SM_GEOM: it
+//    shared them with the geometry while a build and a RANSAC pass could not overlap.
 enum {
   SM_ERR = 0,           // domain error flag
   SM_BBOX = 4,          // 6 x int32: min xyz, max xyz
@@ -230,7 +269,6 @@ enum {
   SM_BK_TICKET = 17,    // bucket build: workgroups of k_bucket_scan_totals that have finished (the last one forms the totals)
   SM_BK_OVERFULL = 18,  // bucket build: buckets with more than 4096 points (they are built in chunks of whole voxels)
   SM_SLOT_VOXELS = 21,  // octl_forest_get_slot_voxels: scan total = voxels in which the pose has points
-  SM_MASK_TOTAL = 22,   // apply_mask without the fused kernel: grand total of its scan
   SM_BK_NOORDER = 23,   // bucket build: some bucket has too many nodes / blocks for k_bucket_finish's own block order
   SM_DEBUG_TOTAL = 24,  // octl_debug_exclusive_scan: scan total
   SM_BK_FLAGS = 25,     // bucket build: some bucket / voxel does not fit (BF_* bits)
@@ -245,22 +283,25 @@ enum {
   SM_INC_NEWVOX = 31,   // incremental insertion: distinct new voxels
   SM_SLOT_COUNTS = 28,  // octl_forest_slot_counts: two u64 (points, leaves of the pose), words 28..31
   SM_BUILD_WORDS = 32,  // (end of the words k_build_begin resets)
+  SM_MASK_TOTAL = 33,   // apply_mask without the fused kernel: grand total of its scan (written before it is read)
   SM_BK_LEVEL = 40,     // bucket build: internal nodes per level (7 words)
   SM_GEOM = 64,         // bucket build: key geometry formed on the device (GeomDev, <= 192 bytes)
-  SM_SLOT_HIST = 64,    // forest_reference_order: blocks per pose slot (up to 256 words)
+  SM_SLOT_HIST = 128,   // forest_reference_order: blocks per pose slot (up to 256 words)
   SM_ALLREDUCE = 512,   // route.hip: int64 allreduce buffer (up to 256 values, to the end of the block)
   SM_WORDS = 1024
 };
 static_assert(SM_ERR < SM_BUILD_WORDS && SM_BBOX + 6 <= SM_BUILD_WORDS && SM_NVOX < SM_BUILD_WORDS &&
                   SM_NSPLIT < SM_BUILD_WORDS && SM_NTILES < SM_BUILD_WORDS && SM_ETOTAL < SM_BUILD_WORDS &&
                   SM_NBLOCKS < SM_BUILD_WORDS && SM_BK_TICKET < SM_BUILD_WORDS && SM_BK_OVERFULL < SM_BUILD_WORDS &&
-                  SM_SLOT_VOXELS < SM_BUILD_WORDS && SM_MASK_TOTAL < SM_BUILD_WORDS &&
+                  SM_SLOT_VOXELS < SM_BUILD_WORDS &&
                   SM_BK_NOORDER < SM_BUILD_WORDS && SM_DEBUG_TOTAL < SM_BUILD_WORDS && SM_BK_FLAGS < SM_BUILD_WORDS &&
                   SM_BK_TOTAL < SM_BUILD_WORDS && SM_BK_TODO < SM_BUILD_WORDS && SM_BK_MISSING < SM_BUILD_WORDS &&
                   SM_CK_COUNT < SM_BUILD_WORDS && SM_INC_NEWVOX < SM_BUILD_WORDS &&
                   SM_SLOT_COUNTS + 4 <= SM_BUILD_WORDS,
-              "single words of the scalar block lie among the words k_build_begin resets");
-static_assert(SM_BUILD_WORDS <= SM_BK_LEVEL && SM_BK_LEVEL + 7 <= SM_GEOM && SM_GEOM + 192 / 4 <= SM_ALLREDUCE &&
+              "the words a build starts from zero lie among the words k_build_begin resets");
+static_assert(SM_MASK_TOTAL >= SM_BUILD_WORDS && SM_MASK_TOTAL < SM_BK_LEVEL,
+              "apply_mask may be in flight beside the next build's front: its word is none of the front's");
+static_assert(SM_BUILD_WORDS <= SM_BK_LEVEL && SM_BK_LEVEL + 7 <= SM_GEOM && SM_GEOM + 192 / 4 <= SM_SLOT_HIST &&
                   SM_SLOT_HIST + 256 <= SM_ALLREDUCE && SM_ALLREDUCE + 2 * 256 <= SM_WORDS,
               "scalar block regions");
 uint32_t octl_wait_next_seq(octl_ctx* ctx);
@@ -296,7 +337,8 @@ int pin_region_mark(octl_ctx* ctx, int r);
 // copy `bytes` (a multiple of 8) from page-locked HOST memory to the device with a kernel on the context's
 // stream: a small hipMemcpyAsync goes through the DMA queue and waits there behind a large upload that is in
 // flight on the copy stream (measured: 2.9 ms per scan of the asynchronous feed)
-int octl_copy_from_pinned(octl_ctx* ctx, void* dst_dev, const void* src_pinned, size_t bytes);
+// (`on`: the stream the copy goes to; nullptr = the context's)
+int octl_copy_from_pinned(octl_ctx* ctx, void* dst_dev, const void* src_pinned, size_t bytes, hipStream_t on = nullptr);
 
 // grow-only device buffer; contents are NOT preserved unless keep != 0
 int devbuf_reserve(octl_ctx* ctx, DevBuf& b, size_t bytes, int keep = 0);
@@ -374,6 +416,52 @@ int octl_ctx_cus(octl_ctx* ctx);
 bool octl_ctx_side_stream(octl_ctx* ctx);
 int octl_exclusive_scan_u32(octl_ctx* ctx, const uint32_t* in, uint32_t* out, int64_t n,
                             uint32_t* total_dev);
+// ---- the ahead stream (ctx.hip) ---------------------------------------------------------------------
+// Points from which a build may run ahead when OCTL_BUILD_AHEAD_MIN_POINTS is not set.  No crossover was found: forced
+// on, the 100 k-point scan of bench.py (secondary.small_scan_100k) is 0.117-0.123 ms against the parent's 0.124-0.125 with
+// one cloud and 0.120-0.122 against 0.129-0.130 with three in turn (three repetitions each, interleaved, one box).  Nothing
+// smaller was measured, so the bound is the smallest size that was.
+constexpr int64_t OCTL_AHEAD_MIN_POINTS = 100000;
+constexpr int64_t OCTL_AHEAD_TILES = 4096;  // status words of the ahead stream's look-back chain
+static inline int64_t octl_ahead_min_points(const octl_ctx* ctx) {
+  return ctx->opt.build_ahead_min_points >= 0 ? ctx->opt.build_ahead_min_points : OCTL_AHEAD_MIN_POINTS;
+}
+// the ahead stream, its two events and its status words, created on first use; false when they cannot be had (not an
+// error: the build stays serial)
+bool octl_ctx_ahead_stream(octl_ctx* ctx);
+// Since the context's last build, did the library enqueue work under an AheadAllow on it, and nothing else?
+bool octl_ahead_untouched(const octl_ctx* ctx, const struct octl_forest* f);
+// Opens a front: the ahead stream waits for ahead_free and for the uploads still in flight into [cloud, cloud + bytes).
+// false: nothing was enqueued there, the build is serial.
+bool octl_ahead_open(octl_ctx* ctx, const void* cloud, size_t bytes);
+// the stream a build's front goes to: the ahead stream while a front is open, else the context's
+static inline hipStream_t octl_front_stream(const octl_ctx* ctx) { return ctx->ahead_open ? ctx->ahead_stream : ctx->stream; }
+// The join: the context's stream waits for everything on the ahead stream.  No-op when no front is open.
+void octl_ahead_join(octl_ctx* ctx);
+// the end of a build of f: ok - the tally starts; else the context's next build is serial
+void octl_ahead_build_end(octl_ctx* ctx, const struct octl_forest* f, bool ok, int64_t n_points);
+// the first allow-listed function behind a build records ahead_free, if nothing else was enqueued in between
+void octl_ahead_arm(octl_ctx* ctx);
+// status words + a fresh epoch for a look-back chain ON THE AHEAD STREAM of up to OCTL_AHEAD_TILES workgroups
+int octl_ahead_status_acquire(octl_ctx* ctx, int64_t tiles, uint64_t** status, uint32_t* epoch);
+// Scope of a function whose device work touches nothing a build's front reads or writes (DESIGN 4.4.1 lists them with
+// the reasons): what it enqueues is added to the context's tally, so that the next build may still run ahead.
+// Scopes may nest (an allow-listed function that calls another one): only the outermost scope counts, so that nothing
+// is added twice - a tally that is too large could balance an enqueue the list does not cover.
+struct AheadAllow {
+  octl_ctx* ctx;
+  uint64_t at = 0;
+  explicit AheadAllow(octl_ctx* c) : ctx(c) {
+    if (ctx->ahead_allow_depth++ != 0) return;
+    if (ctx->ahead_mark_pending) octl_ahead_arm(ctx);
+    at = g_octl_enqueues.load(std::memory_order_relaxed);
+  }
+  ~AheadAllow() {
+    if (--ctx->ahead_allow_depth == 0) ctx->ahead_allowed += g_octl_enqueues.load(std::memory_order_relaxed) - at;
+  }
+  AheadAllow(const AheadAllow&) = delete;
+  AheadAllow& operator=(const AheadAllow&) = delete;
+};
 // status words + a fresh epoch for one look-back chain of up to `tiles` workgroups (lookback.h)
 int octl_scan_status_acquire(octl_ctx* ctx, int64_t tiles, uint64_t** status, uint32_t* epoch);
 // the allocations of a following octl_scan_status_acquire(tiles) / octl_exclusive_scan_u32(n) made now, so that neither

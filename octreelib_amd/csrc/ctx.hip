@@ -32,6 +32,7 @@ const OptName kOptions[] = {
     {"NO_FUSED_TABLES", &OctlOptions::no_fused_tables},     {"NO_SPIN_WAIT", &OctlOptions::no_spin_wait},
     {"NO_SPEC_FINISH", &OctlOptions::no_spec_finish},       {"RANSAC_WAVES", &OctlOptions::ransac_waves},
     {"GEOM_MARGIN", &OctlOptions::geom_margin},             {"NO_RANSAC_PRESCREEN", &OctlOptions::no_ransac_prescreen},
+    {"NO_BUILD_AHEAD", &OctlOptions::no_build_ahead},       {"BUILD_AHEAD_MIN_POINTS", &OctlOptions::build_ahead_min_points},
 };
 }  // namespace
 
@@ -70,6 +71,14 @@ std::atomic<uint64_t> g_octl_launches{0};
 extern "C" int octl_debug_launches(uint64_t* count) {
   if (!count) return OCTL_E_INVALID;
   *count = g_octl_launches.load(std::memory_order_relaxed);
+  return OCTL_OK;
+}
+
+std::atomic<uint64_t> g_octl_enqueues{0}, g_octl_builds_ahead{0};
+
+extern "C" int octl_debug_builds_ahead(uint64_t* count) {
+  if (!count) return OCTL_E_INVALID;
+  *count = g_octl_builds_ahead.load(std::memory_order_relaxed);
   return OCTL_OK;
 }
 
@@ -160,6 +169,119 @@ bool octl_ctx_side_stream(octl_ctx* ctx) {
   if (st) (void)hipStreamDestroy(st);
   (void)hipGetLastError();
   return false;
+}
+
+// ---- the ahead stream -------------------------------------------------------------------------------
+bool octl_ctx_ahead_stream(octl_ctx* ctx) {
+  if (ctx->ahead_stream) return true;
+  hipStream_t st = nullptr;
+  hipEvent_t free_ev = nullptr, done = nullptr;
+  // (the status words come from devbuf_reserve like every device allocation of the library: octl_debug_fail_alloc
+  //  reaches the "cannot be had" branch; a failure is not the caller's error - its message is taken back)
+  const std::string err_before = ctx->err;
+  if (devbuf_reserve(ctx, ctx->ahead_status, (size_t)OCTL_AHEAD_TILES * 8) != OCTL_OK) {
+    ctx->err = err_before;
+    return false;
+  }
+  void* status = ctx->ahead_status.p;
+  // (the status words start as "never published"; the fill is the stream's first operation, once per context - it
+  //  is not part of any build's launches and goes past the launch counter)
+  // (at the default priority: at the device's highest the headline measured the same)
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
+      hipEventCreateWithFlags(&free_ev, hipEventDisableTiming) == hipSuccess &&
+      hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess &&
+      (hipMemsetAsync)(status, 0, (size_t)OCTL_AHEAD_TILES * 8, st) == hipSuccess) {
+    ctx->ahead_stream = st;
+    ctx->ahead_free = free_ev;
+    ctx->ahead_done = done;
+    ctx->ahead_epoch = 0;
+    return true;
+  }
+  if (st) (void)hipStreamSynchronize(st);
+  if (done) (void)hipEventDestroy(done);
+  if (free_ev) (void)hipEventDestroy(free_ev);
+  if (st) (void)hipStreamDestroy(st);
+  (void)hipGetLastError();
+  return false;
+}
+
+bool octl_ahead_untouched(const octl_ctx* ctx, const octl_forest* f) {
+  // (valid only once an allow-listed function has run since the build, octl_ahead_arm: a loop of builds alone has
+  //  nothing to run a front beside, and the two cross-stream waits cost it 30 us of a 620 us build - measured)
+  return ctx->ahead_mark_valid && ctx->ahead_forest == f &&
+         g_octl_enqueues.load(std::memory_order_relaxed) == ctx->ahead_mark + ctx->ahead_allowed;
+}
+
+bool octl_ahead_open(octl_ctx* ctx, const void* cloud, size_t bytes) {
+  if (ctx->ahead_open || !ctx->ahead_stream) return false;
+  // Every wait of the ahead stream is for an event recorded EARLIER on another stream, and the context's stream
+  // waits for the ahead stream only at the join, which is enqueued later: no cycle.
+  bool ok = hipStreamWaitEvent(ctx->ahead_stream, ctx->ahead_free, 0) == hipSuccess;
+  // (the cloud may be the target of an octl_dev_upload_async that is still in flight: the context's stream was made
+  //  to wait for it when the cloud was adopted, and the front reads the cloud too)
+  const char* a = static_cast<const char*>(cloud);
+  for (auto& u : ctx->uploads) {
+    if (!ok) break;
+    if (a + bytes <= u.dst || u.dst + u.bytes <= a) continue;
+    ok = hipStreamWaitEvent(ctx->ahead_stream, u.done, 0) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    return false;  // (only waits were enqueued: harmless)
+  }
+  ctx->ahead_open = true;
+  return true;
+}
+
+void octl_ahead_join(octl_ctx* ctx) {
+  if (!ctx->ahead_open) return;
+  ctx->ahead_open = false;
+  if (hipEventRecord(ctx->ahead_done, ctx->ahead_stream) != hipSuccess ||
+      hipStreamWaitEvent(ctx->stream, ctx->ahead_done, 0) != hipSuccess) {
+    // (no event to order the streams with: the host waits instead, and the next build is serial)
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(ctx->ahead_stream);
+    ctx->ahead_mark_valid = false;
+  }
+}
+
+void octl_ahead_build_end(octl_ctx* ctx, const octl_forest* f, bool ok, int64_t n_points) {
+  octl_ahead_join(ctx);
+  ctx->ahead_mark_valid = ctx->ahead_mark_pending = false;
+  // (a context that is profiling marks the build too: whether the NEXT build may run ahead is the next build's question)
+  if (!ok || ctx->opt.no_build_ahead || n_points < octl_ahead_min_points(ctx)) return;
+  // (the event itself is recorded by the first allow-listed function that follows, octl_ahead_arm: a loop of builds
+  //  alone, which has nothing to run a front beside, does not pay for it - 10 us of a 660 us build, measured)
+  ctx->ahead_forest = f;
+  ctx->ahead_mark = g_octl_enqueues.load(std::memory_order_relaxed);
+  ctx->ahead_allowed = 0;
+  ctx->ahead_mark_pending = true;
+}
+
+void octl_ahead_arm(octl_ctx* ctx) {
+  ctx->ahead_mark_pending = false;
+  // (something else was enqueued between the build and this function: the next build is serial)
+  if (g_octl_enqueues.load(std::memory_order_relaxed) != ctx->ahead_mark || !octl_ctx_ahead_stream(ctx)) return;
+  // "front scratch free": everything the build enqueued - the last readers of part_xyz, bk_table, the scalar words and
+  // the geometry record among it, the attempts of a rejected hint too - is in front of this event, and nothing else is
+  if (hipEventRecord(ctx->ahead_free, ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  ctx->ahead_mark_valid = true;
+}
+
+int octl_ahead_status_acquire(octl_ctx* ctx, int64_t tiles, uint64_t** status, uint32_t* epoch) {
+  if (!ctx->ahead_open || tiles > OCTL_AHEAD_TILES)
+    return octl_set_error(ctx, OCTL_E_STATE, "ahead stream: no front is open, or a look-back chain of %lld tiles",
+                          (long long)tiles);
+  if (ctx->ahead_epoch >= (1u << 30) - 1) {  // (the epoch wraps: the words start over, in the ahead stream's order)
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ahead_status.p, 0, (size_t)OCTL_AHEAD_TILES * 8, ctx->ahead_stream));
+    ctx->ahead_epoch = 0;
+  }
+  *epoch = ++ctx->ahead_epoch;  // 0 = "never published"
+  *status = ctx->ahead_status.as<uint64_t>();
+  return OCTL_OK;
 }
 
 int octl_ctx_cus(octl_ctx* ctx) {
@@ -277,11 +399,11 @@ __global__ __launch_bounds__(256) void k_copy_u64(const uint64_t* __restrict__ s
 }
 }  // namespace
 
-int octl_copy_from_pinned(octl_ctx* ctx, void* dst_dev, const void* src_pinned, size_t bytes) {
+int octl_copy_from_pinned(octl_ctx* ctx, void* dst_dev, const void* src_pinned, size_t bytes, hipStream_t on) {
   const size_t n = bytes / 8;
   if (n == 0) return OCTL_OK;
   const unsigned grid = (unsigned)std::min<size_t>(64, (n + 255) / 256);
-  OCTL_LAUNCH(k_copy_u64, dim3(grid), dim3(256), 0, ctx->stream, static_cast<const uint64_t*>(src_pinned),
+  OCTL_LAUNCH(k_copy_u64, dim3(grid), dim3(256), 0, on ? on : ctx->stream, static_cast<const uint64_t*>(src_pinned),
                      static_cast<uint64_t*>(dst_dev), n);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;
@@ -412,6 +534,7 @@ void octl_ctx_destroy(octl_ctx* ctx) {
   devbuf_free(ctx->ls_buf);
   devbuf_free(ctx->rs_counters);
   devbuf_free(ctx->scan_status);
+  devbuf_free(ctx->ahead_status);
   devbuf_free(ctx->small);
   devbuf_free(ctx->routed_xyz);
   devbuf_free(ctx->routed_gidx);
@@ -425,6 +548,12 @@ void octl_ctx_destroy(octl_ctx* ctx) {
     (void)hipStreamDestroy(ctx->self_stream);
     if (ctx->self_gate) (void)hipEventDestroy(ctx->self_gate);
     if (ctx->self_done) (void)hipEventDestroy(ctx->self_done);
+  }
+  if (ctx->ahead_stream) {
+    (void)hipStreamSynchronize(ctx->ahead_stream);
+    (void)hipStreamDestroy(ctx->ahead_stream);
+    (void)hipEventDestroy(ctx->ahead_free);
+    (void)hipEventDestroy(ctx->ahead_done);
   }
   if (ctx->copy_stream) {
     (void)hipStreamSynchronize(ctx->copy_stream);
@@ -472,6 +601,9 @@ int octl_dev_upload_async(octl_ctx* ctx, void* dptr, const void* src, int64_t by
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->copy_gate, hipEventDisableTiming));
   }
   if (bytes == 0) return OCTL_OK;
+  // (the copy writes the caller's buffer alone, behind a gate that covers every front that read it - a front is joined
+  //  into the context's stream before its build returns: the next build may still run ahead)
+  AheadAllow allow(ctx);
   // the destination may still be read by compute work that was enqueued before this call
   HIP_TRY(ctx, hipEventRecord(ctx->copy_gate, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->copy_gate, 0));

@@ -591,6 +591,7 @@ int octl_forest_apply_mask(octl_forest* f, int64_t* n_alive) {
   if (!f) return OCTL_E_INVALID;
   OCTL_TRY(forest_settle(f));
   if (!f->built) return octl_set_error(f->ctx, OCTL_E_STATE, "apply_mask before build");
+  AheadAllow allow(f->ctx);  // (see octl_forest_apply_mask_async)
   OCTL_TRY(ensure_mask(f));
   return apply_device_mask(f, n_alive);
 }
@@ -599,6 +600,12 @@ int octl_forest_apply_mask_async(octl_forest* f) {
   if (!f) return OCTL_E_INVALID;
   OCTL_TRY(forest_settle(f));
   if (!f->built) return octl_set_error(f->ctx, OCTL_E_STATE, "apply_mask before build");
+  // The compaction reads the mask, the leaf-ordered arrays and the block table, writes their second set, the alive
+  // flags and f->flags, chains its workgroups over the status words of the context's stream and keeps its one scalar
+  // (SM_MASK_TOTAL) outside the words a build's front writes: the partition front of the context's next build may run
+  // on the ahead stream while it is in flight - that build takes no alive flags (every point of a cloud
+  // taken in place is alive), so the fill of f->alive in here is not its concern either.
+  AheadAllow allow(f->ctx);
   OCTL_TRY(ensure_mask(f));
   return apply_device_mask(f, nullptr, true);
 }

@@ -339,6 +339,35 @@ extern "C" int octl_forest_reference_order(octl_forest* f, const int32_t* e0, in
   return OCTL_OK;
 }
 
+// The hypothesis table on the device (ctx->hyp_dev).  The upload writes that buffer out of a staging region of its
+// own, nothing a build's front touches: the context's next build may still run ahead (AheadAllow).
+static int ransac_table_upload(octl_ctx* ctx, const double* hypotheses, int32_t H, int32_t k) {
+  AheadAllow allow(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t hyp_cap_before = ctx->hyp_dev.cap;
+  OCTL_TRY(devbuf_reserve(ctx, ctx->hyp_dev, (size_t)H * k * 8));
+  // the table of the previous call on this context (CudaRansac draws it once per object, cuda_ransac.py:39-41; a
+  // loop over scans hands the same one over for every scan): already on the device
+  const bool same_table = hyp_cap_before == ctx->hyp_dev.cap && ctx->hyp_host.size() == (size_t)H * k &&
+                          std::memcmp(ctx->hyp_host.data(), hypotheses, (size_t)H * k * 8) == 0;
+  if (same_table) {
+    // nothing to upload
+  } else if ((size_t)H * k * 8 <= 64 * 1024) {  // pinned staging: [128 KiB, 192 KiB) of ctx->pinned
+    // the launches below are not synchronised: a later call must not overwrite the staging area
+    // while this copy is still pending
+    char* pin = static_cast<char*>(ctx->pinned) + 128 * 1024;
+    OCTL_TRY(pin_region_wait(ctx, 1));
+    std::memcpy(pin, hypotheses, (size_t)H * k * 8);
+    OCTL_TRY(octl_copy_from_pinned(ctx, ctx->hyp_dev.p, pin, (size_t)H * k * 8));
+    OCTL_TRY(pin_region_mark(ctx, 1));
+  } else {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->hyp_dev.p, hypotheses, (size_t)H * k * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  if (!same_table) ctx->hyp_host.assign(hypotheses, hypotheses + (size_t)H * k);
+  return OCTL_OK;
+}
+
 static int ransac_all_impl(octl_forest* f, int32_t poses_per_batch, const int32_t* e0, int32_t n_e0,
                            const double* hypotheses, int32_t H, int32_t k, double threshold,
                            bool* mask_fresh);
@@ -368,7 +397,6 @@ static int ransac_all_impl(octl_forest* f, int32_t poses_per_batch, const int32_
   const int n_poses = (int)f->pose_off.size() - 1;
   if (e0 && n_e0 != n_poses) return octl_set_error(ctx, OCTL_E_INVALID, "e0 size mismatch");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   // (no "keep" fill here: the batches below cover every block of every pose, the blocks tile the
   //  leaf-ordered arrays, and every block's mask bytes are written - by the scoring kernels, or as zeros for
   //  the blocks with fewer than k points)
@@ -377,27 +405,7 @@ static int ransac_all_impl(octl_forest* f, int32_t poses_per_batch, const int32_
     *mask_fresh = true;  // (the caller marks it valid once everything below has been enqueued)
   }
   if (f->n_blocks == 0) return OCTL_OK;
-  const size_t hyp_cap_before = ctx->hyp_dev.cap;
-  OCTL_TRY(devbuf_reserve(ctx, ctx->hyp_dev, (size_t)H * k * 8));
-  // the table of the previous call on this context (CudaRansac draws it once per object, cuda_ransac.py:39-41; a
-  // loop over scans hands the same one over for every scan): already on the device
-  const bool same_table = hyp_cap_before == ctx->hyp_dev.cap && ctx->hyp_host.size() == (size_t)H * k &&
-                          std::memcmp(ctx->hyp_host.data(), hypotheses, (size_t)H * k * 8) == 0;
-  if (same_table) {
-    // nothing to upload
-  } else if ((size_t)H * k * 8 <= 64 * 1024) {  // pinned staging: [128 KiB, 192 KiB) of ctx->pinned
-    // the launches below are not synchronised: a later call must not overwrite the staging area
-    // while this copy is still pending
-    char* pin = static_cast<char*>(ctx->pinned) + 128 * 1024;
-    OCTL_TRY(pin_region_wait(ctx, 1));
-    std::memcpy(pin, hypotheses, (size_t)H * k * 8);
-    OCTL_TRY(octl_copy_from_pinned(ctx, ctx->hyp_dev.p, pin, (size_t)H * k * 8));
-    OCTL_TRY(pin_region_mark(ctx, 1));
-  } else {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->hyp_dev.p, hypotheses, (size_t)H * k * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
-  if (!same_table) ctx->hyp_host.assign(hypotheses, hypotheses + (size_t)H * k);
+  OCTL_TRY(ransac_table_upload(ctx, hypotheses, H, k));
   const bool one_batch = n_poses <= poses_per_batch;
   std::vector<uint32_t> slot_counts;
   OCTL_TRY(forest_reference_order(f, e0, slot_counts, !one_batch));

@@ -2147,6 +2147,11 @@ int ransac_launch(octl_ctx* ctx, const double* xyz_dev, int64_t n_points,
   // more sample points than the register path holds: every block takes the exact path with a streamed fit
   const bool any_k = k > RS_KMAX;
   if (nb >= ((int64_t)1 << 31)) return octl_set_error(ctx, OCTL_E_INVALID, "too many blocks");
+  // Everything below reads the leaf-ordered arrays, the block table and the hypothesis table and writes the mask, the
+  // caller's scratch and ctx->rs_counters; its look-back chain uses the status words of the context's stream and it
+  // owns no word of the scalar block.  The partition front of the context's NEXT build touches none of that, so it may
+  // run on the ahead stream while these kernels are in flight.
+  AheadAllow allow(ctx);
   hipStream_t st = ctx->stream;
   // scratch: [sizes/scanned u32 nb+8 | desc 32 B x nb | sorted desc 32 B x nb | big list u32 nb |
   //           counters]
