@@ -571,6 +571,45 @@ int octl_forest_point_stats(octl_forest* f, double radius, const uint8_t* slot_s
                             const uint8_t* among_sel, int32_t n_among, int64_t cap, int64_t* n_rows, int32_t* slot,
                             int32_t* index, int64_t* count, double* mean, double* cov, double* eigval,
                             double* eigvec);
+/* Euclidean cluster extraction: the connected components of "two stored points are within `radius` of each other" over
+ * the points of the leaf-ordered arrays that belong to a selected pose (slot_sel[slot] != 0; NULL: every pose;
+ * otherwise n_sel = number of poses).  Two points are joined iff d2 = (dx dx + dy dy) + dz dz <= radius^2 in f64 with
+ * separate products and sums, inclusive - the candidates of octl_forest_radius_count under the same selection, found
+ * by the same walk; a duplicate at the same coordinates is a neighbour.  The selected poses are the whole graph: points
+ * of other poses have no row and bridge nothing.  Points that a pending RANSAC mask is about to drop are still in the
+ * ordered arrays: they have rows and connect.  octreelib_amd/clustering.py: cluster_labels_np is the definition.
+ * One row per vertex: slot[i], index[i] (int32) name the point (its pose's slot and its row in that pose's cloud as
+ * inserted - the index of octl_forest_nearest), first[i] (int64) = slot << 32 | index of the smallest member of its
+ * component in that order, size[i] (int32) the number of members.  The rows come in no particular order: the caller
+ * sorts them by (slot, index) and numbers the distinct values of `first`.  *n_rows = number of rows; they are written
+ * only when cap >= *n_rows (size query: cap = 0), and a cap of at least min(ordered points, store rows of the selected
+ * poses) saves the second wait.  Any output array may be NULL.
+ * OCTL_E_INVALID: cap < 0; n_rows NULL; radius not finite or <= 0; a grid with radius above twice the voxel edge; a
+ * selection of the wrong length.  OCTL_E_STATE: before the first build; a forest whose rows map_leaf_points moved
+ * outside their leaves; a union-find that ran out of its step budget (damaged tables).  One wavefront per (leaf, pose)
+ * block; with the index of the selection in place a call is four kernels (init, link, flatten, rows), two small
+ * uploads, the downloads and one wait (two when cap is below the bound), whatever the number of points, clusters or
+ * path lengths.  The answer is a function of the stored points and the selection alone: not of the subdivision, the
+ * layout or the schedule.  Nothing of the forest changes and no cached table is dropped.  No reference counterpart.  */
+int octl_forest_cluster_points(octl_forest* f, double radius, const uint8_t* slot_sel, int32_t n_sel, int64_t cap,
+                               int64_t* n_rows, int32_t* slot, int32_t* index, int64_t* first, int32_t* size);
+/* Remove small clusters: every point of the selected poses whose component - octl_forest_cluster_points over the same
+ * selection - has fewer than min_points members leaves the leaf-ordered arrays (and counts as removed in the store):
+ * clumps of speckle that octl_forest_remove_sparse keeps because each of their points has neighbours.  Every decision
+ * is made on the map as it is before the call - one simultaneous round, after which a second call removes nothing.
+ * octreelib_amd/clustering.py: small_cluster_keep_np is the rule.  The kernels never read the mask: points a pending
+ * RANSAC mask is about to drop still connect and are judged.  The kernel clears bytes in the mask and the mask is
+ * applied as octl_forest_remove_sparse applies its own: a pending RANSAC mask goes into the same ONE compaction.  The
+ * scheme stays; the index of octl_forest_nearest of a surviving row is unchanged; the block index, the pooled planes,
+ * the segments and the adjustment tables go stale.  *n_alive (nullable) = points left in the leaf-ordered arrays.
+ * OCTL_E_INVALID: min_points < 1; radius as above; a selection of the wrong length.  OCTL_E_STATE: before the first
+ * build; a forest whose rows map_leaf_points moved outside their leaves - both before anything runs: a refused call
+ * leaves points and mask as they were, and every buffer is reserved before the mask is written; a union-find that ran
+ * out of its step budget (damaged tables) clears no byte of the mask and is reported after the compaction.  With the
+ * index of the selection in place a call is four kernels (init, link, flatten, mask: it also writes the ones of a
+ * mask that was not pending), two small uploads and the compaction with its one wait.  No reference counterpart.     */
+int octl_forest_remove_small_clusters(octl_forest* f, double radius, int32_t min_points, const uint8_t* slot_sel,
+                                      int32_t n_sel, int64_t* n_alive);
 /* Plane segments: the rows of the pooled plane table (octl_forest_pooled_leaf_stats of the selection slot_sel; made by
  * this call when the forest holds none that is valid) merged across the faces of their leaves into connected coplanar
  * regions.  octreelib_amd/query.py: plane_segments_np is the definition; every decision is made on the table's bits in

@@ -14,6 +14,8 @@ raises.
 
 from octreelib_amd.adjustment import (Adjustment, AdjustmentLeaves, AdjustmentSystem, BlockMoments, adjust_np,
                                       adjustment_system_np, block_moments_np)
+from octreelib_amd.clustering import (Clusters, check_cluster_args, cluster, cluster_labels_np, remove_small_clusters,
+                                      small_cluster_keep_np)
 from octreelib_amd.criteria import MaxPoints, NotPlanar
 from octreelib_amd.feed import DeviceCloud, ScanPipeline, pinned_empty, upload_async
 from octreelib_amd.query import (LeafPlanes, Neighbours, PlaneSegments, PointToPlane, PruneResult, RayEvidence,
@@ -39,4 +41,5 @@ __all__ = ["MaxPoints", "NotPlanar", "DeviceCloud", "ScanPipeline", "pinned_empt
            "sparse_keep_np", "nearest_plane_registration_system_np", "nearest_plane_registration_system",
            "align_nearest_planes", "cell_index_np", "cell_count_np", "thin_keep_np", "check_cell_args", "cell_count",
            "thin", "PointStatistics", "neighbourhood_statistics", "neighbourhood_statistics_np", "point_statistics",
-           "point_statistics_np", "orient_towards", "__version__"]
+           "point_statistics_np", "orient_towards", "Clusters", "cluster_labels_np", "small_cluster_keep_np",
+           "check_cluster_args", "cluster", "remove_small_clusters", "__version__"]

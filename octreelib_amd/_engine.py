@@ -904,6 +904,61 @@ class Forest:
         return PointStatistics(count[:m][order], mean[:m][order], cov6_to_full(cov[:m][order]),
                                w[:m][order] if eigen else None, v[:m][order] if eigen else None, slot, index)
 
+    def cluster_points(self, radius, slots=None, min_points: int = 1, max_points=None, pose_of_slot=None):
+        """Euclidean clusters of the alive stored points of the poses of `slots` (None: all), the graph taken over those
+        poses alone: a clustering.Clusters in ascending (slot, index) (octl_forest_cluster_points: four kernels once the
+        block index of the selection exists, one wait; nothing of the map changes).  The device gives every point the
+        smallest member and the size of its component; the numbering - the distinct smallest members whose size lies in
+        [min_points, max_points], ascending - is finished here.  pose_of_slot maps slots to pose numbers (None: slots
+        are the pose numbers)."""
+        from octreelib_amd.clustering import Clusters, _number, check_cluster_args
+
+        r, lo, hi = check_cluster_args(radius, min_points, max_points, what="cluster")
+        self.ensure_built()
+        sel, n_sel, chosen = self._adjust_selection(slots)
+        cap = min(int(self.n_ord), int(sum(self.slot_sizes[s] for s in chosen)))
+        rows = C.c_int64(0)
+        for _ in range(2):
+            slot = np.empty(cap, dtype=np.int32)
+            index = np.empty(cap, dtype=np.int32)
+            first = np.empty(cap, dtype=np.int64)
+            size = np.empty(cap, dtype=np.int32)
+            self.ctx.check(self.lib.octl_forest_cluster_points(self.handle, r, nat.ptr(sel), n_sel, cap, C.byref(rows),
+                                                               nat.ptr(slot), nat.ptr(index), nat.ptr(first),
+                                                               nat.ptr(size)))
+            if rows.value <= cap:
+                break
+            cap = int(rows.value)   # (the host's bound was short: once more with the size the library found)
+        else:
+            raise RuntimeError(f"cluster: {rows.value} rows do not fit the {cap} asked for")
+        m = int(rows.value)
+        order = np.lexsort((index[:m], slot[:m]))
+        slot, index = slot[:m][order], index[:m][order]
+        label, keys, sizes = _number(first[:m][order], size[:m][order], lo, hi)
+        first_slot, first_index = (keys >> 32).astype(np.int32), (keys & 0xffffffff).astype(np.int32)
+        if pose_of_slot is not None:
+            names = np.asarray(list(pose_of_slot), dtype=np.int32)
+            slot = names[slot] if m else slot
+            first_slot = names[first_slot] if len(keys) else first_slot
+        return Clusters(slot, index, label, sizes, first_slot, first_index)
+
+    def remove_small_clusters(self, radius, min_points, slots=None) -> int:
+        """Every point of the poses of `slots` (None: all) whose cluster over those poses has fewer than min_points
+        members leaves the map (octl_forest_remove_small_clusters: four kernels, one compaction that also applies a
+        pending RANSAC mask; clustering.small_cluster_keep_np is the rule); the scheme stays.  Returns the number of
+        points removed."""
+        from octreelib_amd.clustering import check_cluster_args
+
+        r, lo, _ = check_cluster_args(radius, min_points, what="remove_small_clusters")
+        self.ensure_built()
+        before = self.n_ord
+        sel, n_sel, _ = self._adjust_selection(slots)
+        n = C.c_int64(0)
+        self.ctx.check(self.lib.octl_forest_remove_small_clusters(self.handle, r, lo, nat.ptr(sel), n_sel, C.byref(n)))
+        self.n_ord = n.value
+        self._invalidate()
+        return before - n.value
+
     def cell_count(self, points, cell, max_count=None, slots=None) -> np.ndarray:
         """How many stored points of the poses of `slots` (None: all) lie in the lattice cell of every query point,
         capped at max_count (None: uncapped): (n,) int32 as thinning.cell_count_np defines it (octl_forest_cell_count:

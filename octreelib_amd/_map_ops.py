@@ -11,7 +11,7 @@ The inheriting class provides
   _plug_poses()            the plug's table that is keyed by pose number
   _noun                    "a Grid" / "an OctreeManager", for the refusals on the caller's own plug types
 
-The module-level map functions (matching.py, thinning.py, neighbourhood.py) take any of the three classes and start with _resolve below.
+The module-level map functions (matching.py, thinning.py, neighbourhood.py, clustering.py) take any of the three classes and start with _resolve below.
 
 Octree is not served from here: its operations take no pose_numbers, so every signature differs, and each is already
 two lines over Forest.
@@ -29,7 +29,7 @@ __all__ = ["MapOperations"]
 
 
 def _resolve(map, pose_numbers, what):
-    """What the module-level map functions (matching.py, thinning.py, neighbourhood.py) start with: (forest or None, HostMap or None,
+    """What the module-level map functions (matching.py, thinning.py, neighbourhood.py, clustering.py) start with: (forest or None, HostMap or None,
     selection, pose numbers in slot order) of a Grid, an OctreeManager or an Octree; TypeError for anything else,
     ValueError for an Octree with pose_numbers, KeyError for an unknown pose."""
     from octreelib_amd.octree import Octree

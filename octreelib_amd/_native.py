@@ -122,6 +122,8 @@ SIGNATURES = {
     "octl_forest_neighbourhood_stats": (C.c_int, [_p, _p, _i64, _f64, _p, _i32, _p, _p, _p, _p, _p]),
     "octl_forest_neighbourhood_stats_device": (C.c_int, [_p, _p, _i64, _f64, _p, _i32, _p, _p, _p, _p, _p]),
     "octl_forest_point_stats": (C.c_int, [_p, _f64, _p, _i32, _p, _i32, _i64, _pi64, _p, _p, _p, _p, _p, _p, _p]),
+    "octl_forest_cluster_points": (C.c_int, [_p, _f64, _p, _i32, _i64, _pi64, _p, _p, _p, _p]),
+    "octl_forest_remove_small_clusters": (C.c_int, [_p, _f64, _i32, _p, _i32, _pi64]),
     "octl_forest_plane_segments": (C.c_int, [_p, _p, _i32, _i32, _f64, _f64, _f64, _i64, _i64, _p, _p, _p, _p, _p, _p,
                                              _p, _p, _p, _pi64, _pi64]),
     "octl_forest_registration_system": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _p, _p]),

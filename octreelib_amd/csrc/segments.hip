@@ -34,6 +34,7 @@
 #include "leaf_moments.h"
 #include "query_walk.h"
 #include "sym3_eigen.h"
+#include "union_find.h"
 
 namespace {
 
@@ -57,23 +58,6 @@ __device__ __forceinline__ double seg_before(double c) {
   if (c == 0.0) return __longlong_as_double((long long)0x8000000000000001ull);
   const long long b = __double_as_longlong(c);
   return __longlong_as_double(c > 0.0 ? b - 1 : b + 1);
-}
-
-__device__ __forceinline__ int32_t uf_load(const int32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of x, halving the path on the way (a non-root's parent only ever moves to another of its ancestors, so any
-// order of these writes keeps parent[x] <= x and the trees); -1 when the table is damaged or the budget is spent
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t x, int64_t& budget) {
-  for (;;) {
-    const int32_t p = uf_load(parent + x);
-    if (p == x) return x;
-    if (p < 0 || p > x || --budget < 0) return -1;
-    const int32_t g = uf_load(parent + p);
-    if (g >= 0 && g < p) atomicMin(parent + x, g);
-    x = p;
-  }
 }
 
 __global__ __launch_bounds__(256) void k_seg_init(int64_t n_rows, const double2* __restrict__ rows, SegGate g,
@@ -125,29 +109,9 @@ __global__ __launch_bounds__(256) void k_seg_link(int64_t n_rows, const int32_t*
   const double oi = (a0.x * dx + a0.y * dy) + a1.x * dz;
   const double oj = (b0.x * dx + b0.y * dy) + b1.x * dz;
   if (!(fabs(oi) <= g.max_offset && fabs(oj) <= g.max_offset)) return;
-  // ---- union of rows i and j ----
+  // ---- union of rows i and j (union_find.h) ----
   int64_t budget = max_steps;
-  int32_t a = (int32_t)i, b = j;
-  for (;;) {
-    a = uf_find(parent, a, budget);
-    b = a < 0 ? -1 : uf_find(parent, b, budget);
-    if (a < 0 || b < 0) {
-      atomicOr(words + SEG_W_ERR, 1u);
-      return;
-    }
-    if (a == b) return;
-    if (a < b) {
-      const int32_t s = a;
-      a = b;
-      b = s;
-    }
-    if (atomicCAS(parent + a, a, b) == a) return;
-    // (someone hooked a first: it is no root any more - find again from where we stand)
-    if (--budget < 0) {
-      atomicOr(words + SEG_W_ERR, 1u);
-      return;
-    }
-  }
+  if (uf_union(parent, (int32_t)i, j, budget) < 0) atomicOr(words + SEG_W_ERR, 1u);
 }
 
 __global__ __launch_bounds__(256) void k_seg_flatten(int64_t n_rows, int64_t max_steps, int32_t* parent,

@@ -1088,6 +1088,34 @@ class HostMap:
                 out.append((t, by_name[t]))
         return out
 
+    def cluster(self, radius, *, min_points=1, max_points=None, pose_numbers=None):
+        """Euclidean clusters over the map as it stands: a clustering.Clusters with one row per point of the chosen
+        poses (pose_numbers, None: all) in the order the poses were inserted, index = the row of clouds([pose])."""
+        from octreelib_amd.clustering import Clusters, check_cluster_args, cluster_labels_np
+
+        r, lo, hi = check_cluster_args(radius, min_points, max_points, what="cluster")
+        self._radius_cap(r, "cluster")
+        clouds = self.clouds(pose_numbers)
+        labels, sizes, first = cluster_labels_np(clouds, r, lo, hi)
+        names = np.asarray([p for p, _ in clouds], dtype=np.int32)
+        lens = [len(c) for _, c in clouds]
+        pose = np.repeat(names, lens).astype(np.int32)
+        index = (np.concatenate([np.arange(m, dtype=np.int32) for m in lens]) if lens else np.empty(0, dtype=np.int32))
+        label = np.concatenate(labels).astype(np.int32) if labels else np.empty(0, dtype=np.int32)
+        first_pose = names[first[:, 0]] if len(first) else np.empty(0, dtype=np.int32)
+        return Clusters(pose, index, label, sizes, first_pose, first[:, 1].astype(np.int32))
+
+    def remove_small_clusters(self, radius, min_points, *, pose_numbers=None):
+        """The decision of remove_small_clusters over the map as it stands: [(pose number, keep)] for every chosen pose
+        (pose_numbers, None: all) in the order the poses were inserted, keep one bool per row of clouds([pose]).  These
+        classes only know a pose through the caller's leaves, so nothing is removed here: the caller applies it."""
+        from octreelib_amd.clustering import check_cluster_args, small_cluster_keep_np
+
+        r, lo, _ = check_cluster_args(radius, min_points, what="remove_small_clusters")
+        self._radius_cap(r, "remove_small_clusters")
+        clouds = self.clouds(pose_numbers)
+        return [(p, k) for (p, _), k in zip(clouds, small_cluster_keep_np(clouds, r, lo))]
+
     def _cell_bounds(self, c, what):
         """What the device refuses for this kind of map: every cell index of the map's domain stays below 2^50."""
         if self.mode == 0:
