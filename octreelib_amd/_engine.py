@@ -1214,18 +1214,97 @@ class Forest:
             call(R, S, neighbour, label, root, n_leaves, count, mean, cov, w, v)
         return PlaneSegments(planes, neighbour, label, SegmentTable(count, mean, cov6_to_full(cov), w, v, root, n_leaves))
 
-    # -- registration (octreelib_amd/registration.py is the host definition) ------------------------------------------
+    # -- registration (octreelib_amd/registration.py is the host definition of the three systems) ---------------------
     @staticmethod
-    def _reg_args(transform, origin, max_variance, max_distance, huber_delta):
+    def _reg_args(transform, origin, max_variance=None, max_distance=None, huber_delta=None, nearest: bool = False):
+        """(transform rows, origin, max_variance, max_distance, huber_delta) as the library takes them; nearest: the
+        distance is the search radius of the two nearest-point systems (required), not own-leaf's optional gate."""
+        from octreelib_amd.query import check_nearest_args
         from octreelib_amd.registration import _as_origin, as_transform
 
+        md = check_nearest_args(1, max_distance)[1] if nearest else None
         R, t = as_transform(transform)
         T12 = np.ascontiguousarray(np.concatenate([R, t[:, None]], axis=1))
         c = np.ascontiguousarray(_as_origin(origin))
         mv = -1.0 if max_variance is None else float(max_variance)
-        md = -1.0 if max_distance is None else float(max_distance)
+        if not nearest:
+            md = -1.0 if max_distance is None else float(max_distance)
         hd = 0.0 if huber_delta is None else float(huber_delta)
         return T12, c, mv, md, hd
+
+    def _reg_system(self, c, call):
+        """The RegistrationSystem of the 28 sums and 2 counts that call(sums pointer, counts pointer), a host form of
+        the library, writes."""
+        from octreelib_amd.registration import system_from_sums
+
+        sums = np.empty(28, dtype=np.float64)
+        counts = np.empty(2, dtype=np.int64)
+        self.ctx.check(call(nat.ptr(sums), nat.ptr(counts)))
+        return system_from_sums(sums, counts, c)
+
+    @staticmethod
+    def _reg_neighbours(slot, index, d2, pose_of_slot):
+        """The (n, 1) per-point answers of a nearest-point system as query.Neighbours, the pose column named through
+        pose_of_slot (None: the slots)."""
+        from octreelib_amd.query import Neighbours
+
+        count = (slot[:, 0] >= 0).astype(np.int32)
+        if pose_of_slot is not None and slot.size:
+            names = np.asarray(list(pose_of_slot) + [-1], dtype=np.int32)   # (-1 pads index the last entry)
+            slot = names[slot]
+        return Neighbours(slot, index, d2, count)
+
+    def _align_on_device(self, points, what, prepare, system_device, accepts_device_cloud, initial, max_iterations,
+                         tolerance, damping):
+        """registration.align_np over one of the three systems: the scan is uploaded once - or, where accepted, is a
+        feed.DeviceCloud of f64 points, read where it lies - prepare() makes the map's tables once, and every
+        iteration is system_device(scan, n, T, origin, sums pointer, counts pointer) on the resident scan plus one
+        download of the 28 + 2 numbers (one host wait, whatever the size of the scan); the 6x6 solve runs on the
+        host."""
+        from octreelib_amd.query import _as_queries
+        from octreelib_amd.registration import align_np, default_origin, system_from_sums
+
+        lib, h = self.lib, self.ctx.handle
+        scan, out = C.c_void_p(), C.c_void_p()
+        resident = False
+        if accepts_device_cloud:
+            from octreelib_amd.feed import DeviceCloud
+
+            resident = isinstance(points, DeviceCloud)
+        if resident:
+            if np.dtype(points.dtype) != np.float64:
+                raise ValueError(f"{what}: a DeviceCloud of float64 points is needed (f32 queries are not supported)")
+            points.wait()
+            n, scan = len(points), points.ptr
+            pts = np.empty((n, 3), dtype=np.float64)     # (the origin of the first iteration needs the points once)
+            if n:
+                self.ctx.check(lib.octl_dev_download(h, nat.ptr(pts), scan, pts.nbytes))
+        else:
+            pts = _as_queries(points)
+            n = len(pts)
+        prepare()
+        if not resident:
+            self.ctx.check(lib.octl_dev_alloc(h, max(pts.nbytes, 8), C.byref(scan)))
+        try:
+            self.ctx.check(lib.octl_dev_alloc(h, 256, C.byref(out)))
+            if n and not resident:
+                self.ctx.check(lib.octl_dev_upload(h, scan, nat.ptr(pts), pts.nbytes))
+            counts_dptr = C.c_void_p(out.value + 28 * 8)
+            buf = np.empty(30, dtype=np.float64)
+
+            def system(T, origin):
+                if origin is None:
+                    origin = default_origin(T, pts)
+                system_device(scan, n, T, origin, out, counts_dptr)
+                self.ctx.check(lib.octl_dev_download(h, nat.ptr(buf), out, buf.nbytes))
+                return system_from_sums(buf[:28].copy(), buf[28:].view(np.int64), origin)
+
+            return align_np(system, initial, max_iterations, tolerance, damping)
+        finally:
+            if not resident:
+                lib.octl_dev_free(h, scan)    # (back to the context's pool: no hipFree on the scan path)
+            if out.value:
+                lib.octl_dev_free(h, out)
 
     def registration_system(self, points, transform=None, origin=None, slots=None, min_points: int = 8,
                             max_variance=None, max_distance=None, huber_delta=None, per_point: bool = False):
@@ -1233,7 +1312,7 @@ class Forest:
         kernels, one host wait); origin None: the centroid of the transformed scan.  per_point: the answers
         point_to_plane gives for the transformed scan come back with the system."""
         from octreelib_amd.query import _as_queries
-        from octreelib_amd.registration import default_origin, system_from_sums
+        from octreelib_amd.registration import default_origin
 
         pts = _as_queries(points)
         planes = self.leaf_planes(slots)
@@ -1241,15 +1320,12 @@ class Forest:
             origin = default_origin(transform, pts)
         T12, c, mv, md, hd = self._reg_args(transform, origin, max_variance, max_distance, huber_delta)
         n = len(pts)
-        sums = np.empty(28, dtype=np.float64)
-        counts = np.empty(2, dtype=np.int64)
         node = np.empty(n, dtype=np.int32) if per_point else None
         row = np.empty(n, dtype=np.int32) if per_point else None
         res = np.empty(n, dtype=np.float64) if per_point else None
-        self.ctx.check(self.lib.octl_forest_registration_system(
-            self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), int(min_points), mv, md, hd, nat.ptr(sums),
-            nat.ptr(counts), nat.ptr(node), nat.ptr(row), nat.ptr(res)))
-        out = system_from_sums(sums, counts, c)
+        out = self._reg_system(c, lambda sums, counts: self.lib.octl_forest_registration_system(
+            self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), int(min_points), mv, md, hd, sums, counts,
+            nat.ptr(node), nat.ptr(row), nat.ptr(res)))
         if per_point:
             out.node, out.row, out.residual, out.planes = node, row, res, planes
         return out
@@ -1266,51 +1342,15 @@ class Forest:
 
     def align(self, points, initial=None, slots=None, min_points: int = 8, max_variance=None, max_distance=None,
               huber_delta=None, max_iterations: int = 20, tolerance: float = 1e-9, damping: float = 0.0):
-        """Gauss-Newton scan-to-map alignment (registration.align_np): the pooled planes are made once, the scan is
-        uploaded once, and every iteration is the device form on the resident scan plus one download of the 28 + 2
-        numbers (two launches, one host wait, whatever the size of the scan); the 6x6 solve runs on the host."""
-        from octreelib_amd.query import _as_queries
-        from octreelib_amd.registration import align_np, default_origin, system_from_sums
-
-        pts = _as_queries(points)
-        self.leaf_planes(slots)
-        n = len(pts)
-        lib, h = self.lib, self.ctx.handle
-        scan, out = C.c_void_p(), C.c_void_p()
-        self.ctx.check(lib.octl_dev_alloc(h, max(pts.nbytes, 8), C.byref(scan)))
-        try:
-            self.ctx.check(lib.octl_dev_alloc(h, 256, C.byref(out)))
-            if n:
-                self.ctx.check(lib.octl_dev_upload(h, scan, nat.ptr(pts), pts.nbytes))
-            counts_dptr = C.c_void_p(out.value + 28 * 8)
-            buf = np.empty(30, dtype=np.float64)
-
-            def system(T, origin):
-                if origin is None:
-                    origin = default_origin(T, pts)
-                self.registration_system_device(scan, n, T, origin, out, counts_dptr, None, None, None, min_points,
-                                                max_variance, max_distance, huber_delta)
-                self.ctx.check(lib.octl_dev_download(h, nat.ptr(buf), out, buf.nbytes))
-                return system_from_sums(buf[:28].copy(), buf[28:].view(np.int64), origin)
-
-            return align_np(system, initial, max_iterations, tolerance, damping)
-        finally:
-            lib.octl_dev_free(h, scan)    # (back to the context's pool: no hipFree on the scan path)
-            if out.value:
-                lib.octl_dev_free(h, out)
+        """Gauss-Newton scan-to-map alignment (_align_on_device over registration_system_device): the pooled planes
+        are made once; an iteration is two launches and one host wait."""
+        return self._align_on_device(
+            points, "align", lambda: self.leaf_planes(slots),
+            lambda scan, n, T, origin, out, counts: self.registration_system_device(
+                scan, n, T, origin, out, counts, None, None, None, min_points, max_variance, max_distance, huber_delta),
+            False, initial, max_iterations, tolerance, damping)
 
     # -- point-to-point registration (registration.point_registration_system_np is the host definition) ---------------
-    @staticmethod
-    def _regp_args(transform, origin, max_distance, huber_delta):
-        from octreelib_amd.query import check_nearest_args
-        from octreelib_amd.registration import _as_origin, as_transform
-
-        _, r = check_nearest_args(1, max_distance)
-        R, t = as_transform(transform)
-        T12 = np.ascontiguousarray(np.concatenate([R, t[:, None]], axis=1))
-        c = np.ascontiguousarray(_as_origin(origin))
-        return T12, c, r, 0.0 if huber_delta is None else float(huber_delta)
-
     def point_registration_system(self, points, transform=None, origin=None, slots=None, max_distance=None,
                                   huber_delta=None, per_point: bool = False, pose_of_slot=None):
         """The point-to-point normal equations of a scan under `transform` against the nearest stored point of the
@@ -1318,33 +1358,26 @@ class Forest:
         the block index of the selection exists, one host wait); origin None: the centroid of the transformed scan.
         per_point: the answers nearest gives for the transformed scan with k = 1 come back with the system, the pose
         column named through pose_of_slot (None: the slots)."""
-        from octreelib_amd.query import Neighbours, _as_queries, check_nearest_args
-        from octreelib_amd.registration import default_origin, system_from_sums
+        from octreelib_amd.query import _as_queries, check_nearest_args
+        from octreelib_amd.registration import default_origin
 
         check_nearest_args(1, max_distance)
         pts = _as_queries(points)
         if origin is None:
             origin = default_origin(transform, pts)
-        T12, c, r, hd = self._regp_args(transform, origin, max_distance, huber_delta)
+        T12, c, _, r, hd = self._reg_args(transform, origin, None, max_distance, huber_delta, nearest=True)
         self.ensure_built()
         sel, n_sel, _ = self._adjust_selection(slots)
         n = len(pts)
-        sums = np.empty(28, dtype=np.float64)
-        counts = np.empty(2, dtype=np.int64)
         slot = np.full((n, 1), -1, dtype=np.int32) if per_point else None
         index = np.full((n, 1), -1, dtype=np.int64) if per_point else None
         d2 = np.full((n, 1), np.inf, dtype=np.float64) if per_point else None
         # (n = 0 still goes to the library: what it refuses whatever the scan is refused for an empty one too)
-        self.ctx.check(self.lib.octl_forest_point_registration_system(
-            self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), r, hd, nat.ptr(sel), n_sel, nat.ptr(sums),
-            nat.ptr(counts), nat.ptr(slot), nat.ptr(index), nat.ptr(d2)))
-        out = system_from_sums(sums, counts, c)
+        out = self._reg_system(c, lambda sums, counts: self.lib.octl_forest_point_registration_system(
+            self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), r, hd, nat.ptr(sel), n_sel, sums, counts,
+            nat.ptr(slot), nat.ptr(index), nat.ptr(d2)))
         if per_point:
-            count = (slot[:, 0] >= 0).astype(np.int32)
-            if pose_of_slot is not None and slot.size:
-                names = np.asarray(list(pose_of_slot) + [-1], dtype=np.int32)   # (-1 pads index the last entry)
-                slot = names[slot]
-            out.neighbours = Neighbours(slot, index, d2, count)
+            out.neighbours = self._reg_neighbours(slot, index, d2, pose_of_slot)
         return out
 
     def point_registration_system_device(self, xyz_dptr, n: int, transform, origin, sys_dptr, counts_dptr,
@@ -1352,7 +1385,7 @@ class Forest:
                                          index_dptr=None, d2_dptr=None):
         """point_registration_system for points that are in device memory already, device pointers in and out (28 f64
         and 2 i64; slot i32, index i64 and distance2 f64 per point, all three or none); the host does not wait."""
-        T12, c, r, hd = self._regp_args(transform, origin, max_distance, huber_delta)
+        T12, c, _, r, hd = self._reg_args(transform, origin, None, max_distance, huber_delta, nearest=True)
         self.ensure_built()
         sel, n_sel, _ = self._adjust_selection(slots)
         self.ctx.check(self.lib.octl_forest_point_registration_system_device(
@@ -1361,52 +1394,17 @@ class Forest:
 
     def align_points(self, points, initial=None, slots=None, max_distance=None, huber_delta=None,
                      max_iterations: int = 20, tolerance: float = 1e-9, damping: float = 0.0):
-        """Gauss-Newton scan-to-map alignment against the nearest stored points (registration.align_np over
-        point_registration_system): the block index is made once, the scan is uploaded once - or is a feed.DeviceCloud
-        of f64 points, read where it lies - and every iteration is the device form on the resident scan plus one
-        download of the 28 + 2 numbers (three launches, one host wait, whatever the size of the scan)."""
-        from octreelib_amd.feed import DeviceCloud
-        from octreelib_amd.query import _as_queries, check_nearest_args
-        from octreelib_amd.registration import align_np, default_origin, system_from_sums
+        """Gauss-Newton scan-to-map alignment against the nearest stored points (_align_on_device over
+        point_registration_system_device; `points` may be a feed.DeviceCloud of f64 points): the block index is made
+        once; an iteration is three launches and one host wait."""
+        from octreelib_amd.query import check_nearest_args
 
         check_nearest_args(1, max_distance)
-        lib, h = self.lib, self.ctx.handle
-        scan, out = C.c_void_p(), C.c_void_p()
-        resident = isinstance(points, DeviceCloud)
-        if resident:
-            if np.dtype(points.dtype) != np.float64:
-                raise ValueError("align_points: a DeviceCloud of float64 points is needed (f32 queries are not "
-                                 "supported)")
-            points.wait()
-            n, scan = len(points), points.ptr
-            pts = np.empty((n, 3), dtype=np.float64)     # (the origin of the first iteration needs the points once)
-            if n:
-                self.ctx.check(lib.octl_dev_download(h, nat.ptr(pts), scan, pts.nbytes))
-        else:
-            pts = _as_queries(points)
-            n = len(pts)
-            self.ctx.check(lib.octl_dev_alloc(h, max(pts.nbytes, 8), C.byref(scan)))
-        try:
-            self.ctx.check(lib.octl_dev_alloc(h, 256, C.byref(out)))
-            if n and not resident:
-                self.ctx.check(lib.octl_dev_upload(h, scan, nat.ptr(pts), pts.nbytes))
-            counts_dptr = C.c_void_p(out.value + 28 * 8)
-            buf = np.empty(30, dtype=np.float64)
-
-            def system(T, origin):
-                if origin is None:
-                    origin = default_origin(T, pts)
-                self.point_registration_system_device(scan, n, T, origin, out, counts_dptr, max_distance, huber_delta,
-                                                      slots)
-                self.ctx.check(lib.octl_dev_download(h, nat.ptr(buf), out, buf.nbytes))
-                return system_from_sums(buf[:28].copy(), buf[28:].view(np.int64), origin)
-
-            return align_np(system, initial, max_iterations, tolerance, damping)
-        finally:
-            if not resident:
-                lib.octl_dev_free(h, scan)    # (back to the context's pool: no hipFree on the scan path)
-            if out.value:
-                lib.octl_dev_free(h, out)
+        return self._align_on_device(
+            points, "align_points", lambda: None,
+            lambda scan, n, T, origin, out, counts: self.point_registration_system_device(
+                scan, n, T, origin, out, counts, max_distance, huber_delta, slots),
+            True, initial, max_iterations, tolerance, damping)
 
     # -- nearest-point-to-plane registration (registration.nearest_plane_registration_system_np is the definition) -----
     def nearest_plane_registration_system(self, points, transform=None, origin=None, slots=None, max_distance=None,
@@ -1418,20 +1416,17 @@ class Forest:
         host wait); origin None: the centroid of the transformed scan.  per_point: neighbours (the answers of nearest
         with k = 1 for the transformed scan, the pose column named through pose_of_slot), node, row, residual and
         planes come back with the system."""
-        from octreelib_amd.query import Neighbours, _as_queries, check_nearest_args
-        from octreelib_amd.registration import default_origin, system_from_sums
+        from octreelib_amd.query import _as_queries, check_nearest_args
+        from octreelib_amd.registration import default_origin
 
         check_nearest_args(1, max_distance)
         pts = _as_queries(points)
         if origin is None:
             origin = default_origin(transform, pts)
-        T12, c, r, hd = self._regp_args(transform, origin, max_distance, huber_delta)
+        T12, c, mv, r, hd = self._reg_args(transform, origin, max_variance, max_distance, huber_delta, nearest=True)
         planes = self.leaf_planes(slots)
         sel, n_sel, _ = self._adjust_selection(slots)
-        mv = -1.0 if max_variance is None else float(max_variance)
         n = len(pts)
-        sums = np.empty(28, dtype=np.float64)
-        counts = np.empty(2, dtype=np.int64)
         slot = np.full((n, 1), -1, dtype=np.int32) if per_point else None
         index = np.full((n, 1), -1, dtype=np.int64) if per_point else None
         d2 = np.full((n, 1), np.inf, dtype=np.float64) if per_point else None
@@ -1439,17 +1434,11 @@ class Forest:
         row = np.full(n, -1, dtype=np.int32) if per_point else None
         res = np.full(n, np.nan, dtype=np.float64) if per_point else None
         # (n = 0 still goes to the library: what it refuses whatever the scan is refused for an empty one too)
-        self.ctx.check(self.lib.octl_forest_nearest_plane_registration_system(
+        out = self._reg_system(c, lambda sums, counts: self.lib.octl_forest_nearest_plane_registration_system(
             self.handle, nat.ptr(pts), n, nat.ptr(T12), nat.ptr(c), r, hd, nat.ptr(sel), n_sel, int(min_points), mv,
-            nat.ptr(sums), nat.ptr(counts), nat.ptr(slot), nat.ptr(index), nat.ptr(d2), nat.ptr(node), nat.ptr(row),
-            nat.ptr(res)))
-        out = system_from_sums(sums, counts, c)
+            sums, counts, nat.ptr(slot), nat.ptr(index), nat.ptr(d2), nat.ptr(node), nat.ptr(row), nat.ptr(res)))
         if per_point:
-            count = (slot[:, 0] >= 0).astype(np.int32)
-            if pose_of_slot is not None and slot.size:
-                names = np.asarray(list(pose_of_slot) + [-1], dtype=np.int32)   # (-1 pads index the last entry)
-                slot = names[slot]
-            out.neighbours = Neighbours(slot, index, d2, count)
+            out.neighbours = self._reg_neighbours(slot, index, d2, pose_of_slot)
             out.node, out.row, out.residual, out.planes = node, row, res, planes
         return out
 
@@ -1460,10 +1449,9 @@ class Forest:
         """nearest_plane_registration_system against the pooled table the device holds (leaf_planes(slots) first), for
         points that are in device memory already, device pointers in and out (28 f64 and 2 i64; slot i32, index i64,
         distance2 f64, node i32, row i32 and residual f64 per point, all six or none); the host does not wait."""
-        T12, c, r, hd = self._regp_args(transform, origin, max_distance, huber_delta)
+        T12, c, mv, r, hd = self._reg_args(transform, origin, max_variance, max_distance, huber_delta, nearest=True)
         self.ensure_built()
         sel, n_sel, _ = self._adjust_selection(slots)
-        mv = -1.0 if max_variance is None else float(max_variance)
         self.ctx.check(self.lib.octl_forest_nearest_plane_registration_system_device(
             self.handle, xyz_dptr, int(n), nat.ptr(T12), nat.ptr(c), r, hd, nat.ptr(sel), n_sel, int(min_points), mv,
             sys_dptr, counts_dptr, slot_dptr, index_dptr, d2_dptr, node_dptr, row_dptr, residual_dptr))
@@ -1471,55 +1459,17 @@ class Forest:
     def align_nearest_planes(self, points, initial=None, slots=None, max_distance=None, min_points: int = 8,
                              max_variance=None, huber_delta=None, max_iterations: int = 20, tolerance: float = 1e-9,
                              damping: float = 0.0):
-        """Gauss-Newton scan-to-map alignment, nearest stored point to the plane of its leaf (registration.align_np
-        over nearest_plane_registration_system): the pooled planes and the block index are made once, the scan is
-        uploaded once - or is a feed.DeviceCloud of f64 points, read where it lies - and every iteration is the
-        device form on the resident scan plus one download of the 28 + 2 numbers (three launches, one host wait,
-        whatever the size of the scan)."""
-        from octreelib_amd.feed import DeviceCloud
-        from octreelib_amd.query import _as_queries, check_nearest_args
-        from octreelib_amd.registration import align_np, default_origin, system_from_sums
+        """Gauss-Newton scan-to-map alignment, nearest stored point to the plane of its leaf (_align_on_device over
+        nearest_plane_registration_system_device; `points` may be a feed.DeviceCloud of f64 points): the pooled planes
+        and the block index are made once; an iteration is three launches and one host wait."""
+        from octreelib_amd.query import check_nearest_args
 
         check_nearest_args(1, max_distance)
-        lib, h = self.lib, self.ctx.handle
-        scan, out = C.c_void_p(), C.c_void_p()
-        resident = isinstance(points, DeviceCloud)
-        if resident:
-            if np.dtype(points.dtype) != np.float64:
-                raise ValueError("align_nearest_planes: a DeviceCloud of float64 points is needed (f32 queries are not "
-                                 "supported)")
-            points.wait()
-            n, scan = len(points), points.ptr
-            pts = np.empty((n, 3), dtype=np.float64)     # (the origin of the first iteration needs the points once)
-            if n:
-                self.ctx.check(lib.octl_dev_download(h, nat.ptr(pts), scan, pts.nbytes))
-        else:
-            pts = _as_queries(points)
-            n = len(pts)
-        self.leaf_planes(slots)
-        if not resident:
-            self.ctx.check(lib.octl_dev_alloc(h, max(pts.nbytes, 8), C.byref(scan)))
-        try:
-            self.ctx.check(lib.octl_dev_alloc(h, 256, C.byref(out)))
-            if n and not resident:
-                self.ctx.check(lib.octl_dev_upload(h, scan, nat.ptr(pts), pts.nbytes))
-            counts_dptr = C.c_void_p(out.value + 28 * 8)
-            buf = np.empty(30, dtype=np.float64)
-
-            def system(T, origin):
-                if origin is None:
-                    origin = default_origin(T, pts)
-                self.nearest_plane_registration_system_device(scan, n, T, origin, out, counts_dptr, max_distance,
-                                                              min_points, max_variance, huber_delta, slots)
-                self.ctx.check(lib.octl_dev_download(h, nat.ptr(buf), out, buf.nbytes))
-                return system_from_sums(buf[:28].copy(), buf[28:].view(np.int64), origin)
-
-            return align_np(system, initial, max_iterations, tolerance, damping)
-        finally:
-            if not resident:
-                lib.octl_dev_free(h, scan)    # (back to the context's pool: no hipFree on the scan path)
-            if out.value:
-                lib.octl_dev_free(h, out)
+        return self._align_on_device(
+            points, "align_nearest_planes", lambda: self.leaf_planes(slots),
+            lambda scan, n, T, origin, out, counts: self.nearest_plane_registration_system_device(
+                scan, n, T, origin, out, counts, max_distance, min_points, max_variance, huber_delta, slots),
+            True, initial, max_iterations, tolerance, damping)
 
     # -- plane adjustment (octreelib_amd/adjustment.py is the host definition) ---------------------------------------------
     def _adjust_selection(self, slots):

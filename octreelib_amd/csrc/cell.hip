@@ -83,8 +83,7 @@ __global__ __launch_bounds__(256) void k_thin_mask(const uint32_t* __restrict__ 
 int launch_cell_count(octl_ctx* ctx, const double* xyz_dev, int64_t n, double cell, int32_t cap, const NNTables& T,
                       int32_t* count) {
   KTimer timer(ctx, "cell_count");
-  const unsigned wgs =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+  const unsigned wgs = grid_stride_for(ctx, n);
   OCTL_LAUNCH(k_cell_count, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, cell, cap, T, count);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;

@@ -411,6 +411,12 @@ static inline hipError_t octl_download(octl_ctx* ctx, T* dst, DevBuf& src, Carve
 // (uint32) is written there.  n up to 2^31.
 // compute units of the context's device (cached)
 int octl_ctx_cus(octl_ctx* ctx);
+// workgroups of 256 threads for n items taken grid-stride, one item per lane and pass: grid_for(n), at least one and at
+// most 16 per compute unit
+static inline unsigned grid_stride_for(octl_ctx* ctx, int64_t n) {
+  const int64_t most = (int64_t)octl_ctx_cus(ctx) * 16, all = ceil_div(n, 256), wgs = all < most ? all : most;
+  return (unsigned)(wgs > 1 ? wgs : 1);
+}
 // the side stream and its two events, created on first use; false when they cannot be had (not an error: the
 // caller uses the context's stream)
 bool octl_ctx_side_stream(octl_ctx* ctx);

@@ -36,8 +36,7 @@ __global__ __launch_bounds__(256) void k_ray_evidence(const double* __restrict__
 int launch_evidence(octl_ctx* ctx, const double* org, const double* dir, const double* t_min, const double* t_free,
                     const double* t_end, int64_t n, const EvidenceTables& T) {
   KTimer timer(ctx, "ray_evidence");
-  const unsigned wgs =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+  const unsigned wgs = grid_stride_for(ctx, n);
   OCTL_LAUNCH(k_ray_evidence, dim3(wgs), dim3(256), 0, ctx->stream, org, dir, t_min, t_free, t_end, n, T);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;

@@ -138,7 +138,7 @@ struct octl_forest {
   int64_t pl_n = 0, pl_cap = 0;
   std::vector<uint8_t> pl_sel;
   DevBuf q_stage;               // staging of the host forms of the queries (points in, answers out)
-  DevBuf rg_rows;               // octl_forest_registration_system (register.hip): per-chunk partial sums, the result
+  DevBuf rg_rows;               // the three registration systems (reg_driver.h: reg_scratch): result, rows, records
 
   // octl_forest_adjustment_system (adjust.hip), prepared once per map and pose selection:
   //  adj_tab   the selected (leaf, pose) blocks in (node, slot) order - 80-byte moments {n, sum d, sum d d^T} about the

@@ -97,8 +97,7 @@ struct MomentStage {
 int launch_neighbourhood_stats(octl_ctx* ctx, const double* xyz_dev, int64_t n, double r, const NNTables& T,
                                const MomentRows& out) {
   KTimer timer(ctx, "neighbourhood_stats");
-  const unsigned wgs =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+  const unsigned wgs = grid_stride_for(ctx, n);
   OCTL_LAUNCH(k_neighbourhood_stats, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, r, r * r, T, out);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;

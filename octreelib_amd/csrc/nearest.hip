@@ -90,8 +90,7 @@ void launch_instance(octl_ctx* ctx, unsigned wgs, const double* xyz_dev, int64_t
 int launch_nearest(octl_ctx* ctx, const double* xyz_dev, int64_t n, int k, double r, const NNTables& T, int32_t* slot,
                    int64_t* index, double* d2, int32_t* count) {
   KTimer timer(ctx, k <= 1 ? "nearest_k1" : k <= 2 ? "nearest_k2" : k <= 4 ? "nearest_k4" : "nearest_k8");
-  const unsigned wgs =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+  const unsigned wgs = grid_stride_for(ctx, n);
   const double r2 = r * r;
   // (a request rounds up to the next instance and writes its first k columns)
   if (k <= 1) launch_instance<1>(ctx, wgs, xyz_dev, n, k, r, r2, T, slot, index, d2, count);

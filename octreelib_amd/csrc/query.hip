@@ -44,8 +44,7 @@ template <bool PLANE>
 int launch_query(octl_ctx* ctx, const char* name, const double* xyz_dev, int64_t n, const QueryTables& t,
                  const PlaneTable& pt, int32_t* node, int32_t* row, double* dist) {
   KTimer timer(ctx, name);
-  const int64_t wgs = std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
-  OCTL_LAUNCH(k_query<PLANE>, dim3((unsigned)wgs), dim3(256), 0, ctx->stream, xyz_dev, n, t, pt, node, row, dist);
+  OCTL_LAUNCH(k_query<PLANE>, dim3(grid_stride_for(ctx, n)), dim3(256), 0, ctx->stream, xyz_dev, n, t, pt, node, row, dist);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;
 }

@@ -95,8 +95,7 @@ int radius_count_begin(octl_forest* f, int64_t n, double radius, int32_t max_cou
 int launch_radius_count(octl_ctx* ctx, const double* xyz_dev, int64_t n, double r, int32_t cap, const NNTables& T,
                         int32_t* count) {
   KTimer timer(ctx, "radius_count");
-  const unsigned wgs =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+  const unsigned wgs = grid_stride_for(ctx, n);
   OCTL_LAUNCH(k_radius_count, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, r, r * r, cap, T, count);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;

@@ -43,8 +43,7 @@ template <bool PLANE>
 int launch_raycast(octl_ctx* ctx, const double* org, const double* dir, const double* t_min, const double* t_max,
                    int64_t n, const RayTables& T, int32_t* node, double* t, int32_t* row) {
   KTimer timer(ctx, PLANE ? "raycast_plane" : "raycast_cube");
-  const unsigned wgs =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
+  const unsigned wgs = grid_stride_for(ctx, n);
   OCTL_LAUNCH(k_raycast<PLANE>, dim3(wgs), dim3(256), 0, ctx->stream, org, dir, t_min, t_max, n, T, node, t, row);
   HIP_TRY(ctx, hipGetLastError());
   return OCTL_OK;

@@ -1,9 +1,18 @@
-// The second half of the registration reductions: the chunk size of the first half and k_reg_fold, which folds the
-// rows of per-chunk sums into the 28 + 2 numbers of a call.  Shared by register.hip (point-to-plane, k_reg_partial)
-// and register_points.hip (point-to-point, k_regp_partial): one tree, a function of n alone (register.hip has the
-// count of additions).
+// What the kernels of the three registration systems share beside the arithmetic of a term: the transform of a query,
+// the chunk size of the first half of the reduction and k_reg_fold, the second half, which folds the rows of per-chunk
+// sums into the 28 + 2 numbers of a call.  Shared by register.hip (k_reg_partial), register_points.hip (k_regp_partial)
+// and register_nearest_plane.hip (k_regn_partial): one tree, a function of n alone (register.hip has the count of
+// additions).
 #pragma once
 #include "sums28.h"
+
+__device__ __forceinline__ void reg_transform(const double* __restrict__ T, double qx, double qy, double qz,
+                                              double p[3]) {
+  // (separate products and sums: the library is built with -ffp-contract=off, and the host forms the same bits)
+  p[0] = ((T[0] * qx + T[1] * qy) + T[2] * qz) + T[3];
+  p[1] = ((T[4] * qx + T[5] * qy) + T[6] * qz) + T[7];
+  p[2] = ((T[8] * qx + T[9] * qy) + T[10] * qz) + T[11];
+}
 
 namespace {
 

@@ -26,15 +26,13 @@
 //                  query streamed;
 //   k_reg_fold     as it is (reg_fold.h).
 // The tree is a function of n alone: no floating-point atomics, nothing sized by the CU count (the grid of k_regn_match
-// is, and it adds nothing).  The host form adds one upload, the 240-byte download through the pinned mirror and ONE
-// host wait; the device form does not wait.  LDS: 960 bytes (k_regn_partial, k_reg_fold), none in k_regn_match.
-#include <algorithm>
-#include <cmath>
-
+// is, and it adds nothing).  The host and the device form around the launches: reg_driver.h.  LDS: 960 bytes
+// (k_regn_partial, k_reg_fold), none in k_regn_match.
 #include "common.h"
 #include "forest.h"
 #include "nearest_walk.h"
 #include "reg_best.h"
+#include "reg_driver.h"
 #include "reg_fold.h"
 #include "reg_plane_term.h"
 
@@ -107,12 +105,7 @@ __global__ __launch_bounds__(256) void k_regn_partial(const double* __restrict__
     reg_plane_term(p[0], p[1], p[2], P.c, nrm, m.w, ar, P.delta, a.s);
   }
   reg_block_reduce(a, lds, ldc);
-  double* out = rows + (int64_t)blockIdx.x * RS_ROW;
-  if (threadIdx.x < RS_SUMS) out[threadIdx.x] = a.s[0];
-  if (threadIdx.x == 0) {
-    reinterpret_cast<long long*>(out)[RS_SUMS] = a.used;
-    reinterpret_cast<long long*>(out)[RS_SUMS + 1] = a.located;
-  }
+  reg_write_row(a, rows);
 }
 
 struct RegNCall {
@@ -135,17 +128,12 @@ bool same_selection(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b
 // system's, then that planes and points come from the same poses; the block index is made last
 int regn_begin(octl_forest* f, const void* xyz, int64_t n, const double* T, const double* origin, int32_t min_points,
                double max_variance, double max_distance, double huber_delta, const uint8_t* slot_sel, int32_t n_sel,
-               const void* sys, const void* counts, const void* const per_point[6], RegNCall* c) {
-  int given = 0;
-  for (int k = 0; k < 6; ++k) given += per_point[k] ? 1 : 0;
-  const bool pointers_ok = (n <= 0 || xyz) && T && origin && sys && counts && (given == 0 || given == 6);
+               const void* sys, const void* counts, bool columns_ok, RegNCall* c) {
+  const bool pointers_ok = (n <= 0 || xyz) && T && origin && sys && counts && columns_ok;
   octl_ctx* ctx = f->ctx;
   // (nearest_begin ends by making the block index; with n = 0 it stops after its refusals, so the count is tested here)
   OCTL_TRY(nearest_begin(f, WHAT, 0, 1, max_distance, slot_sel, n_sel, pointers_ok && !query_bad_count(n), &c->T));
-  for (int k = 0; k < 12; ++k)
-    if (!std::isfinite(T[k])) return octl_set_error(ctx, OCTL_E_INVALID, "%s: the transform is not finite", WHAT);
-  for (int k = 0; k < 3; ++k)
-    if (!std::isfinite(origin[k])) return octl_set_error(ctx, OCTL_E_INVALID, "%s: the origin is not finite", WHAT);
+  OCTL_TRY(reg_check_transform(ctx, WHAT, T, origin));
   OCTL_TRY(query_plane_table(f, WHAT, min_points, max_variance, &c->pt));
   std::vector<uint8_t> sel;
   OCTL_TRY(forest_selection(f, slot_sel, n_sel, &sel));
@@ -162,58 +150,33 @@ int regn_begin(octl_forest* f, const void* xyz, int64_t n, const double* T, cons
   return OCTL_OK;
 }
 
-// scratch of one call in f->rg_rows, laid out as register_points.hip lays it out: [0, 256) the result (28 sums, 2
-// counts), the rows, then the records
-struct RegNScratch {
-  double *result, *rows;
-  double4* rec;
-};
-
-int regn_scratch(octl_forest* f, int64_t n, RegNScratch* s) {
-  const size_t rows_bytes = (size_t)ceil_div(n, RS_CHUNK) * RS_ROW * 8;
-  OCTL_TRY(devbuf_reserve(f->ctx, f->rg_rows, 256 + rows_bytes + (size_t)n * 32));
-  char* base = static_cast<char*>(f->rg_rows.p);
-  s->result = reinterpret_cast<double*>(base);
-  s->rows = reinterpret_cast<double*>(base + 256);
-  s->rec = reinterpret_cast<double4*>(base + 256 + rows_bytes);
-  return OCTL_OK;
-}
-
-struct RegNPerPoint {
-  int32_t* slot;
-  int64_t* index;
-  double* distance2;
-  int32_t *node, *row;
-  double* residual;
-};
-
-// the three kernels
-int regn_launch(octl_ctx* ctx, const RegNCall& c, const double* xyz_dev, int64_t n, const RegNScratch& s,
-                const RegNPerPoint& o, double* sys_dev, int64_t* counts_dev) {
-  const int64_t n_rows = ceil_div(n, RS_CHUNK);
-  const double r2 = c.r * c.r;
-  {
-    KTimer timer(ctx, "regn_match");
-    const unsigned wgs =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
-    if (o.slot)
-      OCTL_LAUNCH(k_regn_match<true>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, c.pt, s.rec,
-                  o.slot, o.index, o.distance2, o.node, o.row, o.residual);
-    else
-      OCTL_LAUNCH(k_regn_match<false>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, c.pt, s.rec,
-                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  {
-    KTimer timer(ctx, "regn_partial");
-    OCTL_LAUNCH(k_regn_partial, dim3((unsigned)n_rows), dim3(256), 0, ctx->stream, xyz_dev, n, c.P,
-                (const double4*)s.rec, s.rows);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  KTimer timer(ctx, "reg_fold");
-  OCTL_LAUNCH(k_reg_fold, dim3(1), dim3(256), 0, ctx->stream, (const double*)s.rows, n_rows, sys_dev, counts_dev);
-  HIP_TRY(ctx, hipGetLastError());
-  return OCTL_OK;
+// the three kernels of a call, as the forms of reg_driver.h enqueue them; columns: slot, index, distance2, node, row,
+// residual
+auto regn_kernels(octl_ctx* ctx, const RegNCall& c, int64_t n) {
+  return [ctx, &c, n](const double* xyz_dev, void* const* col, const RegScratch& s, double* sys_dev,
+                      int64_t* counts_dev) -> int {
+    const int64_t n_rows = ceil_div(n, RS_CHUNK);
+    const double r2 = c.r * c.r;
+    {
+      KTimer timer(ctx, "regn_match");
+      const unsigned wgs = grid_stride_for(ctx, n);
+      if (col[0])
+        OCTL_LAUNCH(k_regn_match<true>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, c.pt,
+                    s.rec, (int32_t*)col[0], (int64_t*)col[1], (double*)col[2], (int32_t*)col[3], (int32_t*)col[4],
+                    (double*)col[5]);
+      else
+        OCTL_LAUNCH(k_regn_match<false>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, c.pt,
+                    s.rec, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+      KTimer timer(ctx, "regn_partial");
+      OCTL_LAUNCH(k_regn_partial, dim3((unsigned)n_rows), dim3(256), 0, ctx->stream, xyz_dev, n, c.P,
+                  (const double4*)s.rec, s.rows);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    return reg_fold_launch(ctx, s.rows, n_rows, sys_dev, counts_dev);
+  };
 }
 
 }  // namespace
@@ -228,53 +191,10 @@ int octl_forest_nearest_plane_registration_system(octl_forest* f, const double* 
                                                   int32_t* row, double* residual) {
   if (!f) return OCTL_E_INVALID;
   RegNCall c;
-  const void* const per_point[6] = {slot, index, distance2, node, row, residual};
+  const RegColumn cols[] = {{slot, 4}, {index, 8}, {distance2, 8}, {node, 4}, {row, 4}, {residual, 8}};
   OCTL_TRY(regn_begin(f, xyz, n, T, origin, min_points, max_variance, max_distance, huber_delta, slot_sel, n_sel, sys,
-                      counts, per_point, &c));
-  if (n == 0) {
-    for (int k = 0; k < RS_SUMS; ++k) sys[k] = 0.0;
-    counts[0] = counts[1] = 0;
-    return OCTL_OK;
-  }
-  octl_ctx* ctx = f->ctx;
-  hipStream_t st = ctx->stream;
-  Carve plan;  // f->q_stage: [queries 3 f64 | index i64 | d2 f64 | residual f64 | slot i32 | node i32 | row i32]
-  const auto q_part = plan.add<double>((size_t)n * 3);
-  const size_t q_only = plan.total;
-  const auto idx_part = plan.add<int64_t>((size_t)n);
-  const auto d2_part = plan.add<double>((size_t)n);
-  const auto res_part = plan.add<double>((size_t)n);
-  const auto slot_part = plan.add<int32_t>((size_t)n);
-  const auto node_part = plan.add<int32_t>((size_t)n);
-  const auto row_part = plan.add<int32_t>((size_t)n);
-  OCTL_TRY(devbuf_reserve(ctx, f->q_stage, slot ? plan.total : q_only));
-  RegNScratch s;
-  OCTL_TRY(regn_scratch(f, n, &s));
-  double* q_d = Carve::at(f->q_stage, q_part);
-  RegNPerPoint o = {};
-  if (slot) {
-    o.slot = Carve::at(f->q_stage, slot_part);
-    o.index = Carve::at(f->q_stage, idx_part);
-    o.distance2 = Carve::at(f->q_stage, d2_part);
-    o.node = Carve::at(f->q_stage, node_part);
-    o.row = Carve::at(f->q_stage, row_part);
-    o.residual = Carve::at(f->q_stage, res_part);
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(q_d, xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
-  OCTL_TRY(regn_launch(ctx, c, q_d, n, s, o, s.result, reinterpret_cast<int64_t*>(s.result + RS_SUMS)));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, s.result, (RS_SUMS + 2) * 8, hipMemcpyDeviceToHost, st));
-  if (slot) {
-    HIP_TRY(ctx, hipMemcpyAsync(slot, o.slot, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(index, o.index, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(distance2, o.distance2, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(node, o.node, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(row, o.row, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(residual, o.residual, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  std::memcpy(sys, ctx->small_host, RS_SUMS * 8);
-  std::memcpy(counts, static_cast<const char*>(ctx->small_host) + RS_SUMS * 8, 16);
-  return OCTL_OK;
+                      counts, reg_columns_ok(cols), &c));
+  return reg_host_form(f, xyz, n, true, cols, sys, counts, regn_kernels(f->ctx, c, n));
 }
 
 int octl_forest_nearest_plane_registration_system_device(octl_forest* f, const double* xyz_dev, int64_t n,
@@ -286,20 +206,11 @@ int octl_forest_nearest_plane_registration_system_device(octl_forest* f, const d
                                                          int32_t* node_dev, int32_t* row_dev, double* residual_dev) {
   if (!f) return OCTL_E_INVALID;
   RegNCall c;
-  const void* const per_point[6] = {slot_dev, index_dev, distance2_dev, node_dev, row_dev, residual_dev};
+  const RegColumn cols[] = {{slot_dev, 4},     {index_dev, 8}, {distance2_dev, 8},
+                            {node_dev, 4},     {row_dev, 4},   {residual_dev, 8}};
   OCTL_TRY(regn_begin(f, xyz_dev, n, T, origin, min_points, max_variance, max_distance, huber_delta, slot_sel, n_sel,
-                      sys_dev, counts_dev, per_point, &c));
-  octl_ctx* ctx = f->ctx;
-  if (n == 0) {  // (nothing to reduce: the zeros are two fills in stream order)
-    HIP_TRY(ctx, hipMemsetAsync(sys_dev, 0, RS_SUMS * 8, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(counts_dev, 0, 16, ctx->stream));
-    return OCTL_OK;
-  }
-  RegNScratch s;
-  OCTL_TRY(regn_scratch(f, n, &s));
-  OCTL_TRY(ctx_wait_uploads(ctx, xyz_dev, (size_t)n * 24));
-  const RegNPerPoint o = {slot_dev, index_dev, distance2_dev, node_dev, row_dev, residual_dev};
-  return regn_launch(ctx, c, xyz_dev, n, s, o, sys_dev, counts_dev);
+                      sys_dev, counts_dev, reg_columns_ok(cols), &c));
+  return reg_device_form(f, xyz_dev, n, true, cols, sys_dev, counts_dev, regn_kernels(f->ctx, c, n));
 }
 
 }  // extern "C"

@@ -19,15 +19,13 @@
 //                  copies and sign changes, reg_block_reduce, row k.  No walk: 56 bytes per query streamed;
 //   k_reg_fold     as it is (reg_fold.h).
 // The tree is a function of n alone: no floating-point atomics, nothing sized by the CU count (the grid of k_reg_match
-// is, and it adds nothing).  The host form adds one upload, the 240-byte download through the pinned mirror and ONE
-// host wait; the device form does not wait.  LDS: 960 bytes (k_regp_partial, k_reg_fold), none in k_reg_match.
-#include <algorithm>
-#include <cmath>
-
+// is, and it adds nothing).  The host and the device form around the launches: reg_driver.h.  LDS: 960 bytes
+// (k_regp_partial, k_reg_fold), none in k_reg_match.
 #include "common.h"
 #include "forest.h"
 #include "nearest_walk.h"
 #include "reg_best.h"
+#include "reg_driver.h"
 #include "reg_fold.h"
 #include "reg_point_term.h"
 
@@ -40,7 +38,7 @@ struct RegPointParams {
   double delta2;
 };
 
-// (RegBest, the k = 1 sink, and reg_transform: reg_best.h - register_nearest_plane.hip matches with the same)
+// (RegBest, the k = 1 sink: reg_best.h; reg_transform: reg_fold.h - register_nearest_plane.hip matches with the same)
 
 template <bool PER_POINT>
 __global__ __launch_bounds__(256) void k_reg_match(const double* __restrict__ xyz, int64_t n, RegPointParams P, double r,
@@ -98,12 +96,7 @@ __global__ __launch_bounds__(256) void k_regp_partial(const double* __restrict__
   a.used = used;
   a.located = located;
   reg_block_reduce(a, lds, ldc);
-  double* out = rows + (int64_t)blockIdx.x * RS_ROW;
-  if (threadIdx.x < RS_SUMS) out[threadIdx.x] = a.s[0];
-  if (threadIdx.x == 0) {
-    reinterpret_cast<long long*>(out)[RS_SUMS] = a.used;
-    reinterpret_cast<long long*>(out)[RS_SUMS + 1] = a.located;
-  }
+  reg_write_row(a, rows);
 }
 
 struct RegPointCall {
@@ -117,18 +110,12 @@ const char* const WHAT = "point_registration_system";
 // the checks every form starts with (nothing has run when one of them fails): the search's, then the system's
 int regp_begin(octl_forest* f, const void* xyz, int64_t n, const double* T, const double* origin, double max_distance,
                double huber_delta, const uint8_t* slot_sel, int32_t n_sel, const void* sys, const void* counts,
-               const void* slot, const void* index, const void* distance2, RegPointCall* c) {
-  const int per_point = (slot ? 1 : 0) + (index ? 1 : 0) + (distance2 ? 1 : 0);
-  const bool pointers_ok = (n <= 0 || xyz) && T && origin && sys && counts && (per_point == 0 || per_point == 3);
+               bool columns_ok, RegPointCall* c) {
+  const bool pointers_ok = (n <= 0 || xyz) && T && origin && sys && counts && columns_ok;
   octl_ctx* ctx = f->ctx;
   // (nearest_begin ends by making the block index: what the system refuses comes first.  Before build, and with
   //  pointers missing, nearest_begin itself refuses - state, then arguments)
-  if (f->built && pointers_ok) {
-    for (int k = 0; k < 12; ++k)
-      if (!std::isfinite(T[k])) return octl_set_error(ctx, OCTL_E_INVALID, "%s: the transform is not finite", WHAT);
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(origin[k])) return octl_set_error(ctx, OCTL_E_INVALID, "%s: the origin is not finite", WHAT);
-  }
+  if (f->built && pointers_ok) OCTL_TRY(reg_check_transform(ctx, WHAT, T, origin));
   OCTL_TRY(nearest_begin(f, WHAT, n, 1, max_distance, slot_sel, n_sel, pointers_ok, &c->T));
   std::memcpy(c->P.T, T, sizeof c->P.T);
   std::memcpy(c->P.c, origin, sizeof c->P.c);
@@ -138,49 +125,31 @@ int regp_begin(octl_forest* f, const void* xyz, int64_t n, const double* T, cons
   return OCTL_OK;
 }
 
-// scratch of one call in f->rg_rows: [0, 256) the result (28 sums, 2 counts), the rows, then the records
-struct RegPointScratch {
-  double *result, *rows;
-  double4* rec;
-};
-
-int regp_scratch(octl_forest* f, int64_t n, RegPointScratch* s) {
-  const size_t rows_bytes = (size_t)ceil_div(n, RS_CHUNK) * RS_ROW * 8;
-  OCTL_TRY(devbuf_reserve(f->ctx, f->rg_rows, 256 + rows_bytes + (size_t)n * 32));
-  char* base = static_cast<char*>(f->rg_rows.p);
-  s->result = reinterpret_cast<double*>(base);
-  s->rows = reinterpret_cast<double*>(base + 256);
-  s->rec = reinterpret_cast<double4*>(base + 256 + rows_bytes);
-  return OCTL_OK;
-}
-
-// the three kernels
-int regp_launch(octl_ctx* ctx, const RegPointCall& c, const double* xyz_dev, int64_t n, const RegPointScratch& s,
-                int32_t* slot, int64_t* index, double* distance2, double* sys_dev, int64_t* counts_dev) {
-  const int64_t n_rows = ceil_div(n, RS_CHUNK);
-  const double r2 = c.r * c.r;
-  {
-    KTimer timer(ctx, "reg_match");
-    const unsigned wgs =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), (int64_t)octl_ctx_cus(ctx) * 16));
-    if (slot)
-      OCTL_LAUNCH(k_reg_match<true>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, s.rec, slot,
-                  index, distance2);
-    else
-      OCTL_LAUNCH(k_reg_match<false>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, s.rec,
-                  nullptr, nullptr, nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  {
-    KTimer timer(ctx, "regp_partial");
-    OCTL_LAUNCH(k_regp_partial, dim3((unsigned)n_rows), dim3(256), 0, ctx->stream, xyz_dev, n, c.P,
-                (const double4*)s.rec, s.rows);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  KTimer timer(ctx, "reg_fold");
-  OCTL_LAUNCH(k_reg_fold, dim3(1), dim3(256), 0, ctx->stream, (const double*)s.rows, n_rows, sys_dev, counts_dev);
-  HIP_TRY(ctx, hipGetLastError());
-  return OCTL_OK;
+// the three kernels of a call, as the forms of reg_driver.h enqueue them; columns: slot, index, distance2
+auto regp_kernels(octl_ctx* ctx, const RegPointCall& c, int64_t n) {
+  return [ctx, &c, n](const double* xyz_dev, void* const* col, const RegScratch& s, double* sys_dev,
+                      int64_t* counts_dev) -> int {
+    const int64_t n_rows = ceil_div(n, RS_CHUNK);
+    const double r2 = c.r * c.r;
+    {
+      KTimer timer(ctx, "reg_match");
+      const unsigned wgs = grid_stride_for(ctx, n);
+      if (col[0])
+        OCTL_LAUNCH(k_reg_match<true>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, s.rec,
+                    (int32_t*)col[0], (int64_t*)col[1], (double*)col[2]);
+      else
+        OCTL_LAUNCH(k_reg_match<false>, dim3(wgs), dim3(256), 0, ctx->stream, xyz_dev, n, c.P, c.r, r2, c.T, s.rec,
+                    nullptr, nullptr, nullptr);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+      KTimer timer(ctx, "regp_partial");
+      OCTL_LAUNCH(k_regp_partial, dim3((unsigned)n_rows), dim3(256), 0, ctx->stream, xyz_dev, n, c.P,
+                  (const double4*)s.rec, s.rows);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    return reg_fold_launch(ctx, s.rows, n_rows, sys_dev, counts_dev);
+  };
 }
 
 }  // namespace
@@ -193,41 +162,10 @@ int octl_forest_point_registration_system(octl_forest* f, const double* xyz, int
                                           int32_t* slot, int64_t* index, double* distance2) {
   if (!f) return OCTL_E_INVALID;
   RegPointCall c;
-  OCTL_TRY(regp_begin(f, xyz, n, T, origin, max_distance, huber_delta, slot_sel, n_sel, sys, counts, slot, index,
-                      distance2, &c));
-  if (n == 0) {
-    for (int k = 0; k < RS_SUMS; ++k) sys[k] = 0.0;
-    counts[0] = counts[1] = 0;
-    return OCTL_OK;
-  }
-  octl_ctx* ctx = f->ctx;
-  hipStream_t st = ctx->stream;
-  Carve plan;  // f->q_stage: [queries 3 f64 | index i64 | d2 f64 | slot i32]
-  const auto q_part = plan.add<double>((size_t)n * 3);
-  const size_t q_only = plan.total;
-  const auto idx_part = plan.add<int64_t>((size_t)n);
-  const auto d2_part = plan.add<double>((size_t)n);
-  const auto slot_part = plan.add<int32_t>((size_t)n);
-  OCTL_TRY(devbuf_reserve(ctx, f->q_stage, slot ? plan.total : q_only));
-  RegPointScratch s;
-  OCTL_TRY(regp_scratch(f, n, &s));
-  double* q_d = Carve::at(f->q_stage, q_part);
-  int64_t* idx_d = slot ? Carve::at(f->q_stage, idx_part) : nullptr;
-  double* d2_d = slot ? Carve::at(f->q_stage, d2_part) : nullptr;
-  int32_t* slot_d = slot ? Carve::at(f->q_stage, slot_part) : nullptr;
-  HIP_TRY(ctx, hipMemcpyAsync(q_d, xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
-  OCTL_TRY(regp_launch(ctx, c, q_d, n, s, slot_d, idx_d, d2_d, s.result,
-                       reinterpret_cast<int64_t*>(s.result + RS_SUMS)));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->small_host, s.result, (RS_SUMS + 2) * 8, hipMemcpyDeviceToHost, st));
-  if (slot) {
-    HIP_TRY(ctx, hipMemcpyAsync(slot, slot_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(index, idx_d, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(distance2, d2_d, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  std::memcpy(sys, ctx->small_host, RS_SUMS * 8);
-  std::memcpy(counts, static_cast<const char*>(ctx->small_host) + RS_SUMS * 8, 16);
-  return OCTL_OK;
+  const RegColumn cols[] = {{slot, 4}, {index, 8}, {distance2, 8}};
+  OCTL_TRY(regp_begin(f, xyz, n, T, origin, max_distance, huber_delta, slot_sel, n_sel, sys, counts,
+                      reg_columns_ok(cols), &c));
+  return reg_host_form(f, xyz, n, true, cols, sys, counts, regp_kernels(f->ctx, c, n));
 }
 
 int octl_forest_point_registration_system_device(octl_forest* f, const double* xyz_dev, int64_t n, const double T[12],
@@ -237,18 +175,10 @@ int octl_forest_point_registration_system_device(octl_forest* f, const double* x
                                                  double* distance2_dev) {
   if (!f) return OCTL_E_INVALID;
   RegPointCall c;
+  const RegColumn cols[] = {{slot_dev, 4}, {index_dev, 8}, {distance2_dev, 8}};
   OCTL_TRY(regp_begin(f, xyz_dev, n, T, origin, max_distance, huber_delta, slot_sel, n_sel, sys_dev, counts_dev,
-                      slot_dev, index_dev, distance2_dev, &c));
-  octl_ctx* ctx = f->ctx;
-  if (n == 0) {  // (nothing to reduce: the zeros are two fills in stream order)
-    HIP_TRY(ctx, hipMemsetAsync(sys_dev, 0, RS_SUMS * 8, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(counts_dev, 0, 16, ctx->stream));
-    return OCTL_OK;
-  }
-  RegPointScratch s;
-  OCTL_TRY(regp_scratch(f, n, &s));
-  OCTL_TRY(ctx_wait_uploads(ctx, xyz_dev, (size_t)n * 24));
-  return regp_launch(ctx, c, xyz_dev, n, s, slot_dev, index_dev, distance2_dev, sys_dev, counts_dev);
+                      reg_columns_ok(cols), &c));
+  return reg_device_form(f, xyz_dev, n, true, cols, sys_dev, counts_dev, regp_kernels(f->ctx, c, n));
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // The 28 sums + 2 counts of a 6x6 point-to-plane system and their reduction over a workgroup of 256: shared by
-// register.hip (k_reg_partial), register_points.hip (k_regp_partial), reg_fold.h (k_reg_fold) and adjust.hip
-// (k_adj_partial / k_adj_fold) - one fixed tree.
+// register.hip (k_reg_partial), register_points.hip (k_regp_partial), register_nearest_plane.hip (k_regn_partial),
+// reg_fold.h (k_reg_fold) and adjust.hip (k_adj_partial / k_adj_fold) - one fixed tree.
 #pragma once
 #include "common.h"
 
@@ -42,6 +42,16 @@ __device__ __forceinline__ void reg_block_reduce(RegAcc& a, double (*lds)[RS_SUM
   if (tid == 0) {
     a.used = ldc[0][0] + ldc[1][0] + ldc[2][0] + ldc[3][0];
     a.located = ldc[0][1] + ldc[1][1] + ldc[2][1] + ldc[3][1];
+  }
+}
+
+// what reg_block_reduce left, into the scratch row of this workgroup (the epilogue of the three *_partial kernels)
+__device__ __forceinline__ void reg_write_row(const RegAcc& a, double* __restrict__ rows) {
+  double* out = rows + (int64_t)blockIdx.x * RS_ROW;
+  if (threadIdx.x < RS_SUMS) out[threadIdx.x] = a.s[0];
+  if (threadIdx.x == 0) {
+    reinterpret_cast<long long*>(out)[RS_SUMS] = a.used;
+    reinterpret_cast<long long*>(out)[RS_SUMS + 1] = a.located;
   }
 }
 

@@ -32,8 +32,10 @@ from tests.test_cpu_nearest import lattice_case
 from tests.test_cpu_nearest_plane_registration import (GAP_LEAF, GAP_R, assert_gap_geometry, gap_scene)
 from tests.test_cpu_point_registration import sums28
 from tests.test_gpu_point_registration import (FIELDS, T_SMALL, _assert_neighbours, _grid, _names, _same_bits)
+from tests.test_gpu_point_registration import _device_form as _point_device_form
 from tests.test_gpu_query import BAD, _counter, _DevBuf
 from tests.test_gpu_registration import _abs_term_sums, _depth_bound
+from tests.test_gpu_registration import _device_form as _own_leaf_device_form
 
 pytestmark = pytest.mark.gpu
 
@@ -598,3 +600,53 @@ def test_other_queries_are_untouched():
     align_nearest_planes(g, Q[:-len(BAD)], max_distance=0.2, max_iterations=2)
     after, launches_after = snapshot()
     assert after == before and launches_after == launches_before
+
+
+# ---- test 8: one driver, three layouts -----------------------------------------------------------------------------------
+def test_three_systems_take_turns_on_one_map():
+    """The three systems go through one host driver and lay out the same two buffers of the map differently: the
+    staging of the host forms holds 0, 3 or 6 per-point columns behind the queries, the scratch holds records or none.
+    Called in rotation on ONE map - both forms, with and without the per-point answers, at n = 257 (a second pass of
+    the lanes), then 4097 (a second chunk row), then 1 (a call that shrinks after the buffers grew) - every answer has
+    the bits the same call gives on a fresh map of the same contents: the 28 sums, the 2 counts and every per-point
+    column.  No tolerance."""
+    _, clouds, _, Q, T, c = _planar_grid()
+    r, delta = 0.2, 0.01
+
+    def host(f, system, Qn, per_point):
+        if system == "own leaf":
+            s = f.registration_system(Qn, T, origin=c, max_distance=r, huber_delta=delta, per_point=per_point)
+            cols = [s.node, s.row, s.residual]
+        elif system == "point":
+            s = f.point_registration_system(Qn, T, origin=c, max_distance=r, huber_delta=delta, per_point=per_point)
+            cols = [getattr(s.neighbours, k) for k in FIELDS] if per_point else []
+        else:
+            s = f.nearest_plane_registration_system(Qn, T, origin=c, max_distance=r, huber_delta=delta,
+                                                    per_point=per_point)
+            cols = ([getattr(s.neighbours, k) for k in FIELDS] if per_point else []) + [s.node, s.row, s.residual]
+        return [sums28(s), np.array([s.n_used, s.n_located])] + (cols if per_point else [])
+
+    def device(f, system, Qn, per_point):
+        if system == "own leaf":
+            f.leaf_planes(None)
+            return _own_leaf_device_form(f, Qn, T, c, per_point, max_distance=r, huber_delta=delta)
+        if system == "point":
+            return _point_device_form(f, Qn, T, c, r, delta, None, per_point)
+        return _device_form(f, Qn, T, c, r, 8, None, delta, None, per_point)
+
+    shared = _grid(clouds, leaf=64)._forest
+    calls = 0
+    for n in (257, 4097, 1):
+        Qn = np.ascontiguousarray(Q[:n])
+        for form in (host, device):
+            for per_point in (False, True):
+                for system in ("own leaf", "point", "nearest plane"):
+                    what = (system, form.__name__, per_point, n)
+                    got = form(shared, system, Qn, per_point)
+                    want = form(_grid(clouds, leaf=64)._forest, system, Qn, per_point)
+                    assert len(got) == len(want) and (len(got) > 2) == per_point, what
+                    for k, (a, b) in enumerate(zip(got, want)):
+                        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (what, k)
+                    assert n == 1 or 0 < got[1][0] <= got[1][1] <= n, (what, got[1])      # (used, located)
+                    calls += 1
+    assert calls == 36
